@@ -7,7 +7,12 @@ the rank's shard, inputs already resident in HBM, followed by the final gather o
 (the only collective).  Contract: W untimed warm-up steps, EXACTLY K timed steps bracketed by
 barrier + synchronize, MAX over ranks, one JSON line from rank 0.
 
+A plain run does only what that line's headline needs: set up, warm up, time the K steps, write the outputs of the
+last step (--dump-outputs DIR) and print.  --full adds the untimed extra passes: per-kernel durations on one stream,
+two handles pipelined, the CPU-oracle baseline and parity samples, the 1e-5 parity leg and the secondary workloads.
+
     python bench.py                       # 1 GPU
+    python bench.py --full                # 1 GPU, with every extra pass
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -44,6 +49,8 @@ PARITY_EPS = 3e-7
 DU_METRIC = ("per agent: max_j |U_hip[j] - U_oracle[j]| / max(1, max_j |U_oracle[j]|) -- vector-relative with a floor of 1 "
              "on the scale; the drive input saturates at |d| = 1, so this is an ABSOLUTE 1e-5 on every component, the "
              "steering angle (|delta| <= 0.32) included")
+# --dump-outputs: at most this many bytes in all; beyond it every array is cut to the same fixed, seeded sample of rows
+DUMP_BYTES = 64 << 20
 
 
 def straight_centerline(S=100):
@@ -136,6 +143,24 @@ def cpu_baseline(model, N, cfg_kw, cl, U_gpu=None, st_gpu=None, agents=None, n=4
     return base, parity
 
 
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: every array of `arrays` (name -> [rows, ...], one row per agent) as <out_dir>/<name>.npy in float64.
+    If they hold more than `budget` bytes, each keeps the rows of a fixed sample (seed 0, sorted) of the same fraction of its
+    rows, and <name>_rows.npy records which (as float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    budget -= 2 * 4096 * len(arrays)                 # room for the .npy headers
+    frac = 1.0
+    if sum(a.nbytes for a in arrays.values()) > budget:
+        frac = budget / sum(a.nbytes + 8 * len(a) for a in arrays.values())
+    for name, a in arrays.items():
+        if frac < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(len(a), int(len(a) * frac), replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def pmc_profile():
     """HBM traffic per kernel from the committed rocprofv3 counter passes (tools/profile.sh -> tools/pmc_summary.py):
     the profiles/r*_pmc_summary.json whose `library_source_sha256` is the RUNNING library's (mpc_source_hash), or
@@ -189,6 +214,11 @@ def main():
                          "0 = the library default (5000)")
     ap.add_argument("--max-total-evals", type=int, default=0, help="evaluation budget per solve (0 = none)")
     ap.add_argument("--lbfgs-memory", type=int, default=0, help="L-BFGS memory (0 = the reference's: N_horiz, controller.py:36)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the untimed extra passes (per-kernel, pipelined, CPU baseline, "
+                         "parity leg, secondary workloads); the --no-* options below skip single ones of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (controls, stats, multipliers) to DIR/<name>.npy")
     ap.add_argument("--cpu-sample", type=int, default=4096)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pipeline-pass", action="store_true",
@@ -202,6 +232,8 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--same-gpu", action="store_true", help="rehearsal: every rank uses device 0")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -243,9 +275,9 @@ def main():
     U0 = torch.tensor([1.0, 0.0], dtype=torch.float64, device=dev).repeat(B, N)   # controller.py:20
 
     def step():
-        U, _, st = eng.solve(X0, cl, U0)
+        U, lam, st = eng.solve(X0, cl, U0)
         full = gather_controls(U, B_total, dst=0)
-        return U, st, full
+        return U, lam, st, full
 
     def fence():
         if world > 1:
@@ -262,7 +294,7 @@ def main():
     ev0.record()
     infos = []
     for _ in range(args.steps):
-        U, st, full = step()
+        U, lam, st, full = step()
         infos.append(eng.last_solve_info())
     ev1.record()
     fence()
@@ -281,6 +313,14 @@ def main():
         if rank != 0:
             return
 
+    # what the timed path handed its caller in the last step: the gathered controls of all ranks; the stats and (with
+    # state constraints) the multipliers of rank 0's shard
+    if args.dump_outputs:
+        arrays = {"controls": full.cpu().numpy(), "stats": st.cpu().numpy()}
+        if lam is not None:
+            arrays["multipliers"] = lam.cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
+
     conv = float((st[:, 0] == 1).double().mean().item())
     it_mean = float(st[:, 2].mean().item()); it_max = float(st[:, 2].max().item())
     ev_mean = float(st[:, 7].mean().item()); ev_max = float(st[:, 7].max().item())
@@ -288,7 +328,7 @@ def main():
     # ---- untimed: per-kernel durations WITHOUT stream overlap (one sub-batch group, HIP events on the
     # solve's stream around sampled launch sets), the inputs of the per-kernel roofline figures
     kinfo = None
-    if rank == 0 and not args.no_kernel_pass:
+    if rank == 0 and args.full and not args.no_kernel_pass:
         eng.set_groups(1); eng.set_profile(True)
         eng.solve(X0, cl, U0)
         kinfo = eng.last_solve_info()
@@ -300,7 +340,7 @@ def main():
     # idle issue slots are filled by the next.  Reported beside `value`, never as it: a timed step above is
     # one blocking solve of one batch.
     pipe = None
-    if rank == 0 and not args.no_pipeline_pass:
+    if rank == 0 and args.full and not args.no_pipeline_pass:
         eng.set_profile(False)
         eng2 = mp.BatchedMPC(cfg, dev)
         side = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
@@ -431,7 +471,7 @@ def main():
             "note": "`value` is measured at the reference's own tolerance eps = 1e-6 (controller.py:41); north_star's parity "
                     "bar (controls within 1e-5 of the CPU path) holds for EVERY sampled agent at eps = %g: that throughput is "
                     "`parity_at_1e-5.value`, and `parity_sample.frac_dU_le_1e-5` is the fraction within the bar at `value`'s "
-                    "tolerance" % PARITY_EPS,
+                    "tolerance (both with --full)" % PARITY_EPS,
             "config": {"workload": workload,
                        "batch_per_gpu": args.batch, "horizon": N, "nx": nx, "nu": 2, "m_c": m,
                        "lbfgs_memory": int(cfg.lbfgs_memory), "tolerance": cfg.alm_eps,
@@ -472,14 +512,14 @@ def main():
             out["kernels_overlapped_ms_per_step"] = {
                 k: float(np.mean([i["kernel_ms"][k] for i in infos])) for k in infos[0]["kernel_ms"]}
         Unp, stnp = U.cpu().numpy(), st.cpu().numpy()
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             base, parity = cpu_baseline(args.model, N, cfg_kw, cl_np, Unp, stnp, n=args.cpu_sample)
             out["cpu_baseline"] = base
             out["parity_sample"] = parity
             out["solver"]["frac_dU_le_1e-5_at_this_tolerance"] = parity["frac_dU_le_1e-5"]
         # ---- reported beside the headline, never as it: the SAME batch at the loosest tolerance where north_star's
         # parity bar (controls within 1e-5 relative of the CPU path) holds for every agent of the sample
-        if not args.no_parity_leg and world == 1 and args.model == mp.MODEL_KINEMATIC:
+        if args.full and not args.no_parity_leg and world == 1 and args.model == mp.MODEL_KINEMATIC:
             eng.set_profile(False)
             kw = dict(cfg_kw, alm_eps=PARITY_EPS)
             eng_p = mp.BatchedMPC(mp.default_config(args.model, N, **kw), dev)
@@ -501,7 +541,7 @@ def main():
             del eng_p
         secondary = {}
         # ---- the reference's own model (car_dynamics.py:93-129, nx = 6; main.py:67-68 N = 12) at the same batch
-        if not args.no_secondary and world == 1 and args.model == mp.MODEL_KINEMATIC:
+        if args.full and not args.no_secondary and world == 1 and args.model == mp.MODEL_KINEMATIC:
             Np = 12
             eng_s = mp.BatchedMPC(mp.default_config(mp.MODEL_PACEJKA, Np), dev)
             Xs = torch.tensor(synthetic_states(mp.MODEL_PACEJKA, lo, hi), dtype=torch.float64, device=dev)

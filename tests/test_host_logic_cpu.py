@@ -151,3 +151,28 @@ def test_bench_uses_only_a_counter_summary_of_the_running_build(tmp_path, monkey
     _time.sleep(0.05)
     (prof / "r04b_pmc_summary.json").write_text(_json.dumps({"library_source_sha256": mine, "hbm_bytes_per_solve": 4.0}))
     assert bench.pmc_profile()[0]["hbm_bytes_per_solve"] == 4.0
+
+
+def test_bench_dump_outputs_whole_or_one_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float64 .npy files of what the timed step returned; within the byte budget the arrays
+    are written whole, beyond it every array keeps the rows of the same seeded sample (listed in <name>_rows.npy), the
+    same on every call, and all files together stay within the budget."""
+    import bench
+    U = np.arange(1000 * 40, dtype=np.float64).reshape(1000, 40)
+    st = np.arange(1000 * 8, dtype=np.float32).reshape(1000, 8)
+    bench.dump_outputs(str(tmp_path / "whole"), {"controls": U, "stats": st})
+    assert sorted(os.listdir(tmp_path / "whole")) == ["controls.npy", "stats.npy"]
+    got = np.load(tmp_path / "whole" / "stats.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, st)
+    assert np.array_equal(np.load(tmp_path / "whole" / "controls.npy"), U)
+    budget = 200_000
+    for d in ("cut1", "cut2"):
+        bench.dump_outputs(str(tmp_path / d), {"controls": U, "stats": st}, budget=budget)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= budget
+    rows = np.load(tmp_path / "cut1" / "controls_rows.npy")
+    assert 0 < len(rows) < 1000 and np.array_equal(rows, np.load(tmp_path / "cut1" / "stats_rows.npy"))
+    r = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "cut1" / "controls.npy"), U[r])
+    assert np.array_equal(np.load(tmp_path / "cut1" / "stats.npy"), st[r])
+    for f in os.listdir(tmp_path / "cut1"):
+        assert np.array_equal(np.load(tmp_path / "cut1" / f), np.load(tmp_path / "cut2" / f))

@@ -9,7 +9,7 @@ cd $R
 i=0
 for V in "$@"; do
   i=$((i+1))
-  env $V timeout -k 10 200 python bench.py --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline --no-pipeline-pass --no-parity-leg --no-secondary ${BENCH_ARGS} > $OUT/ab_$i.json 2> $OUT/ab_$i.err || { echo "variant '$V' failed"; tail -5 $OUT/ab_$i.err; exit 3; }
+  env $V timeout -k 10 200 python bench.py --full --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline --no-pipeline-pass --no-parity-leg --no-secondary ${BENCH_ARGS} > $OUT/ab_$i.json 2> $OUT/ab_$i.err || { echo "variant '$V' failed"; tail -5 $OUT/ab_$i.err; exit 3; }
   python - "$V" $OUT/ab_$i.json <<'PY'
 import json,sys
 d=json.load(open(sys.argv[2]))
