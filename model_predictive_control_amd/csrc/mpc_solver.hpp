@@ -98,6 +98,26 @@ struct Workspace {
     int Ls;                                        // stride between the two work lists
 };
 
+// The DevCfg and Workspace of a kernel whose first two parameters they are (`const DevCfg c, const Workspace w`),
+// read where a loop body uses them.  Left to itself the compiler loads their words once, before the loop, and keeps
+// them all live across it: far more than a wave's 106 scalar registers, so they were spilled into VGPR lanes and
+// moved back with v_writelane / v_readlane, one VALU issue slot each.  Taken from the kernel's argument segment
+// through an address that the empty asm makes opaque, they are scalar loads at the point of use (scalar cache
+// hits) that no pass can hoist out of the loop.  The layout is the ABI's: each argument at the next offset aligned
+// for its type (tests/test_step_kernel_registers.py checks it against the code object's metadata).
+struct KernArgs {
+    static constexpr size_t W_OFF = (sizeof(DevCfg) + alignof(Workspace) - 1) / alignof(Workspace) * alignof(Workspace);
+    const __attribute__((address_space(4))) char *p;
+    __device__ __forceinline__ explicit KernArgs(bool on = true) : p(nullptr)   // on = false (constant): no code at all
+    {
+        if (!on) return;
+        p = (const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(p));
+    }
+    __device__ __forceinline__ const DevCfg &c() const { return *(const DevCfg *)p; }
+    __device__ __forceinline__ const Workspace &w() const { return *(const Workspace *)(p + W_OFF); }
+};
+
 #ifdef MPC_DEV_STAMP
 // (timing experiments, never in the product build: -DMPC_DEV_STAMP=1 K1a (two lanes per request), 2 the fused K1b+K1c kernel,
 // 3 the step kernel, 4 K1a of the Pacejka model (four lanes per request), 5 the persistent kernel (per agent), 6 K1b (stage_kernel))
@@ -258,7 +278,7 @@ __device__ __forceinline__ double rfl(double v)
     return __hiloint2double(hi, lo);
 }
 struct RecD { // a double scalar of the agent record, held in lane `slot` of the record register
-    double &rv; const int lane, slot;
+    double &rv; const int &lane; const int slot;
     __device__ __forceinline__ operator double() const { return rdlane(rv, slot); }
     __device__ __forceinline__ RecD &operator=(double x) { rv = lane == slot ? x : rv; return *this; }
     __device__ __forceinline__ RecD &operator=(const RecD &o) { return *this = (double)o; }
@@ -266,7 +286,7 @@ struct RecD { // a double scalar of the agent record, held in lane `slot` of the
     __device__ __forceinline__ RecD &operator/=(double x) { return *this = (double)*this / x; }
 };
 struct RecI { // an integer scalar of the record (stored as 2^52 + k: rec_int)
-    double &rv; const int lane, slot;
+    double &rv; const int &lane; const int slot;
     __device__ __forceinline__ operator int() const { return __builtin_amdgcn_readlane(__double2loint(rv), slot); }
     __device__ __forceinline__ RecI &operator=(int x)
     {
@@ -599,16 +619,21 @@ __device__ __forceinline__ AgentIn<NE> load_agent(const DevCfg &c, const Workspa
 
 // HASM = false: the caller knows that the problem has no constraints (m == 0) -- every multiplier / penalty loop
 // and the eight pointers behind them drop out of the code (fewer live scalar registers in the round path's kernel).
-template <int NE, int MC, bool HASM = true>
-__device__ int advance_agent(const DevCfg &c, const Workspace &w, int a, int lane, const AgentIn<NE> &in,
+// LEAN: nothing loop-invariant is held in scalar registers across the state machine's loop -- `cfg` and `ws` are the
+// calling kernel's first two parameters and each turn re-reads what it uses of them from the argument segment
+// (KernArgs), and each turn forms the lane masks of the record's slots (lane == slot, one v_cmp) where it writes them:
+// hoisted out of the loop, 50 such masks and the configuration were live across all of it, far more than a wave's
+// 106 scalar registers, and came back from spill lanes with two v_readlane each.
+template <int NE, int MC, bool HASM = true, bool LEAN = false>
+__device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int lane, const AgentIn<NE> &in,
                              double *hist, bool hist_ready, bool allow_spec = true, bool allow_chain = false,
                              int P = 1 << 30)
 {
 #pragma clang fp contract(off)   // fixed roundings: the step kernel and the persistent kernel must agree bit for bit
-    const int n = c.n, m = HASM ? c.m : 0;
-    if (P > c.M) P = c.M;                                // ring slots of the history that the LDS copy holds (MC < 0)
+    const int n = cfg.n, m = HASM ? cfg.m : 0;
+    if (P > cfg.M) P = cfg.M;                            // ring slots of the history that the LDS copy holds (MC < 0)
     const size_t an = (size_t)a * n, am = (size_t)a * m;
-    double *recp = w.rec + (size_t)a * REC;
+    double *recp = ws.rec + (size_t)a * REC;
     // The ~50 per-agent scalars live in LDS for the duration of the step (wave-uniform values would
     // otherwise each occupy a VGPR pair next to the cached history rows).
     // The record and the four rows nearly every phase needs are requested together (one memory
@@ -617,66 +642,67 @@ __device__ int advance_agent(const DevCfg &c, const Workspace &w, int a, int lan
     double rv = in.rv;
     Row<NE> X = in.X, G = in.G, GE = in.GE, Q = in.Q, XN = in.XN;
     if (__builtin_amdgcn_readlane(__double2loint(rv), R_PHASE) == PH_DONE) return REQ_NONE;
+    int lane_r = lane;    // the lane as the record's accessors see it (LEAN: renewed at every turn of the loop below)
     // The ~50 per-agent scalars stay where they arrive: slot s of the record in lane s of `rv`.
     // A scalar is read with v_readlane when a phase needs it and written back into its lane;
     // a phase touches a handful of them, so nothing is unpacked or repacked wholesale.
-    RecD psie{rv, lane, R_PSIE};
-    RecD psik{rv, lane, R_PSI};
-    RecD Lk{rv, lane, R_L};
-    RecD gamma{rv, lane, R_GAMMA};
-    RecD phik{rv, lane, R_PHI};
-    RecD psixh{rv, lane, R_PSIXH};
-    RecD pp{rv, lane, R_PP};
-    RecD gp{rv, lane, R_GP};
-    RecD tau{rv, lane, R_TAU};
-    RecD psin{rv, lane, R_PSIN};
-    RecD Ln{rv, lane, R_LN};
-    RecD gamman{rv, lane, R_GAMMAN};
-    RecD psixhn{rv, lane, R_PSIXHN};
-    RecD gpn{rv, lane, R_GPN};
-    RecD ppn{rv, lane, R_PPN};
-    RecD sigpp{rv, lane, R_SIGPP};
-    RecD eps{rv, lane, R_EPS};
-    RecD hn2{rv, lane, R_HN2};
-    RecD hfd{rv, lane, R_HFD};
-    RecD gamma_top{rv, lane, R_GAMMA_TOP};
-    RecD Delta{rv, lane, R_DELTA};
-    RecD rho_alm{rv, lane, R_RHO};
-    RecD eps_old{rv, lane, R_EPS_OLD};
-    RecD ne1{rv, lane, R_NE1};
-    RecD ps_eps{rv, lane, R_PS_EPS};
-    RecD out_eps{rv, lane, R_OUT_EPS};
-    RecD out_delta{rv, lane, R_OUT_DELTA};
-    RecD psi_out{rv, lane, R_PSI_OUT};
+    RecD psie{rv, lane_r, R_PSIE};
+    RecD psik{rv, lane_r, R_PSI};
+    RecD Lk{rv, lane_r, R_L};
+    RecD gamma{rv, lane_r, R_GAMMA};
+    RecD phik{rv, lane_r, R_PHI};
+    RecD psixh{rv, lane_r, R_PSIXH};
+    RecD pp{rv, lane_r, R_PP};
+    RecD gp{rv, lane_r, R_GP};
+    RecD tau{rv, lane_r, R_TAU};
+    RecD psin{rv, lane_r, R_PSIN};
+    RecD Ln{rv, lane_r, R_LN};
+    RecD gamman{rv, lane_r, R_GAMMAN};
+    RecD psixhn{rv, lane_r, R_PSIXHN};
+    RecD gpn{rv, lane_r, R_GPN};
+    RecD ppn{rv, lane_r, R_PPN};
+    RecD sigpp{rv, lane_r, R_SIGPP};
+    RecD eps{rv, lane_r, R_EPS};
+    RecD hn2{rv, lane_r, R_HN2};
+    RecD hfd{rv, lane_r, R_HFD};
+    RecD gamma_top{rv, lane_r, R_GAMMA_TOP};
+    RecD Delta{rv, lane_r, R_DELTA};
+    RecD rho_alm{rv, lane_r, R_RHO};
+    RecD eps_old{rv, lane_r, R_EPS_OLD};
+    RecD ne1{rv, lane_r, R_NE1};
+    RecD ps_eps{rv, lane_r, R_PS_EPS};
+    RecD out_eps{rv, lane_r, R_OUT_EPS};
+    RecD out_delta{rv, lane_r, R_OUT_DELTA};
+    RecD psi_out{rv, lane_r, R_PSI_OUT};
     LocI phase(rv, R_PHASE);
     LocI k(rv, R_K);
-    RecI lidx{rv, lane, R_LIDX};
-    RecI lfull{rv, lane, R_LFULL};
-    RecI noprog{rv, lane, R_NOPROG};
-    RecI nJ{rv, lane, R_NJ};
-    RecI outer{rv, lane, R_OUTER};
-    RecI first{rv, lane, R_FIRST};
-    RecI init_red{rv, lane, R_INITRED};
-    RecI pen_red{rv, lane, R_PENRED};
-    RecI inner_tot{rv, lane, R_INNER_TOT};
-    RecI inner_fail{rv, lane, R_INNER_FAIL};
-    RecI status{rv, lane, R_STATUS};
-    RecI nevals{rv, lane, R_NEVALS};
-    RecI max_it{rv, lane, R_MAXIT};
-    RecI overwrite{rv, lane, R_OVERWRITE};
-    RecI fallback{rv, lane, R_FALLBACK};
-    RecI ps_status{rv, lane, R_PS_STATUS};
-    RecI ps_iters{rv, lane, R_PS_ITERS};
-    RecI out_of_iter{rv, lane, R_OUT_OF_ITER};
-    RecI spec{rv, lane, R_SPEC};
-    RecD spec_gamma{rv, lane, R_SPEC_GAMMA};
-    RecD run_mineps{rv, lane, R_RUN_MINEPS};
-    RecI run_ev0{rv, lane, R_RUN_EV0};
-    RecI memo_status{rv, lane, R_MEMO_STATUS};
-    RecI memo_iters{rv, lane, R_MEMO_ITERS};
-    RecI memo_evals{rv, lane, R_MEMO_EVALS};
-    RecD memo_mineps{rv, lane, R_MEMO_MINEPS};
-    RecD memo_eps{rv, lane, R_MEMO_EPS};
+    RecI lidx{rv, lane_r, R_LIDX};
+    RecI lfull{rv, lane_r, R_LFULL};
+    RecI noprog{rv, lane_r, R_NOPROG};
+    RecI nJ{rv, lane_r, R_NJ};
+    RecI outer{rv, lane_r, R_OUTER};
+    RecI first{rv, lane_r, R_FIRST};
+    RecI init_red{rv, lane_r, R_INITRED};
+    RecI pen_red{rv, lane_r, R_PENRED};
+    RecI inner_tot{rv, lane_r, R_INNER_TOT};
+    RecI inner_fail{rv, lane_r, R_INNER_FAIL};
+    RecI status{rv, lane_r, R_STATUS};
+    RecI nevals{rv, lane_r, R_NEVALS};
+    RecI max_it{rv, lane_r, R_MAXIT};
+    RecI overwrite{rv, lane_r, R_OVERWRITE};
+    RecI fallback{rv, lane_r, R_FALLBACK};
+    RecI ps_status{rv, lane_r, R_PS_STATUS};
+    RecI ps_iters{rv, lane_r, R_PS_ITERS};
+    RecI out_of_iter{rv, lane_r, R_OUT_OF_ITER};
+    RecI spec{rv, lane_r, R_SPEC};
+    RecD spec_gamma{rv, lane_r, R_SPEC_GAMMA};
+    RecD run_mineps{rv, lane_r, R_RUN_MINEPS};
+    RecI run_ev0{rv, lane_r, R_RUN_EV0};
+    RecI memo_status{rv, lane_r, R_MEMO_STATUS};
+    RecI memo_iters{rv, lane_r, R_MEMO_ITERS};
+    RecI memo_evals{rv, lane_r, R_MEMO_EVALS};
+    RecD memo_mineps{rv, lane_r, R_MEMO_MINEPS};
+    RecD memo_eps{rv, lane_r, R_MEMO_EPS};
     if (phase > PH_MASK) phase = (int)phase & PH_MASK;   // (a chain_block's launch tag: see chain_tag)
     double t_pp, t_gp;
     int lb_rows = 0, n_grad = 0;
@@ -685,23 +711,27 @@ __device__ int advance_agent(const DevCfg &c, const Workspace &w, int a, int lan
 
     int n_spec = 0, n_used = 0;
     bool hist_landed = false; // the LDS copy of the history has been waited for in this step
-    // Speculation: while the cost at xhat(x+) is being evaluated, the gradient the NEXT iteration
-    // needs for its Hessian-vector product (at x+ + h q_J, PH_AFTER_DL) is evaluated as well, on the
-    // second channel, assuming x+ is accepted with step gm.  Same formulas as PH_AFTER_DL on the same
-    // inputs, so the point -- and the gradient -- are bit-identical when the assumption holds.
-    auto speculate = [&](double gm) {
-        if (c.no_spec || !allow_spec) { spec = 0; return; }
-        Row<NE> xh;
-        const int nj = spec_point<NE>(c, par, n, lane, XN, GE, gm, xh);
-        spec = 0;
-        if (nj > 0 && nj < n) {
-            strow<NE>(w.xe2 + an, n, lane, xh);
-            spec = 1; spec_gamma = gm;
-            req |= REQ_SPEC; n_spec = 1;
-        }
-    };
 
     while (req == REQ_NONE && phase != PH_DONE) {
+        const KernArgs ka(LEAN);
+        const DevCfg &c = LEAN ? ka.c() : cfg;
+        const Workspace &w = LEAN ? ka.w() : ws;
+        if (LEAN) asm volatile("" : "+v"(lane_r));
+        // Speculation: while the cost at xhat(x+) is being evaluated, the gradient the NEXT iteration
+        // needs for its Hessian-vector product (at x+ + h q_J, PH_AFTER_DL) is evaluated as well, on the
+        // second channel, assuming x+ is accepted with step gm.  Same formulas as PH_AFTER_DL on the same
+        // inputs, so the point -- and the gradient -- are bit-identical when the assumption holds.
+        auto speculate = [&](double gm) {
+            if (c.no_spec || !allow_spec) { spec = 0; return; }
+            Row<NE> xh;
+            const int nj = spec_point<NE>(c, par, n, lane, XN, GE, gm, xh);
+            spec = 0;
+            if (nj > 0 && nj < n) {
+                strow<NE>(w.xe2 + an, n, lane, xh);
+                spec = 1; spec_gamma = gm;
+                req |= REQ_SPEC; n_spec = 1;
+            }
+        };
         switch (phase) {
         // ------------------------------------------------------------------ ALM outer (K5)
         case PH_OUTER_BEGIN: {
@@ -1338,13 +1368,17 @@ step_kernel(const DevCfg c, const Workspace w, int *__restrict__ lists_out,
     AgentIn<NE> nxt;
     int loc = claim();
     // (MPC_ALL_ROWS: the six-row fetch of rounds 1 - 2, for the A/B measurement and the bit-identity test)
-    const auto phase_of = [&](int l) { return c.all_rows ? -1 : (__builtin_amdgcn_readlane(phw, l) & PH_MASK); };
-    if (loc >= 0) nxt = load_agent<NE>(c, w, base + loc, lane, phase_of(loc));
+    const auto phase_of = [&](const DevCfg &cc, int l) { return cc.all_rows ? -1 : (__builtin_amdgcn_readlane(phw, l) & PH_MASK); };
+    if (loc >= 0) nxt = load_agent<NE>(c, w, base + loc, lane, phase_of(c, loc));
     while (loc >= 0) {
+        // (the kernel's parameters c and w are not used inside this loop: see KernArgs)
+        const KernArgs ka;
+        const DevCfg &c = ka.c();
+        const Workspace &w = ka.w();
         const int a = base + loc;
         const AgentIn<NE> cur = nxt;
         const int loc_next = claim();
-        if (loc_next >= 0) nxt = load_agent<NE>(c, w, base + loc_next, lane, phase_of(loc_next)); // in flight during agent a
+        if (loc_next >= 0) nxt = load_agent<NE>(c, w, base + loc_next, lane, phase_of(c, loc_next)); // in flight during agent a
         bool hist_ready = false;
         if (MC < 0) {
             // An agent that comes back from its Hessian-vector evaluation (or from the cost of a trial
@@ -1368,7 +1402,7 @@ step_kernel(const DevCfg c, const Workspace w, int *__restrict__ lists_out,
         const long long tv0 = __builtin_amdgcn_s_memrealtime();
         const int ph_in = __builtin_amdgcn_readlane(__double2loint(cur.rv), R_PHASE) & PH_MASK;
 #endif
-        const int req = advance_agent<NE, MC, HASM>(c, w, a, lane, cur, hist, hist_ready, true, /*allow_chain=*/true, P);
+        const int req = advance_agent<NE, MC, HASM, true>(c, w, a, lane, cur, hist, hist_ready, true, /*allow_chain=*/true, P);
 #if MPC_DEV_STAMP == 3
         {   // the longest agent-step of this wave: its length in 10 ns ticks (nmid, capped at 255) and the phase it came in with (nslow)
             const int dt = (int)(__builtin_amdgcn_s_memrealtime() - tv0);
