@@ -93,6 +93,11 @@ const char *mpc_last_error(void);
  * ("unknown" for a build by other means).  Committed profiles name the build they measured by it and bench.py
  * uses a profile's counters only when it matches the running library. */
 const char *mpc_source_hash(void);
+/* host-only: how the round path's step kernel with the L-BFGS history in LDS is launched for an n-variable problem
+ * with memory M and m constraints -- the history pairs P it copies into LDS (lds_pairs > 0: the MPC_LDS_PAIRS
+ * override), the launch's dynamic LDS bytes per workgroup (chain != 0: with the thread-per-agent chain blocks) and
+ * the waves per SIMD (= workgroups per CU) the kernel is compiled for, which P is sized to let share a CU */
+int mpc_step_lds_plan(int n, int M, int m, int chain, int lds_pairs, int *pairs, int *lds_bytes, int *waves_per_simd);
 
 /* a-1 (car_dynamics.py:93-132 / dynamics.py:67-119,:144-173): dx[B][nx] = f(x[B][nx], u[B][2]) */
 int mpc_rhs(mpc_handle *h, int B, const double *x, const double *u, double *dx, void *stream);

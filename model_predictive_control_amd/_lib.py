@@ -48,7 +48,7 @@ EXPORTS = [
     "mpc_eval_cost_grad_wave", "mpc_centerline_blocks", "mpc_set_nearest_blocks", "mpc_set_memo",
     "mpc_set_round_limit", "mpc_stream_concurrency", "mpc_last_solo_ms",
     "mpc_set_poll_timeout", "mpc_debug_spin", "mpc_debug_records", "mpc_debug_record_names", "mpc_source_hash",
-    "mpc_last_lookahead",
+    "mpc_last_lookahead", "mpc_step_lds_plan",
 ]
 NREC = 64
 
@@ -140,6 +140,7 @@ def load():
     L.mpc_last_solve_info2.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.mpc_last_speculation.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.mpc_last_lookahead.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.mpc_step_lds_plan.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     L.mpc_math_probe.argtypes = [vp, ci, ci, vp, vp, vp, vp]
     L.mpc_lane_payoff.argtypes = [vp, ci, ci, C.POINTER(C.c_double), vp, vp, vp, vp, vp]
     L.mpc_set_profile.argtypes = [vp, ci]

@@ -758,31 +758,37 @@ static hipEvent_t get_event(mpc_handle *h, size_t i)
     return h->ev_pool[i];
 }
 
+// LDS copy of an agent's L-BFGS history in the step kernel (MC < 0): the ring slots 0 .. P - 1, 2 P n doubles per
+// wave.  P is what lets the kernel's occupancy target (step_waves_per_simd: its workgroups per CU) share a CU's 160 KiB
+// -- 12 pairs at n = 40 for five workgroups, where an application reads 5.4 on average; a longer history reads its
+// remaining slots from global memory.  Two elements per lane (n > 64; BASELINE config 3: N = 40, n = 80, M = 40):
+// three workgroups per CU, 10 pairs of 2 x 640 B per wave at n = 80, where an application reads 11.7 on average
+// (DESIGN.md 5).  With state constraints (m > 0) the whole history.  lds_pairs > 0 (MPC_LDS_PAIRS: experiments,
+// tests) overrides the choice.
+static constexpr size_t CU_LDS_BYTES = 160 * 1024;
+static constexpr size_t STEP_LDS_RESERVE = 1024;   // per workgroup: s_req / s_next (264 B) and the allocation granule
+static int step_lds_pairs(int ne, int n, int M, int m, int lds_pairs)
+{
+    if (lds_pairs > 0) return std::max(1, std::min(M, lds_pairs));
+    if (m != 0 && ne == 1) return M;
+    const size_t per_pair = (size_t)STEP_WAVES * 2 * n * sizeof(double);
+    const int fit = (int)((CU_LDS_BYTES / step_waves_per_simd(ne, -1, m != 0) - STEP_LDS_RESERVE) / per_pair);
+    return std::max(1, std::min(M, fit));
+}
+// dynamic LDS of a step launch: the history copies of its four waves, or the chain blocks' tile if that is larger
+static size_t step_dyn_lds(int ne, int n, int P, bool chain)
+{
+    size_t lds = (size_t)STEP_WAVES * 2 * P * n * sizeof(double);
+    if (ne == 1 && chain) lds = std::max(lds, sizeof(double) * CHAIN_SLOTS * (size_t)(n + 1) + sizeof(int) * CHAIN_SLOTS);
+    return lds;
+}
+
 template <int NE, int MC>
 static void launch_step_t(mpc_handle *h, const Workspace &w, hipStream_t s, int *lists, int *counts, int *counts_next,
                           int slot_bound, int par)
 {
-    // LDS copy of an agent's L-BFGS history (MC < 0): the ring slots 0 .. P - 1.  The unconstrained variant runs four
-    // waves per SIMD (128 registers), so P is what lets four workgroups share a CU's 160 KB -- 15 pairs at n = 40,
-    // where an application reads 5.4 on average; a longer history reads its remaining slots from global memory
-    int P = h->dc.M;
-    if (MC < 0 && NE == 1 && h->dc.m == 0) {
-        const size_t per_pair = (size_t)STEP_WAVES * 2 * h->dc.n * sizeof(double);
-        const int fit = (int)((160 * 1024 / 4 - 512) / per_pair);
-        P = std::max(1, std::min(P, fit));
-    }
-    if (MC < 0 && NE == 2) {
-        // two elements per lane (n > 64; BASELINE config 3: N = 40, n = 80, M = 40), compiled for three waves per SIMD => three
-        // workgroups per CU; the LDS copy holds what fits a third of a CU's LDS -- 10 pairs of 2 x 640 B per wave at n = 80, where an
-        // application reads 11.7 pairs on average -- the rest of a long history comes from global memory.
-        // Round 4: this replaces the global-memory two-loop (MC = 0), which read every pair twice: 574 GB per solve of
-        // config 3 at full size.
-        const size_t per_pair = (size_t)STEP_WAVES * 2 * h->dc.n * sizeof(double);
-        const int fit = (int)((160 * 1024 / 3 - 1024) / per_pair);
-        P = std::max(1, std::min(P, fit));
-    }
-    if (h->lds_pairs > 0) P = std::max(1, std::min(h->dc.M, h->lds_pairs));   // MPC_LDS_PAIRS: experiments, tests
-    size_t lds = MC < 0 ? (size_t)STEP_WAVES * 2 * P * h->dc.n * sizeof(double) : 0;
+    const int P = MC < 0 ? step_lds_pairs(NE, h->dc.n, h->dc.M, h->dc.m, h->lds_pairs) : h->dc.M;
+    const int Pl = MC < 0 ? P : 0;
     // thread-per-agent blocks for the agents that wait in PH_W_LS_G (chain_block): one per 64 gradient slots the
     // finished round can have held (the same bound that sizes the K1 grids)
     // ... only while the round is a full one: the thread-per-agent chain is ~15 us long whatever the count, which a
@@ -793,13 +799,23 @@ static void launch_step_t(mpc_handle *h, const Workspace &w, hipStream_t s, int 
     if (NE == 1 && dcl.chain) {
         nchain = w.Bp / 64;
         if (slot_bound >= 0) nchain = std::min(nchain, (slot_bound + 126) / 64 + 1);
-        lds = std::max(lds, sizeof(double) * CHAIN_SLOTS * (size_t)(h->dc.n + 1) + sizeof(int) * CHAIN_SLOTS);
     }
-    // agents per workgroup: 16 per wave fills the chip from ~50 k agents; smaller batches trade
-    // throughput for latency (a wave walks its agents serially)
+    const size_t lds = step_dyn_lds(NE, h->dc.n, Pl, NE == 1 && dcl.chain);
+    // agents per workgroup: a wave walks apb / 4 agents serially, so a smaller apb trades the work per launch of
+    // a workgroup for more of them resident.  The lean variant (history in LDS, five workgroups per CU) takes 32
+    // for a sub-batch group of 16 Ki - 32 Ki agents (the headline's four groups): 512 workgroups per group launch, so
+    // the groups' step launches fill the fifth slot of every CU; a 64 Ki one-stream launch keeps 64 (its 1 024
+    // workgroups leave the fifth slots to its chain blocks).  Measured, 65 536 kinematic agents, same box
+    // (profiles/r05_experiments.txt entry 1; headline k solves/s | one-stream step kernel ms per solve):
+    //   P = 15, apb 64 (four per CU): 483.8 - 485.7 | 60.0     P = 15, apb 32: 476.7 | 63.9
+    //   P = 12, apb 64:  493.4 | 57.0     P = 12, apb 32:  499.0 | 62.5     P = 12, apb 16:  455.6 | 71.9
+    //   P = 12, apb 32 for 16 Ki groups, 64 for 64 Ki (kept): 498.8 - 499.6 | 56.4 - 56.6
+    // Pacejka (4 x 16 Ki, same kernel, all 12 pairs in LDS): apb 32 vs 64 within the spread (160.0 - 161.1 vs
+    // 159.2 - 160.7 k).  Below 16 Ki (and every other variant) as measured in round 2: B = 1 Ki, 4 Ki -> 4; 8 Ki -> 16.
     const int apb_env = h->apb_env;
+    const bool lean = MC < 0 && NE == 1 && h->dc.m == 0;
     const int apb = apb_env == 64 || apb_env == 32 || apb_env == 16 || apb_env == 8 || apb_env == 4 ? apb_env
-                  : w.B >= 16384 ? 64 : w.B >= 6144 ? 16 : 4; // measured: B = 1 Ki, 4 Ki -> 4; 8 Ki -> 16; 21 Ki -> 64
+                  : w.B >= 32768 ? 64 : w.B >= 16384 ? (lean ? 32 : 64) : w.B >= 6144 ? 16 : 4;
     const int nstep = (w.B + apb - 1) / apb;
     if (h->dc.m == 0)
         hipLaunchKernelGGL((step_kernel<NE, MC, false>), dim3((unsigned)(nstep + nchain)), dim3(64 * STEP_WAVES), lds, s,
@@ -819,6 +835,16 @@ static void launch_step(mpc_handle *h, const Workspace &w, hipStream_t s, int *l
         else launch_step_t<1, 0>(h, w, s, lists, counts, counts_next, slot_bound, par);
     } else if (!h->step_regs) launch_step_t<2, -1>(h, w, s, lists, counts, counts_next, slot_bound, par);
     else launch_step_t<2, 0>(h, w, s, lists, counts, counts_next, slot_bound, par);   // MPC_STEP_REGS: the global-memory two-loop
+}
+
+extern "C" int mpc_step_lds_plan(int n, int M, int m, int chain, int lds_pairs, int *pairs, int *lds_bytes, int *waves_per_simd)
+{
+    if (n < 1 || M < 1 || m < 0 || !pairs || !lds_bytes || !waves_per_simd) return fail(MPC_E_ARG, "mpc_step_lds_plan: bad argument");
+    const int ne = n <= 64 ? 1 : 2;
+    *pairs = step_lds_pairs(ne, n, M, m, lds_pairs);
+    *lds_bytes = (int)step_dyn_lds(ne, n, *pairs, chain != 0);
+    *waves_per_simd = step_waves_per_simd(ne, -1, m != 0);
+    return MPC_OK;
 }
 
 // The persistent wave-per-agent kernel for the agents of view `v` that are still running (`listed`:

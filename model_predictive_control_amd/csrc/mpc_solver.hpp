@@ -1209,9 +1209,9 @@ __device__ __forceinline__ int wave_append(int *counter, bool on)
 // the finished round (coalesced; K1a of this round has not run yet), the results leave through the tiles again;
 // one wave does the arithmetic, 40 elements per lane, with the sums formed as the wave reductions form them.
 // ~2 000 wave-instructions per 64 slots, against ~350 per AGENT for the wave-per-agent step.
-constexpr int CHAIN_SLOTS = 64;   // slots per workgroup: one tile of 64 x (n + 1) doubles, 21 KB at n = 40 -- under the 38 KB of
-                                  // history the wave-per-agent blocks of the launch hold, so that four workgroups of either
-                                  // kind share a CU
+constexpr int CHAIN_SLOTS = 64;   // slots per workgroup: one tile of 64 x (n + 1) doubles, 21 KB at n = 40 -- under the 31 KB of
+                                  // history the wave-per-agent blocks of the launch hold (12 pairs), so that five workgroups of
+                                  // either kind share a CU (both kinds get the launch's one dynamic-LDS size)
 __device__ __forceinline__ void chain_block(const DevCfg &c, const Workspace &w, int cb, int gpad, int par,
                                             int *__restrict__ lists_out, int *__restrict__ counts_out, double *lds)
 {
@@ -1312,14 +1312,21 @@ __device__ __forceinline__ void chain_block(const DevCfg &c, const Workspace &w,
 // gradient / cost work lists with one atomic per list, in agent order.
 constexpr int STEP_WAVES = 4;
 #ifndef MPC_STEP_WAVES_LEAN
-#define MPC_STEP_WAVES_LEAN 4
+#define MPC_STEP_WAVES_LEAN 5
 #endif
 
-// (the unconstrained one-element-per-lane variant with the history in LDS -- the benchmark's -- needs 133
-// registers: held to 128 it runs four waves per SIMD, with the LDS copy of the history capped at P pairs so that
-// four workgroups share a CU; every other variant keeps its two or three)
+// The occupancy target of a step kernel: its waves per SIMD, which -- a workgroup being one wave on each of a CU's
+// four SIMDs -- is also the number of its workgroups that share a CU.  The kernel is compiled for it (launch_bounds)
+// and the host sizes the LDS copy of the history from it (step_lds_pairs in mpc_api.hip), so the two cannot drift
+// apart.  The unconstrained one-element-per-lane variant with the history in LDS -- the benchmark's -- runs five
+// (84 VGPRs, no spills); every other variant keeps its two or three.
+__host__ __device__ constexpr int step_waves_per_simd(int ne, int mc, bool hasm)
+{
+    return (ne == 1 && mc < 0 && !hasm) ? MPC_STEP_WAVES_LEAN : (ne == 2 && mc < 0) ? 3 : 2;
+}
+
 template <int NE, int MC, bool HASM>
-__global__ void __launch_bounds__(64 * STEP_WAVES, (NE == 1 && MC < 0 && !HASM) ? MPC_STEP_WAVES_LEAN : (NE == 2 && MC < 0) ? 3 : 2)
+__global__ void __launch_bounds__(64 * STEP_WAVES, step_waves_per_simd(NE, MC, HASM))
 step_kernel(const DevCfg c, const Workspace w, int *__restrict__ lists_out,
             int *__restrict__ counts_out, int *__restrict__ counts_next, int apb, int nstep, int par, int P)
 {
