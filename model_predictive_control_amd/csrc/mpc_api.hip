@@ -43,30 +43,22 @@ struct mpc_handle {
                                 // step kernel's workgroups hold 38 KB of LDS instead of 51 (round 3): the fused kernel's
                                 // 44 KB workgroups now share a CU with them, and the stage records never leave LDS
                                 // (rounds 1 - 2: 16384 -- beyond that the two-kernel path was faster)
-    bool arrive_adjoint = false; // MPC_ARRIVE: K1c inside K1b's last-arriving stage block instead of a launch of its own
-                                 // (same bits; measured 3 % slower -- write-through record stores: DESIGN.md 6)
-    int *arrive_buf = nullptr;  // arrival counters, one per block of 64 slots
     bool quad_rollout = true;   // K1a by two (kinematic) / four (Pacejka) lanes per request (MPC_NO_QUAD: one thread)
     int pac_quad_max = 24576;   // Pacejka: requests bound of a round up to which K1a runs four lanes per request (MPC_PAC_QUAD_MAX)
-    bool step_regs = false;     // MPC_STEP_REGS at mpc_create: history rows cached in registers, not LDS
+    bool step_regs = false;     // MPC_STEP_REGS: the two-loop reads the history from global memory, not from an LDS copy
     int chain_min = 24576;      // MPC_CHAIN_MIN: requests bound of a group's round from which the thread-per-agent blocks
                                 // (chain_block) ride in its step launch.  Measured with the one-wave form (r03_experiments 18):
                                 // 65 536 agents (groups of 16 384) +1.2 % with them; 32 768 agents (groups of 10 923)
                                 // and 16 384 (groups of 8 192) -1 ... -2 %: only the full rounds of big groups
     int lds_pairs = 0;          // MPC_LDS_PAIRS: history pairs the step kernel's LDS copy holds (0 = chosen by launch_step_t)
     int num_cus = 256;
-    // block bounding boxes of the centerline table last handed to mpc_centerline_blocks
-    double *cl_boxes = nullptr;
-    size_t cl_boxes_bytes = 0;
-    const double *cl_boxes_for = nullptr; // the table they describe (device pointer identity)
-    int cl_boxes_rows = 0;
-    int nearest_mode = 2;                 // mpc_set_nearest_blocks: 0 full scan (MPC_NEAREST_SCAN), 1 block boxes (MPC_NEAREST_BLOCKS;
-                                          // measured slower: profiles/r02_nearest_blocks.txt), 2 grid of index ranges (default);
+    int nearest_mode = 2;                 // mpc_set_nearest_blocks: 0 full scan (MPC_NEAREST_SCAN), 2 grid of index ranges (default);
                                           // a table that mpc_centerline_blocks has not prepared takes the full scan
+    // the grid of index ranges of the centerline table last handed to mpc_centerline_blocks
+    const double *cl_grid_for = nullptr;             // the table the grid was prepared for (device pointer identity), or null
     double *cl_gmeta = nullptr, *cl_gxy = nullptr;   // grid placement [C][GRID_META], interleaved points [C][S][2]
     unsigned *cl_gcells = nullptr;                   // [C][GRID_CELLS]
     int cl_grid_cap = 0;                             // rows the grid buffers hold
-    bool cl_grid_ok = false;                         // the grid describes the prepared table (not built for > MPC_GRID_MAX_ROWS rows)
     int solo_all = 4096;        // a batch of at most this many agents runs in the persistent kernel from the start
                                 // (MPC_SOLO_ALL; measured: kinematic 4 096 agents 62.8 -> 53.3 ms, 8 192 worse; Pacejka 1 024)
     int solo_max = 1024;        // a group with at most this many requests per round finishes in the persistent
@@ -117,6 +109,10 @@ struct mpc_handle {
     hipEvent_t syncev = nullptr;   // bounded_sync
     hipStream_t gstream[MPC_MAX_GROUPS] = {};
     hipEvent_t gevent[MPC_MAX_GROUPS + 1] = {};
+    int check_every = 8;           // rounds per polled window of the round loop (MPC_CHECK_EVERY)
+    bool spin = false;             // the round loop busy-waits instead of napping (MPC_SPIN)
+    bool host_timing = false;      // the round loop prints its host-side times to stderr (MPC_HOST_TIMING)
+    std::string host_trace;        // file the round loop appends one line per polled window to (MPC_HOST_TRACE; empty: none)
     // staging buffers for the standalone entry points
     double *stage = nullptr;
     size_t stage_bytes = 0;
@@ -207,15 +203,6 @@ static int make_devcfg(const mpc_config &c, DevCfg &d)
     d.max_num_initial_retries = c.max_num_initial_retries; d.max_num_retries = c.max_num_retries;
     d.max_total_num_retries = c.max_total_num_retries; d.max_total_inner = c.max_total_inner;
     d.max_total_evals = c.max_total_evals;
-    d.no_spec = getenv("MPC_NO_SPEC") != nullptr;
-    d.no_memo = getenv("MPC_NO_MEMO") != nullptr;
-    d.no_la = getenv("MPC_NO_LOOKAHEAD") != nullptr;
-    d.all_rows = getenv("MPC_ALL_ROWS") != nullptr;
-    // (MPC_NO_CHAIN: never; which launches carry them is decided per launch: chain_min)
-    // (kinematic model only by default: measured on the Pacejka model, whose rounds wait for the rollout, 668 -> 699 ms per
-    // solve with them; MPC_CHAIN_MIN set explicitly turns them on for either model)
-    d.chain = getenv("MPC_NO_CHAIN") == nullptr && 2 * c.N <= 64 &&
-              (c.model == MPC_MODEL_KINEMATIC || getenv("MPC_CHAIN_MIN") != nullptr);
     d.h = c.Ts / c.nfe; d.v_ref = c.v_ref;
     for (int i = 0; i < 6; i++) { d.w[i] = c.cost_w[i]; d.g_off[i] = c.g_off[i]; d.D_lb[i] = c.D_lb[i]; d.D_ub[i] = c.D_ub[i]; }
     d.lf = c.veh[1]; d.lr = c.veh[2]; d.mass = c.veh[7]; d.inv_mass = 1.0 / c.veh[7]; d.inv_iz = 1.0 / c.veh[8];
@@ -291,6 +278,48 @@ static int probe_stream_concurrency(mpc_handle *h)
     return cached[d];
 }
 
+// The library's environment switches (README.md has the table), read once per handle by mpc_create and nowhere else:
+// they set handle fields and, from them, the DevCfg flags the kernels test.  None of them changes a result bit.
+static void read_switches(mpc_handle *h)
+{
+    const auto num = [](const char *e, int &v) { if (e) v = atoi(e); };
+    DevCfg &d = h->dc;
+    d.no_spec = getenv("MPC_NO_SPEC") != nullptr;
+    d.no_memo = getenv("MPC_NO_MEMO") != nullptr;
+    d.no_la = getenv("MPC_NO_LOOKAHEAD") != nullptr;
+    d.all_rows = getenv("MPC_ALL_ROWS") != nullptr;
+    // thread-per-agent chain blocks (MPC_NO_CHAIN: never; which launches carry them is decided per launch: chain_min).
+    // Kinematic model only by default: measured on the Pacejka model, whose rounds wait for the rollout, 668 -> 699 ms per
+    // solve with them; MPC_CHAIN_MIN set explicitly turns them on for either model.
+    const char *chain_min = getenv("MPC_CHAIN_MIN");
+    num(chain_min, h->chain_min);
+    d.chain = getenv("MPC_NO_CHAIN") == nullptr && d.n <= 64 && (h->cfg.model == MPC_MODEL_KINEMATIC || chain_min != nullptr);
+    h->step_regs = getenv("MPC_STEP_REGS") != nullptr;
+    num(getenv("MPC_LDS_PAIRS"), h->lds_pairs);
+    h->quad_rollout = getenv("MPC_NO_QUAD") == nullptr;
+    num(getenv("MPC_PAC_QUAD_MAX"), h->pac_quad_max);
+    num(getenv("MPC_WIDE_MAX"), h->wide_max);
+    num(getenv("MPC_APB"), h->apb_env);
+    h->fused_eval = getenv("MPC_UNFUSED_EVAL") == nullptr;
+    num(getenv("MPC_FUSED_MAX"), h->fused_max);
+    if (const char *e = getenv("MPC_SOLO_MAX")) h->solo_max = h->solo_all = atoi(e);
+    num(getenv("MPC_SOLO_ALL"), h->solo_all);
+    if (getenv("MPC_NEAREST_SCAN")) h->nearest_mode = 0;
+    const char *p = getenv("MPC_PROFILE");
+    h->profile = p && p[0] == '1';
+    if (const char *e = getenv("MPC_POLL_TIMEOUT_S")) { const double t = atof(e); if (t > 0.0) h->poll_timeout_s = t; }
+    num(getenv("MPC_GROUPS"), h->ngroups);
+    int check = 0;
+    num(getenv("MPC_CHECK_EVERY"), check);
+    if (check > 0) h->check_every = check;
+    h->spin = getenv("MPC_SPIN") != nullptr;
+    h->host_timing = getenv("MPC_HOST_TIMING") != nullptr;
+    if (const char *e = getenv("MPC_HOST_TRACE")) h->host_trace = e;
+    // (MPC_HW_QUEUES overrides the measurement: experiments only)
+    const char *hwq = getenv("MPC_HW_QUEUES");
+    h->hw_queues = hwq ? atoi(hwq) : probe_stream_concurrency(h);
+}
+
 extern "C" int mpc_create(const mpc_config *cfg, int device, mpc_handle **out)
 {
     if (!cfg || !out) return fail(MPC_E_ARG, "mpc_create: null argument");
@@ -303,16 +332,6 @@ extern "C" int mpc_create(const mpc_config *cfg, int device, mpc_handle **out)
     HIPCHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(MPC_E_ARG, "mpc_create: no such device");
     mpc_handle *h = new mpc_handle();
-    h->step_regs = getenv("MPC_STEP_REGS") != nullptr;
-    if (getenv("MPC_LDS_PAIRS")) h->lds_pairs = atoi(getenv("MPC_LDS_PAIRS"));
-    if (getenv("MPC_CHAIN_MIN")) h->chain_min = atoi(getenv("MPC_CHAIN_MIN"));
-    h->quad_rollout = getenv("MPC_NO_QUAD") == nullptr;
-    if (getenv("MPC_PAC_QUAD_MAX")) h->pac_quad_max = atoi(getenv("MPC_PAC_QUAD_MAX"));
-    h->arrive_adjoint = getenv("MPC_ARRIVE") != nullptr;
-    if (getenv("MPC_WIDE_MAX")) h->wide_max = atoi(getenv("MPC_WIDE_MAX"));
-    if (getenv("MPC_APB")) h->apb_env = atoi(getenv("MPC_APB"));
-    h->fused_eval = getenv("MPC_UNFUSED_EVAL") == nullptr;
-    if (getenv("MPC_FUSED_MAX")) h->fused_max = atoi(getenv("MPC_FUSED_MAX"));
     // Pacejka model: 128.  Its persistent-kernel waves take a whole SIMD each (512 registers); the 2 237 agents that four
     // groups hand over at 1 024 requests each are more than the chip's 1 024 SIMDs hold, the later groups' waves queue and
     // the ones in flight starve the other groups' rounds, while a thin Pacejka round is no slower per evaluation than a
@@ -321,13 +340,9 @@ extern "C" int mpc_create(const mpc_config *cfg, int device, mpc_handle **out)
     // a thin round, two waves per SIMD).
     h->solo_max = cfg->model == MPC_MODEL_PACEJKA ? 128 : 1024;
     h->solo_all = (cfg->model == MPC_MODEL_KINEMATIC && cfg->N <= 32) ? 4096 : 1024;
-    if (getenv("MPC_SOLO_MAX")) h->solo_max = h->solo_all = atoi(getenv("MPC_SOLO_MAX"));
-    if (getenv("MPC_SOLO_ALL")) h->solo_all = atoi(getenv("MPC_SOLO_ALL"));
-    h->nearest_mode = getenv("MPC_NEAREST_SCAN") ? 0 : getenv("MPC_NEAREST_BLOCKS") ? 1 : 2;
     h->cfg = *cfg;
     int rc = make_devcfg(*cfg, h->dc);
     if (rc) { delete h; return rc; }
-    if (h->arrive_adjoint) h->dc.chain = 0;   // (the experimental K1c-inside-K1b variant leaves no gradient-slot count for chain_block)
     h->device = device;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) {
@@ -336,13 +351,7 @@ extern "C" int mpc_create(const mpc_config *cfg, int device, mpc_handle **out)
     }
     if (e == hipSuccess) e = hipHostMalloc((void **)&h->host_counts, 512, hipHostMallocDefault);
     if (e != hipSuccess) { delete h; return fail(MPC_E_HIP, std::string("mpc_create: ") + hipGetErrorString(e)); }
-    const char *p = getenv("MPC_PROFILE");
-    h->profile = p && p[0] == '1';
-    if (getenv("MPC_POLL_TIMEOUT_S")) { const double t = atof(getenv("MPC_POLL_TIMEOUT_S")); if (t > 0.0) h->poll_timeout_s = t; }
-    const char *gq = getenv("MPC_GROUPS");
-    h->ngroups = gq ? atoi(gq) : 0;
-    // (MPC_HW_QUEUES overrides the measurement: experiments only)
-    h->hw_queues = getenv("MPC_HW_QUEUES") ? atoi(getenv("MPC_HW_QUEUES")) : probe_stream_concurrency(h);
+    read_switches(h);
     *out = h;
     return MPC_OK;
 }
@@ -358,7 +367,6 @@ extern "C" int mpc_destroy(mpc_handle *h)
     (void)hipSetDevice(h->device);
     if (h->arena) (void)hipFree(h->arena);
     if (h->stage) (void)hipFree(h->stage);
-    if (h->cl_boxes) (void)hipFree(h->cl_boxes);
     if (h->cl_gmeta) (void)hipFree(h->cl_gmeta);
     if (h->cl_gxy) (void)hipFree(h->cl_gxy);
     if (h->cl_gcells) (void)hipFree(h->cl_gcells);
@@ -387,8 +395,7 @@ static int reserve(mpc_handle *h, int B)
     const size_t nd = 8 * n + 2 * M * n + 7 * m + REC;          // agent-major doubles per agent
     const size_t nscr = (N + 1) * nx + 2 * N + N + N * JS;       // K1 scratch doubles per slot
     const size_t ni = 4;                                         // list ints per agent
-    const size_t bytes = (nd * 8 + ni * 4) * (size_t)Bp + nscr * 8 * St + 4 * St + 8 * 4 * MPC_MAX_GROUPS + 256 + 64 +
-                         4 * (St / 64 + 16) + 256;
+    const size_t bytes = (nd * 8 + ni * 4) * (size_t)Bp + nscr * 8 * St + 4 * St + 8 * 4 * MPC_MAX_GROUPS + 256 + 64 + 256;
     char *base = nullptr;
     hipError_t e = hipMalloc((void **)&base, bytes);
     if (e != hipSuccess) return fail(MPC_E_ALLOC, "workspace hipMalloc failed: " + std::string(hipGetErrorString(e)));
@@ -411,8 +418,6 @@ static int reserve(mpc_handle *h, int B)
     w.counts = ip; // 8 ints per group
     w.totals = (unsigned long long *)(ip + 8 * MPC_MAX_GROUPS);
     w.solo_ctr = (int *)(w.totals + 16); // [group][claim counter, list length]
-    h->arrive_buf = w.solo_ctr + 2 * MPC_MAX_GROUPS + 32; // [St / 64 + 16]: stage blocks done per slot block
-    w.arrive = nullptr;
     w.Bp = Bp; w.B = B; w.St = (int)St; w.Ls = Bp;
     w.ws_xe = w.xe; w.ws_ge = w.ge; w.ws_yhe = w.yhe; w.ws_Sig = w.Sig;
     HIPCHK(hipMemset(base, 0, bytes));
@@ -474,18 +479,20 @@ static bool launch_eval_t(mpc_handle *h, const Workspace &w, hipStream_t s, cons
         hipLaunchKernelGGL((rollout_kernel<MODEL>), dim3((unsigned)nblk), dim3(64), lds, s, c, w, lists, counts, nG, nC);
     if (eva) (void)hipEventRecord(eva, s);
     // (kinematic model only: the Pacejka stage needs more registers than the fused kernel leaves it)
-    if (MODEL == KIN && h->fused_eval && (!counts || (slot_bound >= 0 && slot_bound <= h->fused_max))) {
-        // K1b + K1c in one launch, stage records through LDS (see stage_adjoint_kernel)
-        constexpr int BLK = FusedBlk<MODEL>::BLK, JS = JacRec<MODEL>::SIZE;
-        const int spb = BLK / c.N;
-        const int gb = (nblk * 64 + spb - 1) / spb;
-        const size_t flds = sizeof(double) * (size_t)(JS + 1) * c.N * spb;
-        if (shared)
-            hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, true>), dim3((unsigned)gb), dim3(BLK), flds, s, c, w, counts, nG, nC, desc);
-        else
-            hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, false>), dim3((unsigned)gb), dim3(BLK), flds, s, c, w, counts, nG, nC, desc);
-        if (evb) (void)hipEventRecord(evb, s);
-        return true;
+    if constexpr (MODEL == KIN) {
+        if (h->fused_eval && (!counts || (slot_bound >= 0 && slot_bound <= h->fused_max))) {
+            // K1b + K1c in one launch, stage records through LDS (see stage_adjoint_kernel)
+            constexpr int JS = JacRec<MODEL>::SIZE;
+            const int spb = FUSED_BLK / c.N;
+            const int gb = (nblk * 64 + spb - 1) / spb;
+            const size_t flds = sizeof(double) * (size_t)(JS + 1) * c.N * spb;
+            if (shared)
+                hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, true>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c, w, counts, nG, nC, desc);
+            else
+                hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, false>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c, w, counts, nG, nC, desc);
+            if (evb) (void)hipEventRecord(evb, s);
+            return true;
+        }
     }
     // (tried: nblk rounded up to a multiple of 8, which puts every stage block of slot block sb and its adjoint
     // block on XCD sb % 8 so that K1c could read records from the L2 they were written to -- no change: the 13 MB
@@ -496,7 +503,6 @@ static bool launch_eval_t(mpc_handle *h, const Workspace &w, hipStream_t s, cons
     else
         hipLaunchKernelGGL((stage_kernel<MODEL, false>), dim3((unsigned)(nblk * c.N)), dim3(64), 0, s, c, w, counts, nG, nC, nblk);
     if (evb) (void)hipEventRecord(evb, s);
-    if (w.arrive) return true;               // K1c ran inside K1b (last-arriving stage block)
     hipLaunchKernelGGL((adjoint_kernel<MODEL>), dim3((unsigned)nblk), dim3(64), 0, s, c, w, counts, nG, nC, desc);
     return false;
 }
@@ -532,32 +538,19 @@ static int check_common(mpc_handle *h, int B, const char *who, bool from_worker 
 // the search tables to use with centerline table `cl` (all null: none prepared for it, or switched off)
 static NearTab near_for(const mpc_handle *h, const double *cl)
 {
-    NearTab nt = {nullptr, nullptr, nullptr, nullptr};
-    if (!h->cl_boxes_for || h->cl_boxes_for != cl) return nt;
-    if (h->nearest_mode == 1 && h->cl_boxes) nt.boxes = h->cl_boxes;
-    if (h->nearest_mode == 2 && h->cl_gmeta && h->cl_grid_ok) { nt.gmeta = h->cl_gmeta; nt.gcells = h->cl_gcells; nt.gxy = h->cl_gxy; }
+    NearTab nt = {nullptr, nullptr, nullptr};
+    if (h->nearest_mode == 2 && h->cl_grid_for && h->cl_grid_for == cl) { nt.gmeta = h->cl_gmeta; nt.gcells = h->cl_gcells; nt.gxy = h->cl_gxy; }
     return nt;
 }
 
 extern "C" int mpc_centerline_blocks(mpc_handle *h, const double *cl, int C, void *stream)
 {
     int rc = check_common(h, C, "mpc_centerline_blocks"); if (rc) return rc;
-    h->cl_boxes_for = nullptr; h->cl_boxes_rows = 0;
-    if (C == 0 || !cl) return MPC_OK;
-    const DevCfg &c = h->dc;
-    const int NB = (c.S - 1 + NEAR_BLK - 1) / NEAR_BLK;
-    const bool blocks = NB <= 64;         // the block search keeps one bit per block: longer tables do without it
-    const size_t bytes = sizeof(double) * 4 * (size_t)NB * (size_t)C;
-    if (blocks && bytes > h->cl_boxes_bytes) {
-        if (h->cl_boxes) { HIPCHK(hipFree(h->cl_boxes)); h->cl_boxes = nullptr; h->cl_boxes_bytes = 0; }
-        if (hipMalloc((void **)&h->cl_boxes, bytes) != hipSuccess) return fail(MPC_E_ALLOC, "centerline block table hipMalloc failed");
-        h->cl_boxes_bytes = bytes;
-    }
-    if (!blocks && h->cl_boxes) { HIPCHK(hipFree(h->cl_boxes)); h->cl_boxes = nullptr; h->cl_boxes_bytes = 0; }
+    h->cl_grid_for = nullptr;
     // the grid costs 256 KB per centerline row: a table with one row per agent keeps the full scan
-    const bool grid = C <= MPC_GRID_MAX_ROWS;
-    h->cl_grid_ok = false;
-    if (grid && C > h->cl_grid_cap) {
+    if (C == 0 || !cl || C > MPC_GRID_MAX_ROWS) return MPC_OK;
+    const DevCfg &c = h->dc;
+    if (C > h->cl_grid_cap) {
         if (h->cl_gmeta) { HIPCHK(hipFree(h->cl_gmeta)); h->cl_gmeta = nullptr; }
         if (h->cl_gxy) { HIPCHK(hipFree(h->cl_gxy)); h->cl_gxy = nullptr; }
         if (h->cl_gcells) { HIPCHK(hipFree(h->cl_gcells)); h->cl_gcells = nullptr; }
@@ -569,14 +562,10 @@ extern "C" int mpc_centerline_blocks(mpc_handle *h, const double *cl, int C, voi
         h->cl_grid_cap = C;
     }
     hipStream_t s = (hipStream_t)stream;
-    if (blocks) hipLaunchKernelGGL(cl_blocks_kernel, grid_for(C * NB, 256), dim3(256), 0, s, c, cl, C, h->cl_boxes);
-    if (grid) {
-        hipLaunchKernelGGL(cl_grid_meta_kernel, dim3((unsigned)C), dim3(64), 0, s, c, cl, C, h->cl_gmeta, h->cl_gxy);
-        hipLaunchKernelGGL(cl_grid_cells_kernel, dim3(GRID_CELLS / 256, C), dim3(256), 0, s, c, cl, C, h->cl_gmeta, h->cl_gcells);
-    }
+    hipLaunchKernelGGL(cl_grid_meta_kernel, dim3((unsigned)C), dim3(64), 0, s, c, cl, C, h->cl_gmeta, h->cl_gxy);
+    hipLaunchKernelGGL(cl_grid_cells_kernel, dim3(GRID_CELLS / 256, C), dim3(256), 0, s, c, cl, C, h->cl_gmeta, h->cl_gcells);
     HIPCHK(hipGetLastError());
-    h->cl_grid_ok = grid;
-    h->cl_boxes_for = cl; h->cl_boxes_rows = C;
+    h->cl_grid_for = cl;
     return MPC_OK;
 }
 
@@ -685,8 +674,6 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     // direct mode: the kernel reads and writes the caller's agent-major buffers in place
     Workspace w = h->ws;
     w.cl = cl; w.cl_index = cl_index; w.x0 = x0; w.near = near_for(h, cl);
-    w.arrive = h->arrive_adjoint ? h->arrive_buf : nullptr;
-    if (w.arrive) HIPCHK(hipMemsetAsync(h->arrive_buf, 0, sizeof(int) * (size_t)(h->ws.St / 64 + 16), s));
     w.xe = const_cast<double *>(U); w.ge = grad ? grad : h->ws.ws_ge;
     w.y = const_cast<double *>(y); w.Sig = c.m ? const_cast<double *>(Sigma) : h->ws.ws_Sig;
     w.yhe = (yhat && c.m) ? yhat : h->ws.ws_yhe;
@@ -740,10 +727,8 @@ extern "C" int mpc_lbfgs_apply(mpc_handle *h, int B, const double *S, const doub
     const DevCfg &c = h->dc;
     hipStream_t s = (hipStream_t)stream;
     unsigned long long *rows = h->ws.totals + 3;
-    if (c.n <= 64) {
-        if (c.M <= 20) launch_lbfgs_harness<1, 20>(c, s, B, S, Y, idx, full, mask, q, ok, rows);
-        else launch_lbfgs_harness<1, 0>(c, s, B, S, Y, idx, full, mask, q, ok, rows);
-    } else launch_lbfgs_harness<2, 0>(c, s, B, S, Y, idx, full, mask, q, ok, rows);
+    if (c.n <= 64) launch_lbfgs_harness<1, 0>(c, s, B, S, Y, idx, full, mask, q, ok, rows);
+    else launch_lbfgs_harness<2, 0>(c, s, B, S, Y, idx, full, mask, q, ok, rows);
     HIPCHK(hipGetLastError());
     return MPC_OK;
 }
@@ -828,13 +813,13 @@ static void launch_step(mpc_handle *h, const Workspace &w, hipStream_t s, int *l
                         int slot_bound, int par)
 {
     const DevCfg &c = h->dc;
-    if (c.n <= 64) { // one element per lane; history rows cached in registers up to M = 20
-        // history of one agent in LDS (12.5 KiB per wave at M n = 800: three workgroups per CU)
+    // the history read through an LDS copy (MC < 0; one element per lane: up to M n = 800, 12.5 KiB per wave), or from
+    // global memory (MC = 0: a longer history, or MPC_STEP_REGS)
+    if (c.n <= 64) {
         if (!h->step_regs && c.M * c.n <= 800) launch_step_t<1, -1>(h, w, s, lists, counts, counts_next, slot_bound, par);
-        else if (c.M <= 20) launch_step_t<1, 20>(h, w, s, lists, counts, counts_next, slot_bound, par);
         else launch_step_t<1, 0>(h, w, s, lists, counts, counts_next, slot_bound, par);
     } else if (!h->step_regs) launch_step_t<2, -1>(h, w, s, lists, counts, counts_next, slot_bound, par);
-    else launch_step_t<2, 0>(h, w, s, lists, counts, counts_next, slot_bound, par);   // MPC_STEP_REGS: the global-memory two-loop
+    else launch_step_t<2, 0>(h, w, s, lists, counts, counts_next, slot_bound, par);
 }
 
 extern "C" int mpc_step_lds_plan(int n, int M, int m, int chain, int lds_pairs, int *pairs, int *lds_bytes, int *waves_per_simd)
@@ -861,7 +846,7 @@ static void launch_solo_t(mpc_handle *h, const Workspace &v, hipStream_t s, int 
     const bool la = NE == 1 && solo_lookahead(MODEL, c.nfe, c.N, c.m, c.no_la);
     const size_t lds = sizeof(double) * SOLO_WAVES * solo_lds_doubles<MODEL>(c.nfe, c.N, c.n, c.M, MC < 0, la);
     int nblk = (bound + SOLO_WAVES - 1) / SOLO_WAVES;
-    nblk = std::max(1, std::min(nblk, 4 * SoloOcc<MODEL, MC>::WPS * h->num_cus)); // what is resident (registers); the rest queues
+    nblk = std::max(1, std::min(nblk, 4 * SoloOcc<MODEL>::WPS * h->num_cus)); // what is resident (registers); the rest queues
     if constexpr (MODEL == PAC && NE == 1) {
         if (la) {
             hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, true>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c, v, list,
@@ -879,7 +864,6 @@ static void launch_solo_m(mpc_handle *h, const Workspace &v, hipStream_t s, int 
     const DevCfg &c = h->dc;
     if (c.n <= 64) { // the same variant choice as launch_step: results do not depend on it
         if (!h->step_regs && c.M * c.n <= 800) launch_solo_t<MODEL, 1, -1>(h, v, s, ctr, listed, bound, max_trips);
-        else if (c.M <= 20) launch_solo_t<MODEL, 1, 20>(h, v, s, ctr, listed, bound, max_trips);
         else launch_solo_t<MODEL, 1, 0>(h, v, s, ctr, listed, bound, max_trips);
     } else launch_solo_t<MODEL, 2, 0>(h, v, s, ctr, listed, bound, max_trips);
 }
@@ -942,7 +926,6 @@ static Workspace group_view(const Workspace &w, const DevCfg &c, int g, int lo, 
     const size_t soff = 2 * (size_t)lo + 64 * (size_t)g; // disjoint slot intervals inside the shared scratch
     v.trajx = w.trajx + soff; v.useq = w.useq + soff; v.stage_L = w.stage_L + soff; v.jac = w.jac + soff;
     v.agent_of = w.agent_of + soff;
-    if (w.arrive) v.arrive = w.arrive + soff / 64;
     v.lists = w.lists + lo;
     v.counts = w.counts + 8 * g;
     v.B = hi - lo; v.Bp = (v.B + 63) & ~63;
@@ -976,7 +959,6 @@ static int run_solver_rounds(mpc_handle *h, hipStream_t s)
     HIPCHK(hipMemsetAsync(w.counts, 0, 8 * MPC_MAX_GROUPS * sizeof(int) + 16 * sizeof(unsigned long long) +
                                            2 * MPC_MAX_GROUPS * sizeof(int), s));
     hipLaunchKernelGGL(init_kernel, dim3((unsigned)(((size_t)B * REC + 255) / 256)), dim3(256), 0, s, c, w);
-    if (w.arrive) HIPCHK(hipMemsetAsync(h->arrive_buf, 0, sizeof(int) * (size_t)(w.St / 64 + 16), s)); // (a failed launch may have left counts)
     h->rounds = 0; h->evals_grad = 0; h->evals_cost = 0; h->eval_ms = 0.0; h->step_ms = 0.0;
     h->lbfgs_ms = 0.0; h->lbfgs_rows = 0; h->solo_agents = 0;
     for (int k = 0; k < 5; k++) { h->kernel_ms[k] = 0.0; h->kernel_launches[k] = 0; }
@@ -1036,8 +1018,7 @@ static int run_solver_rounds(mpc_handle *h, hipStream_t s)
             HIPCHK(hipStreamWaitEvent(gs[g], h->gevent[MPC_MAX_GROUPS], 0));
         }
     }
-    static const int check_env = getenv("MPC_CHECK_EVERY") ? atoi(getenv("MPC_CHECK_EVERY")) : 0;
-    const int check_every = check_env > 0 ? check_env : 8;
+    const int check_every = h->check_every;
     // Every group advances on its own: a window of `check_every` rounds is queued, its request counters are
     // copied back behind it, and the host looks at them ONE WINDOW LATE -- a second window is already queued
     // by then, so the stream does not run dry while the host decides.  The host serves whichever group's
@@ -1061,9 +1042,8 @@ static int run_solver_rounds(mpc_handle *h, hipStream_t s)
     int rc_loop = MPC_OK;
     double host_queue_s = 0.0;                  // host time spent queueing launches (MPC_HOST_TIMING: printed at the end)
     long long dry_windows = 0, first_dry_round = -1;
-    static const char *host_trace = getenv("MPC_HOST_TRACE");   // file: one line per polled window (group, round, us, requests)
-    std::vector<std::array<long long, 4>> trace;
-    static const bool host_timing = getenv("MPC_HOST_TIMING") != nullptr;
+    const bool host_trace = !h->host_trace.empty(), host_timing = h->host_timing;
+    std::vector<std::array<long long, 4>> trace;                 // MPC_HOST_TRACE: one line per polled window
     const auto t_loop0 = std::chrono::steady_clock::now();
     auto queue_window_impl = [&](int g) {       // `check_every` rounds of group g, then the copy of its counters
         GroupRun &r = gr[g];
@@ -1132,7 +1112,6 @@ static int run_solver_rounds(mpc_handle *h, hipStream_t s)
     // -- a second window is always queued behind the one polled, so a nap delays no launch -- and leaves its
     // core to whoever needs it (eight ranks on one node are eight of these loops: INTEGRATION.md 4).
     // MPC_SPIN=1 keeps the pure busy-wait.
-    static const bool spin_only = getenv("MPC_SPIN") != nullptr;
     auto last_progress = std::chrono::steady_clock::now();
     while (nactive > 0 && rc_loop == MPC_OK) {
         bool progressed = false;
@@ -1169,7 +1148,7 @@ static int run_solver_rounds(mpc_handle *h, hipStream_t s)
         if (std::chrono::duration<double>(std::chrono::steady_clock::now() - last_progress).count() > h->poll_timeout_s) {
             h->timed_out = true; rc_loop = MPC_E_HIP; break;      // no window has completed for poll_timeout_s
         }
-        if (spin_only || std::chrono::steady_clock::now() - last_progress < std::chrono::microseconds(40))
+        if (h->spin || std::chrono::steady_clock::now() - last_progress < std::chrono::microseconds(40))
             __builtin_ia32_pause();
         else
             std::this_thread::sleep_for(std::chrono::microseconds(20));
@@ -1180,7 +1159,7 @@ static int run_solver_rounds(mpc_handle *h, hipStream_t s)
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_loop0).count(),
                 host_queue_s * 1e3, launch_sets, ng, dry_windows, first_dry_round);
     if (host_trace) {
-        if (FILE *f = fopen(host_trace, "a")) {
+        if (FILE *f = fopen(h->host_trace.c_str(), "a")) {
             fprintf(f, "# solve: group, last round of the window, us since the loop began, requests of that round\n");
             for (const auto &t : trace) fprintf(f, "%lld %lld %lld %lld\n", t[0], t[1], t[2], t[3]);
             fclose(f);
@@ -1273,7 +1252,6 @@ static int solve_batch_impl(mpc_handle *h, int B, const double *x0, const double
     Workspace &w = h->ws;
     w.cl = cl; w.cl_index = cl_index; w.x0 = x0; w.xo = U; w.y = lambda; w.psi_direct = nullptr;
     w.near = near_for(h, cl);
-    w.arrive = h->arrive_adjoint ? h->arrive_buf : nullptr;
     w.xe = w.ws_xe; w.ge = w.ws_ge; w.yhe = w.ws_yhe; w.Sig = w.ws_Sig;
     rc = run_solver(h, s); if (rc) return rc;
     if (stats) hipLaunchKernelGGL(stats_kernel, grid_for(B, 256), dim3(256), 0, s, w, stats);
@@ -1423,7 +1401,8 @@ extern "C" int mpc_set_nearest_blocks(mpc_handle *h, int on)
 {
     if (!h) return fail(MPC_E_ARG, "mpc_set_nearest_blocks: null handle");
     { const int rb = refuse_if_busy(h, "mpc_set_nearest_blocks"); if (rb) return rb; }
-    if (on < 0 || on > 2) return fail(MPC_E_ARG, "mpc_set_nearest_blocks: mode is 0 (full scan), 1 (block boxes) or 2 (grid)");
+    if (on == 1) return fail(MPC_E_ARG, "mpc_set_nearest_blocks: mode 1 (the block-box search) was removed: 0 (full scan) or 2 (grid)");
+    if (on != 0 && on != 2) return fail(MPC_E_ARG, "mpc_set_nearest_blocks: mode is 0 (full scan) or 2 (grid)");
     h->nearest_mode = on;
     return MPC_OK;
 }

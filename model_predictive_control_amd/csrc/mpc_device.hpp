@@ -950,7 +950,7 @@ MPC_DEV void stage_tangents_at(const DevCfg &c, const StageInput<MODEL> &u, cons
 // car_dynamics.py:174-192: start at point 0, candidates 1..S-2, strict <.  Squared distances are
 // compared (sqrt is monotone).  cl is the flat row [x_0..x_{S-1}, y_0..y_{S-1}].
 // The squared distance is ONE fixed expression, fma(dx, dx, dy * dy), wherever it is formed: the
-// block-pruned search below must reproduce the full scan's argmin bit for bit.
+// grid search below must reproduce the full scan's argmin bit for bit.
 MPC_DEV double dist2(double cx, double cy, double px, double py)
 {
 #pragma clang fp contract(off)
@@ -988,58 +988,9 @@ MPC_DEV int nearest_index(const DevCfg &c, const double *__restrict__ cl, double
     return idx;
 }
 
-// the same argmin without looking at every point.  The candidates 0 .. S-2 are cut into
-// blocks of NEAR_BLK consecutive points whose bounding boxes [xlo, xhi, ylo, yhi] are computed once per
-// centerline row (cl_blocks_kernel).  (1) the first point of every block is a candidate like any
-// other: the best of them bounds the minimum from above; (2) a block whose box is farther than that
-// bound cannot hold the minimum -- the box distance is formed by the same expression as a point
-// distance and rounding is monotone, so "cannot" holds bit for bit; (3) the remaining blocks (one or
-// two on a smooth track) are scanned, each lane walking ITS OWN blocks through per-lane loads, so a
-// wave of cars spread along the track does not pay for the union of their neighbourhoods.  Ties go
-// to the lower index, as the reference's in-order strict "<" does.
-constexpr int NEAR_BLK = 8;
-MPC_DEV int nearest_index_blocks(const DevCfg &c, const double *__restrict__ cl, const double *__restrict__ bx,
-                                 double px, double py)
-{
-#pragma clang fp contract(off)
-    const int S = c.S, nc = S - 1, NB = (nc + NEAR_BLK - 1) / NEAR_BLK;
-    double best = dist2(cl[0], cl[S], px, py);
-    int idx = 0;
-    for (int b = 1; b < NB; b++) {                       // (1) block heads, in index order: strict "<" keeps ties low
-        const int i = b * NEAR_BLK;
-        const double d = dist2(cl[i], cl[S + i], px, py);
-        const bool lt = d < best;
-        best = lt ? d : best;
-        idx = lt ? i : idx;
-    }
-    unsigned long long mask = 0ull;
-    for (int b = 0; b < NB; b++) {                       // (2) boxes that can still hold the minimum
-        const double *q = bx + 4 * b;
-        const double ex = fmax(fmax(q[0] - px, px - q[1]), 0.0), ey = fmax(fmax(q[2] - py, py - q[3]), 0.0);
-        const double lb = fma(ex, ex, ey * ey);
-        mask |= lb <= best ? 1ull << b : 0ull;
-    }
-    while (__ballot(mask != 0ull) != 0ull) {             // (3) uniform loop, per-lane blocks
-        const bool on = mask != 0ull;
-        const int b = on ? (int)__builtin_ctzll(mask) : 0;
-        mask &= mask - 1ull;
-#pragma unroll
-        for (int j = 1; j < NEAR_BLK; j++) {             // the head (j = 0) has been looked at
-            const int i = b * NEAR_BLK + j;
-            const bool valid = on && i < nc;
-            const int ii = valid ? i : 0;
-            const double d = dist2(cl[ii], cl[S + ii], px, py);
-            const bool take = valid && (d < best || (d == best && i < idx));
-            best = take ? d : best;
-            idx = take ? i : idx;
-        }
-    }
-    return idx;
-}
-
-// SURVEY 8f-2, second form: a uniform grid over the neighbourhood of a centerline row.  Every cell holds
-// the index range [lo, hi] that is GUARANTEED to contain the full scan's answer for any query point in
-// the cell: with U = min_j (largest squared distance from the cell to point j), the nearest point of any
+// the same argmin without looking at every point, by a uniform grid over the neighbourhood of
+// a centerline row.  Every cell holds the index range [lo, hi] that is GUARANTEED to contain the full
+// scan's answer for any query point in the cell: with U = min_j (largest squared distance from the cell to point j), the nearest point of any
 // query in the cell is at most U away, so it is among the points whose smallest squared distance to
 // the cell is <= U (cl_grid_cells_kernel adds a relative 1e-9 and grows the cell by 1e-6 of its size:
 // far more than the roundings of dist2 and of the cell lookup).  The first minimum of dist2 over
@@ -1054,7 +1005,6 @@ constexpr int GRID_META = 8;        // doubles per row
 // global memory (one more trip to L2 per candidate point) -- same index either way
 constexpr int GRID_LDS_MAX_S = 512;
 struct NearTab {
-    const double *boxes;            // [C][NB][4]        block boxes (nearest_index_blocks), or null
     const double *gmeta;            // [C][GRID_META]    grid placement, or null
     const unsigned *gcells;         // [C][GRID_CELLS]   lo | hi << 16
     const double *gxy;              // [C][S][2]         interleaved points
@@ -1103,10 +1053,6 @@ MPC_DEV int nearest_lookup(const DevCfg &c, const double *__restrict__ clp, cons
         const unsigned *cells = nt.gcells + (size_t)row * GRID_CELLS;
         const double2 *__restrict__ gp = reinterpret_cast<const double2 *>(nt.gxy + (size_t)row * 2 * (size_t)c.S);
         return nearest_index_grid(c, clp, meta, cells, [=](int i) { return gp[i]; }, px, py);
-    }
-    if (nt.boxes) {
-        const int NB = (c.S - 1 + NEAR_BLK - 1) / NEAR_BLK;
-        return nearest_index_blocks(c, clp, nt.boxes + (size_t)row * NB * 4, px, py);
     }
     return nearest_index(c, clp, px, py);
 }

@@ -640,15 +640,7 @@ __device__ __forceinline__ void adjoint_rec_quad_kin(const DevCfg &c, bool is_g,
     (void)NZ;
 }
 
-// K1b.  With `w.arrive` set it also does K1c for a block of 64 slots, in the stage-block that finishes
-// last (arrival counter per slot block): the records are stored write-through (sc1: relaxed
-// agent-scope atomic stores, so no release fence), the wave drains its stores, one lane adds to the
-// counter, and the wave whose add returns N - 1 -- every other stage of these slots has then drained
-// its stores before its own add -- invalidates its L1 (agent-scope acquire) and runs the adjoint
-// recursion of its 64 slots with plain loads (the recipe of cdna_hip_programming.md, Guideline 16 R1 in
-// its counter form).  No wave waits for another one.  The adjoint launch and its place in a round's
-// chain of dependent launches disappear; the arithmetic is adjoint_rec either way: same bits.
-// (kinematic: held to 168 registers = three waves per SIMD, 144 B of scratch per lane: K1b -3.6 %)
+// K1b.  (kinematic: held to 168 registers = three waves per SIMD, 144 B of scratch per lane: K1b -3.6 %)
 #ifndef MPC_K1B_WAVES
 #define MPC_K1B_WAVES 3
 #endif
@@ -671,7 +663,6 @@ stage_kernel(const DevCfg c, const Workspace w, const int *__restrict__ counts, 
     const bool is_g = sb < sm.nblk_g;
     const int uslot = sb * 64 + threadIdx.x;
     const int raw = w.agent_of[uslot];
-    const bool arr = w.arrive != nullptr;                // uniform
     // grid search on a shared centerline: the wave keeps the row's points (1.6 KB) in LDS, so that the
     // candidate points and the three geometry points after them are LDS reads, not two more trips to L2
     extern __shared__ double2 s_xy[];
@@ -681,50 +672,30 @@ stage_kernel(const DevCfg c, const Workspace w, const int *__restrict__ counts, 
         for (int j = threadIdx.x; j < c.S; j += 64) s_xy[j] = gp[j];
         __builtin_amdgcn_wave_barrier();                                           // (all 64 lanes are still here)
     }
-    if (raw < 0 && !arr) return;
+    if (raw < 0) return;
     const int a = raw & AGENT_MASK;
     const bool ch2 = (raw & CH2_BIT) != 0;   // speculative channel: only the gradient is kept
     const size_t St = (size_t)w.St;
-    if (raw >= 0) {
-        double xs[NX], xe[NX];
+    double xs[NX], xe[NX];
 #pragma unroll
-        for (int i = 0; i < NX; i++) {
-            xs[i] = w.trajx[(size_t)(k * NX + i) * St + uslot];
-            xe[i] = w.trajx[(size_t)((k + 1) * NX + i) * St + uslot];
-        }
-        const double d = w.useq[(size_t)(2 * k) * St + uslot], dl = w.useq[(size_t)(2 * k + 1) * St + uslot];
-        const double *__restrict__ clp = SHARED_CL ? w.cl : w.cl + (size_t)w.cl_index[a] * 2 * (size_t)c.S;
-        double *const jr = w.jac + (size_t)k * JS * St + uslot;
-        double *const sl = w.stage_L + (size_t)k * St + uslot;
-        const auto put = [=](int f, double v) {
-            double *p = f == JS ? sl : jr + (size_t)f * St;
-            if (arr) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else *p = v;
-        };
-        if (is_g) stage_sens_record<MODEL>(c, xs, xe, d, dl, put);
-        Geom g;
-        if (lds_xy) {
-            const int idx = nearest_index_grid(c, clp, w.near.gmeta, w.near.gcells, [=](int i) { return s_xy[i]; }, xe[0], xe[1]);
-            load_geom_xy(s_xy, idx, g);
-        } else {
-            stage_geom(c, w, clp, SHARED_CL ? 0 : w.cl_index[a], xe[0], xe[1], g);
-        }
-        stage_record<MODEL>(c, w, a, ch2, is_g, k, xs, xe, d, dl, g, put);
+    for (int i = 0; i < NX; i++) {
+        xs[i] = w.trajx[(size_t)(k * NX + i) * St + uslot];
+        xe[i] = w.trajx[(size_t)((k + 1) * NX + i) * St + uslot];
     }
-    if (!arr) return;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's record stores have left
-    int old = 0;
-    if (threadIdx.x == 0) old = __hip_atomic_fetch_add(&w.arrive[sb], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    old = __builtin_amdgcn_readfirstlane(old);
-    if (old != c.N - 1) return;                          // uniform: not the last stage of this slot block
-    if (threadIdx.x == 0) __hip_atomic_store(&w.arrive[sb], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // for the next launch
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // drop this CU's stale L1 lines of the record block
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (raw < 0) return;
-    const double *const jac = w.jac + uslot, *const slp = w.stage_L + uslot;
-    adjoint_rec<MODEL>(c, w, a, ch2, is_g, [=](int kk, int f) {
-        return f == JS ? slp[(size_t)kk * St] : jac[((size_t)kk * JS + f) * St];
-    });
+    const double d = w.useq[(size_t)(2 * k) * St + uslot], dl = w.useq[(size_t)(2 * k + 1) * St + uslot];
+    const double *__restrict__ clp = SHARED_CL ? w.cl : w.cl + (size_t)w.cl_index[a] * 2 * (size_t)c.S;
+    double *const jr = w.jac + (size_t)k * JS * St + uslot;
+    double *const sl = w.stage_L + (size_t)k * St + uslot;
+    const auto put = [=](int f, double v) { *(f == JS ? sl : jr + (size_t)f * St) = v; };
+    if (is_g) stage_sens_record<MODEL>(c, xs, xe, d, dl, put);
+    Geom g;
+    if (lds_xy) {
+        const int idx = nearest_index_grid(c, clp, w.near.gmeta, w.near.gcells, [=](int i) { return s_xy[i]; }, xe[0], xe[1]);
+        load_geom_xy(s_xy, idx, g);
+    } else {
+        stage_geom(c, w, clp, SHARED_CL ? 0 : w.cl_index[a], xe[0], xe[1], g);
+    }
+    stage_record<MODEL>(c, w, a, ch2, is_g, k, xs, xe, d, dl, g, put);
 }
 
 // (tried: four lanes per gradient request -- lane `role` of a DPP quad owning lambda[role] and one row of the
@@ -758,18 +729,20 @@ adjoint_kernel(const DevCfg c, const Workspace w, const int *__restrict__ counts
 // first SPB threads run the cost sum and the adjoint recursion of their slot out of LDS.  The
 // N (NX^2 + NX + 2)-double record block of a gradient request (3.5 KB at N = 20, nx = 4) never goes to
 // HBM and one launch per round disappears.  Threads are stage-major (j fastest), so a wave reads
-// SPB consecutive slots per stage from the slot-indexed scratch.
-template <int MODEL> struct FusedBlk { static constexpr int BLK = MODEL == PAC ? 128 : 256; };
+// SPB consecutive slots per stage from the slot-indexed scratch.  Kinematic model only: the Pacejka stage needs more
+// registers than the fused kernel leaves it, and takes the two launches.
+constexpr int FUSED_BLK = 256;
 
 #ifndef MPC_FUSED_WAVES
 #define MPC_FUSED_WAVES 3
 #endif
 template <int MODEL, bool SHARED_CL>
-__global__ void __launch_bounds__(FusedBlk<MODEL>::BLK, (MODEL == KIN ? MPC_FUSED_WAVES : 2))
+__global__ void __launch_bounds__(FUSED_BLK, MPC_FUSED_WAVES)
 stage_adjoint_kernel(const DevCfg c, const Workspace w, const int *__restrict__ counts, int nG_imm, int nC_imm,
                      int *__restrict__ desc)
 {
-    constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE, BLK = FusedBlk<MODEL>::BLK;
+    static_assert(MODEL == KIN, "the fused K1b + K1c kernel is the kinematic model's");
+    constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE, BLK = FUSED_BLK;
     extern __shared__ double s_rec[];                    // [JS + 1][N][SPB]; row JS = stage cost
 #if MPC_DEV_STAMP == 2
     DevStamp stamp(blockIdx.x * (BLK / 64) + (threadIdx.x >> 6));
@@ -806,29 +779,19 @@ stage_adjoint_kernel(const DevCfg c, const Workspace w, const int *__restrict__ 
         }
     }
     __syncthreads();
-    if constexpr (MODEL == KIN) {
-        // the adjoint recursion by a quad of lanes per request (adjoint_rec_quad_kin): 4 SPB lanes -- more than the
-        // workgroup has threads when the horizon is shorter than four stages, hence the loop (quads stay aligned: 4 | BLK)
-        for (int t = threadIdx.x; t < 4 * SPB; t += BLK) {
-            const int j = t >> 2, comp = t & 3, uslot = slot0 + j;
-            const int raw = uslot < nslots ? w.agent_of[uslot] : -1;
-            if (raw < 0) continue;                       // (the same for the four lanes of a quad)
-            const double *const rj = s_rec + j;
-            const int a = raw & AGENT_MASK;
-            const bool ch2 = (raw & CH2_BIT) != 0;
-            double *psi_out = w.psi_direct ? w.psi_direct + a : !ch2 ? w.rec + (size_t)a * REC + R_PSIE : nullptr;
-            adjoint_rec_quad_kin(c, uslot < sm.gpad, comp, [=](int k, int f) { return rj[(size_t)f * NS + k * SPB]; },
-                                 psi_out, (ch2 ? w.ge2 : w.ge) + (size_t)a * c.n);
-        }
-        return;
+    // the adjoint recursion by a quad of lanes per request (adjoint_rec_quad_kin): 4 SPB lanes -- more than the
+    // workgroup has threads when the horizon is shorter than four stages, hence the loop (quads stay aligned: 4 | BLK)
+    for (int t = threadIdx.x; t < 4 * SPB; t += BLK) {
+        const int j = t >> 2, comp = t & 3, uslot = slot0 + j;
+        const int raw = uslot < nslots ? w.agent_of[uslot] : -1;
+        if (raw < 0) continue;                           // (the same for the four lanes of a quad)
+        const double *const rj = s_rec + j;
+        const int a = raw & AGENT_MASK;
+        const bool ch2 = (raw & CH2_BIT) != 0;
+        double *psi_out = w.psi_direct ? w.psi_direct + a : !ch2 ? w.rec + (size_t)a * REC + R_PSIE : nullptr;
+        adjoint_rec_quad_kin(c, uslot < sm.gpad, comp, [=](int k, int f) { return rj[(size_t)f * NS + k * SPB]; },
+                             psi_out, (ch2 ? w.ge2 : w.ge) + (size_t)a * c.n);
     }
-    if ((int)threadIdx.x >= SPB) return;
-    const int j = threadIdx.x, uslot = slot0 + j;
-    const int raw = uslot < nslots ? w.agent_of[uslot] : -1;
-    if (raw < 0) return;
-    const double *const rj = s_rec + j;
-    adjoint_rec<MODEL>(c, w, raw & AGENT_MASK, (raw & CH2_BIT) != 0, uslot < sm.gpad,
-                       [=](int k, int f) { return rj[(size_t)f * NS + k * SPB]; });
 }
 
 } // namespace mpc

@@ -382,15 +382,14 @@ __device__ __forceinline__ void solo_agent_la(const DevCfg &c, const Workspace &
 // waves per SIMD) it spills ~90 of them and a lone wave is no slower for it (1 024 agents: 32.5 vs 33.1 ms),
 // while twice as many agents are in flight (4 096 agents: 78 -> 53 ms).  The Pacejka variant needs all 512
 // and its long serial chains lose more to the spills than they gain (65 536 agents: 0.97 -> 1.01 s): one wave.
-// (the variant that caches twenty history pairs in registers cannot be held to 256 either)
 #ifndef MPC_SOLO_WPS_KIN
 #define MPC_SOLO_WPS_KIN 2
 #endif
-template <int MODEL, int MC> struct SoloOcc { static constexpr int WPS = (MODEL == KIN && MC <= 0) ? MPC_SOLO_WPS_KIN : 1; };
+template <int MODEL> struct SoloOcc { static constexpr int WPS = MODEL == KIN ? MPC_SOLO_WPS_KIN : 1; };
 
 // LA: the lookahead variant (host: solo_lookahead) -- a kernel of its own, so that neither holds the other's code
 template <int MODEL, int NE, int MC, bool LA = false>
-__global__ void __launch_bounds__(64 * SOLO_WAVES, (SoloOcc<MODEL, MC>::WPS))
+__global__ void __launch_bounds__(64 * SOLO_WAVES, SoloOcc<MODEL>::WPS)
 solo_kernel(const DevCfg c, const Workspace w, const int *__restrict__ list, int *__restrict__ ctr,
             long long max_trips)
 {

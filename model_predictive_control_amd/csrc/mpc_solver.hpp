@@ -6,7 +6,7 @@
 // row is one coalesced 8n-byte access, vector updates are one instruction for the whole agent and
 // inner products are wavefront shuffle reductions.  Control flow is wave-uniform (one agent per
 // wave), so nothing diverges.  The L-BFGS history rows of an agent are read ONCE per two-loop
-// recursion (K3) -- by LDS-DMA into the wave's LDS slice, or into registers (MC = 20 variant).
+// recursion (K3) -- by LDS-DMA into the wave's LDS slice -- or twice from global memory (MC = 0 variant).
 #pragma once
 #include "mpc_device.hpp"
 #include <float.h>
@@ -87,7 +87,6 @@ struct Workspace {
     double *stage_L;                               // [N][St]        stage costs (+ ALM terms)
     double *jac;                                   // [N*JS][St]     dL/dx, dL/du, stage sensitivities
     int *agent_of;                                 // [St]           agent of a slot (-1: none)
-    int *arrive;                                   // [St / 64]      stage blocks done per slot block (K1c inside K1b), or null
     const double *cl;                              // [C][2S]
     const int *cl_index;                           // [B] or null
     NearTab near;                                  // tables of the pruned nearest-point searches (all null: full scan)
@@ -156,31 +155,6 @@ __device__ __forceinline__ double dpp_xchg(double v)
     hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
     return __hiloint2double(hi, lo);
 }
-#ifdef MPC_SCAN_SUM
-// Wavefront sum as a DPP scan: four row_shr steps leave each 16-lane row's total in its last lane,
-// row_bcast:15 / row_bcast:31 (GFX9 cross-row DPP) carry the totals upwards, lane 63 ends up with
-// the sum of all 64 lanes and is read through SGPRs -- 6 x (2 v_mov_dpp + 1 v_add_f64) + 2
-// v_readlane, no LDS, no VGPR<->SGPR juggling for the cross-row part.  All lanes active.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_take(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double scan_sum(double v) // lane 63 holds the wave total afterwards
-{
-    v += dpp_take<0x111, 0xf>(v); // row_shr:1 (lanes shifted in from outside the row read 0)
-    v += dpp_take<0x112, 0xf>(v); // row_shr:2
-    v += dpp_take<0x114, 0xf>(v); // row_shr:4
-    v += dpp_take<0x118, 0xf>(v); // row_shr:8
-    v += dpp_take<0x142, 0xa>(v); // row_bcast:15 into rows 1 and 3
-    v += dpp_take<0x143, 0xc>(v); // row_bcast:31 into rows 2 and 3
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v) { return rdlane(scan_sum(v), 63); }
-#else
 __device__ __forceinline__ double row_sum16(double v)
 {
     v += dpp_xchg<0xB1>(v);  // quad_perm [1,0,3,2]
@@ -189,7 +163,6 @@ __device__ __forceinline__ double row_sum16(double v)
     v += dpp_xchg<0x140>(v); // row_mirror
     return v;
 }
-__device__ __forceinline__ double scan_sum(double v) { return row_sum16(v); }
 // The four row totals are added as (r0 + r1) + (r2 + r3).  A vector of n <= 48 (<= 32) elements leaves
 // row 3 (rows 2 and 3) all zero: their totals are skipped -- adding an exact zero changes no bit -- and
 // with them two (four) SGPR reads and an addition per sum (NROWS is what the caller knows about n).
@@ -205,7 +178,6 @@ __device__ __forceinline__ double wave_sum(double v)
     v = row_sum16(v);
     return cross_rows<4>(v);
 }
-#endif
 // reciprocal by v_rcp_f64 + two Newton steps (<= 1 ulp): the IEEE division sequence costs ~6x more
 // issue slots, and the two-loop does one per history pair
 __device__ __forceinline__ double fast_rcp(double x)
@@ -222,20 +194,6 @@ __device__ __forceinline__ double fd_step(double xx)
 #pragma clang fp contract(off)
     return cbrt(DBL_EPSILON) * (1.0 + sqrt(xx));
 }
-#ifdef MPC_SCAN_SUM
-__device__ __forceinline__ void wave_sum2(double &a, double &b)
-{
-    a = scan_sum(a); b = scan_sum(b);
-    a = rdlane(a, 63); b = rdlane(b, 63);
-}
-__device__ __forceinline__ void wave_sum3(double &a, double &b, double &c)
-{
-    a = scan_sum(a); b = scan_sum(b); c = scan_sum(c);
-    a = rdlane(a, 63); b = rdlane(b, 63); c = rdlane(c, 63);
-}
-__device__ __forceinline__ double wave_sum_n(double v, int) { return wave_sum(v); }
-__device__ __forceinline__ void wave_sum2_n(double &a, double &b, int) { wave_sum2(a, b); }
-#else
 __device__ __forceinline__ void wave_sum2(double &a, double &b)
 {
     a = row_sum16(a); b = row_sum16(b);
@@ -261,7 +219,6 @@ __device__ __forceinline__ void wave_sum3(double &a, double &b, double &c)
     b = (rdlane(b, 0) + rdlane(b, 16)) + (rdlane(b, 32) + rdlane(b, 48));
     c = (rdlane(c, 0) + rdlane(c, 16)) + (rdlane(c, 32) + rdlane(c, 48));
 }
-#endif
 __device__ __forceinline__ double wave_max(double v)
 {
     v = fmax(v, dpp_xchg<0xB1>(v)); v = fmax(v, dpp_xchg<0x4E>(v));
@@ -400,9 +357,9 @@ __device__ __forceinline__ void hist_wait()
 
 // K3: masked L-BFGS two-loop (alpaqa LBFGS::apply(q, -1, J)) for one agent held by one wave.
 // rho is recomputed on J, pairs with rho <= 0 are skipped, H0 = s'y / y'y of the newest valid
-// pair.  MC > 0: the cnt <= MC history rows are loaded once into registers and serve both loops.
-// MC < 0: Sa / Ya point at the wave's LDS copy of the agent's whole history (hist_dma), rows are
-// read from there with the next pair requested while the current one is being used.
+// pair.  MC < 0: Sa / Ya point at the wave's LDS copy of the agent's history (hist_dma), rows are
+// read from there with the next pair requested while the current one is being used.  MC = 0: Sa / Ya
+// are the history in global memory, each loop reads its rows from there.
 template <int NE, int MC>
 __device__ __forceinline__ bool lbfgs_two_loop(const DevCfg &c, const double *__restrict__ Sa,
                                                const double *__restrict__ Ya, int n, int lane,
@@ -418,20 +375,6 @@ __device__ __forceinline__ bool lbfgs_two_loop(const DevCfg &c, const double *__
     rows_read += cnt;
     double alpha_v = 0.0, rho_v = -1.0; // lane t keeps alpha_t / rho_t
     double h0 = -1.0;
-    constexpr int MCC = MC > 0 ? MC : 1;
-    Row<NE> sc[MCC], yc[MCC];
-    if (MC > 0) {
-#pragma unroll
-        for (int t = 0; t < MCC; t++) {
-            if (t < cnt) {
-                int i = lidx - 1 - t; if (i < 0) i += M;
-                sc[t] = ldrow<NE>(Sa + (size_t)i * n, n, lane);
-                yc[t] = ldrow<NE>(Ya + (size_t)i * n, n, lane);
-#pragma unroll
-                for (int e = 0; e < NE; e++) if (!inj[e]) { sc[t].v[e] = 0.0; yc[t].v[e] = 0.0; }
-            }
-        }
-    }
     auto first_loop = [&](int t, const Row<NE> &s, const Row<NE> &y) {
         double sy = 0.0, sq = 0.0;
 #pragma unroll
@@ -481,10 +424,7 @@ __device__ __forceinline__ bool lbfgs_two_loop(const DevCfg &c, const double *__
 #pragma unroll
         for (int e = 0; e < NE; e++) if (!inj[e]) { s.v[e] = 0.0; y.v[e] = 0.0; }
     };
-    if (MC > 0) {
-#pragma unroll
-        for (int t = 0; t < MCC; t++) if (t < cnt) first_loop(t, sc[t], yc[t]);
-    } else if (MC < 0) {
+    if (MC < 0) {
         Row<NE> s, y;
         load_masked(0, s, y);
         for (int t = 0; t < cnt; t++) {
@@ -499,10 +439,7 @@ __device__ __forceinline__ bool lbfgs_two_loop(const DevCfg &c, const double *__
     if (h0 < 0.0) return false;
 #pragma unroll
     for (int e = 0; e < NE; e++) if (inj[e]) q.v[e] *= h0;
-    if (MC > 0) {
-#pragma unroll
-        for (int t = MCC - 1; t >= 0; t--) if (t < cnt) second_loop(t, sc[t], yc[t]);
-    } else if (MC < 0) {
+    if (MC < 0) {
         Row<NE> s, y;
         load_masked(cnt - 1, s, y);
         for (int t = cnt - 1; t >= 0; t--) {

@@ -41,8 +41,9 @@ class BatchedMPC:
         self._pending = False       # an asynchronous solve is in flight: the worker thread owns the handle
         self._cl_key, self._cl_keep = None, None   # the centerline table the search tables were last built for
         import os
-        # nearest-point search of K1b: 2 grid of index ranges (default), 1 block boxes, 0 the full scan
-        self._nearest_blocks = 0 if "MPC_NEAREST_SCAN" in os.environ else 1 if "MPC_NEAREST_BLOCKS" in os.environ else 2
+        # nearest-point search of K1b as the library chose it at mpc_create: 2 grid of index ranges (default), 0 the
+        # full scan (MPC_NEAREST_SCAN) -- which needs no tables
+        self._nearest_blocks = 0 if "MPC_NEAREST_SCAN" in os.environ else 2
 
     def close(self):
         if getattr(self, "_h", None):
@@ -305,10 +306,11 @@ class BatchedMPC:
         _lib.check(self.lib.mpc_set_groups(self._h, int(groups)))
 
     def set_nearest_blocks(self, on=True):
-        """Nearest-point search of K1b: 0 / False the full 98-candidate scan, 1 / True the block-pruned
-        search, 2 the grid of index ranges -- the same index whichever runs."""
-        self._nearest_blocks = int(on)
-        _lib.check(self.lib.mpc_set_nearest_blocks(self._h, int(on)))
+        """Nearest-point search of K1b: 0 / False the full 98-candidate scan, 2 / True the grid of index
+        ranges -- the same index whichever runs.  (Mode 1, the block-box search, was removed: refused.)"""
+        mode = (2 if on else 0) if isinstance(on, bool) else int(on)
+        _lib.check(self.lib.mpc_set_nearest_blocks(self._h, mode))
+        self._nearest_blocks = mode
 
     def set_solo_max(self, max_requests):
         """Requests per round up to which a group finishes in the persistent wave-per-agent kernel (0 = off)."""

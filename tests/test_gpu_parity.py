@@ -122,18 +122,20 @@ def test_tracking_errors_match_oracle_and_road_py(dev, O, ref_golden):
     assert np.allclose(err[ok, 1], ref_golden["road_err"][ok, 1], rtol=1e-12, atol=1e-12)
 
 
-@pytest.mark.parametrize("mode", [1, 2])
+@pytest.mark.parametrize("mode", [2])
 @pytest.mark.parametrize("S", [100, 6, 37, 130])
 def test_block_pruned_nearest_point_is_exact(dev, O, S, mode):
-    """f-2 (car_dynamics.py:185-190): the pruned searches (mode 1: block boxes, mode 2: grid of index
-    ranges) return the reference's argmin -- first index of the minimum over the points 0 .. S-2 --
-    bit-exactly: against the full scan and against the oracle, on the straight line, the circle and the
-    ten Bezier lane-change rows; exact ties (a pose midway between two points), index-0 wins, the
-    excluded last point, far-away and non-finite poses, poses all over the grid and beyond its edge,
-    block counts that do not divide S - 1."""
-    from model_predictive_control_amd import bezier_curves as bc
+    """f-2 (car_dynamics.py:185-190): the pruned search (mode 2: grid of index ranges) returns the
+    reference's argmin -- first index of the minimum over the points 0 .. S-2 -- bit-exactly: against
+    the full scan and against the oracle, on the straight line, the circle and the ten Bezier
+    lane-change rows; exact ties (a pose midway between two points), index-0 wins, the excluded last
+    point, far-away and non-finite poses, poses all over the grid and beyond its edge.  Mode 1 (the
+    block-box search) was removed: it is refused."""
+    from model_predictive_control_amd import _lib, bezier_curves as bc
     cfg, ocfg = both(O, 1, 12, S=S)
     eng = mp.BatchedMPC(cfg, dev)
+    with pytest.raises(_lib.MpcError, match="removed"):
+        eng.set_nearest_blocks(1)
     th = np.linspace(0, 2 * np.pi, S)
     grid = np.stack([np.arange(S, dtype=float), np.zeros(S)], 1).ravel(order="F")      # integer coordinates: exact ties
     zig = np.stack([np.arange(S) * 0.25, (np.arange(S) % 3) * 0.5], 1).ravel(order="F")
@@ -845,8 +847,8 @@ def _lbfgs_reference(S, Y, idx, full, mask, q):
 
 @pytest.mark.parametrize("N,M", [(12, 12), (20, 20), (40, 40), (9, 5)])
 def test_lbfgs_two_loop_matches_reference_recursion(dev, N, M):
-    """K3 (a-11): register-resident (n = 24, 40), re-reading (n = 80) and generic (n = 18) variants;
-    empty history, partially filled ring, wrapped ring, negative-curvature pairs, one-index J."""
+    """K3 (a-11): the two-loop that reads the history from global memory, one element per lane (n = 18, 24, 40)
+    and two (n = 80); empty history, partially filled ring, wrapped ring, negative-curvature pairs, one-index J."""
     n, B = 2 * N, 70
     eng = mp.BatchedMPC(mp.default_config(0, N, lbfgs_memory=M), dev)
     rng = np.random.default_rng(N)
@@ -956,9 +958,9 @@ def test_evaluation_budget_matches_oracle(dev, O):
 
 
 def test_step_kernel_variants_are_bit_identical(dev, monkeypatch):
-    """The step kernel keeps an agent's L-BFGS history either in LDS (LDS-DMA, default while
-    M n <= 800) or in registers (MPC_STEP_REGS / larger n): same arithmetic, same order, so the
-    two give the same bits; N = 32 (n = 64) takes the register variant by itself."""
+    """The step kernel reads an agent's L-BFGS history either from an LDS copy (LDS-DMA, default while
+    M n <= 800) or from global memory (MPC_STEP_REGS / larger M n): same arithmetic, same order, so the
+    two give the same bits; N = 32 (n = 64, M n = 2048) takes the global-memory variant by itself."""
     monkeypatch.setenv("MPC_SOLO_MAX", "0")      # the round path (the persistent kernel has its own test)
     monkeypatch.delenv("MPC_NO_SPEC", raising=False)   # (the speculation counters below are part of the subject)
     B, N = 300, 20
@@ -1027,12 +1029,8 @@ def test_wide_rollout_is_bit_identical(dev, monkeypatch, N):
     assert torch.equal(Uw, Us) and torch.equal(stw, sts) and es.last_solve_info()["spec_issued"] == 0
     monkeypatch.setenv("MPC_UNFUSED_EVAL", "1")                          # K1b and K1c as two launches
     Uu, _, stu = mp.BatchedMPC(cfg, dev).solve(X0, cl, U0)
-    assert torch.equal(Uw, Uu) and torch.equal(stw, stu)
-    monkeypatch.setenv("MPC_ARRIVE", "1")                                # ... K1c inside K1b's last-arriving stage block
-    Uv, _, stv = mp.BatchedMPC(cfg, dev).solve(X0, cl, U0)               # (arrival counters, write-through records)
-    monkeypatch.delenv("MPC_ARRIVE")
     monkeypatch.delenv("MPC_UNFUSED_EVAL")
-    assert torch.equal(Uw, Uv) and torch.equal(stw, stv)
+    assert torch.equal(Uw, Uu) and torch.equal(stw, stu)
     monkeypatch.setenv("MPC_APB", "64")                                  # 64 agents per step workgroup, not 4
     Ua, _, sta = mp.BatchedMPC(cfg, dev).solve(X0, cl, U0)
     monkeypatch.delenv("MPC_APB")
@@ -1200,7 +1198,7 @@ def test_persistent_kernel_is_bit_identical(dev, model, N, B, kw):
     """The persistent wave-per-agent kernel (mpc_solo.hpp: a wave solves an agent start to finish
     without returning to the host) against the round path, and a switch from rounds to it in
     mid-solve: same controls, multipliers and statistics, bit for bit -- it runs the same device
-    functions.  Covers every step-kernel variant (history in LDS / registers / HBM, two elements per
+    functions.  Covers every step-kernel variant (history in LDS / HBM, two elements per
     lane), both models, per-agent centerline rows and the ALM path."""
     from model_predictive_control_amd import bezier_curves as bc
     x0 = synthetic_states(model, B, seed=17)

@@ -176,3 +176,25 @@ def test_bench_dump_outputs_whole_or_one_fixed_sample(tmp_path):
     assert np.array_equal(np.load(tmp_path / "cut1" / "stats.npy"), st[r])
     for f in os.listdir(tmp_path / "cut1"):
         assert np.array_equal(np.load(tmp_path / "cut1" / f), np.load(tmp_path / "cut2" / f))
+
+
+def test_readme_switch_table_names_every_switch_read():
+    """README.md's table of environment switches names exactly the MPC_* variables the library reads (getenv in
+    csrc/, all in read_switches) and the package reads (os.environ): a switch added, renamed or removed in the code
+    must show in the table, and the table keeps no switch that is gone."""
+    import re
+    from conftest import ROOT
+    pkg = os.path.join(ROOT, "model_predictive_control_amd")
+    read = set()
+    for f in os.listdir(os.path.join(pkg, "csrc")):
+        read |= set(re.findall(r'getenv\("(MPC_\w+)"\)', open(os.path.join(pkg, "csrc", f)).read()))
+    for f in os.listdir(pkg):
+        if f.endswith(".py"):
+            for line in open(os.path.join(pkg, f)):
+                if "os.environ" in line:
+                    read |= set(re.findall(r'"(MPC_\w+)"', line))
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    table = re.findall(r"^\| `(MPC_\w+)` \|", readme, re.M)
+    assert len(table) == len(set(table)), "a switch is listed twice"
+    assert set(table) == read
+    assert "MPC_STEP_REGS" in read and "MPC_LIB_PATH" in read       # (both sources were searched)

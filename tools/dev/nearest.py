@@ -1,4 +1,4 @@
-"""Development script: timing of K1 with the block-pruned nearest-point search on / off."""
+"""Development script: timing of K1 and of a solve with the grid nearest-point search (mode 2) and the full scan (0)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
@@ -11,7 +11,7 @@ X0 = torch.tensor(bench.synthetic_states(0, 0, B), dtype=torch.float64, device=d
 U0 = torch.tensor([1.0, 0.0], dtype=torch.float64, device=dev).repeat(B, N)
 eng = mp.BatchedMPC(mp.default_config(0, N), dev)
 for rep in range(2):
-    for on in (2, 1, 0):
+    for on in (2, 0):
         eng.set_nearest_blocks(on)
         for wg in (True, False):
             eng.eval_cost_grad(X0, cl, U0, want_grad=wg)
