@@ -99,6 +99,25 @@ const char *mpc_source_hash(void);
  * the waves per SIMD (= workgroups per CU) the kernel is compiled for, which P is sized to let share a CU */
 int mpc_step_lds_plan(int n, int M, int m, int chain, int lds_pairs, int *pairs, int *lds_bytes, int *waves_per_simd);
 
+/* Per-agent vehicle and cost parameters: a table of P rows in device memory and one row index per agent, beside
+ * the centerline table.  One row, all doubles: [0..21] veh (car_dynamics.py:65-88 order, as mpc_config.veh),
+ * [22] accel, [23] friction (dynamics.py:34-35), [24] v_ref, [25..30] cost_w (car_dynamics.py:230) -- in the
+ * reference these are run-time data of the problem (main.py:30, :119 `prob.param`), not part of its construction.
+ * mpc_default_params (host only): the row `cfg` describes.
+ * mpc_set_agent_params: table == NULL unbinds (the handle is then what it was before).  Bound, the calls that
+ * evaluate the model -- mpc_rhs, mpc_rollout, mpc_stage_cost, mpc_eval_cost_grad(_wave), mpc_solve_batch(_async),
+ * mpc_closed_loop -- use row index[b] for agent b and return MPC_E_ARG for a batch size other than B;
+ * mpc_closed_loop advances the plant with row plant_index[b] (NULL: the same rows; main.py:145's separate `param`).
+ * The input box, the constraint data, Ts, N and every solver parameter stay the handle's.  table [P][MPC_NPARAM],
+ * index [B] and plant_index [B] are DEVICE memory of the caller, read at every call: rows may be rewritten in place
+ * between calls without binding again.  The P rows are checked once, at bind time, through a synchronous copy:
+ * every value finite, veh[1] + veh[2] > 0, and on the Pacejka model veh[7] > 0 and veh[8] > 0; index ranges are the
+ * caller's to check (the Python front end does).  Refused (MPC_E_ARG) while an asynchronous solve is in flight. */
+#define MPC_NPARAM 31
+int mpc_default_params(const mpc_config *cfg, double *row);
+int mpc_set_agent_params(mpc_handle *h, const double *table, int P, const int32_t *index,
+                         const int32_t *plant_index, int B);
+
 /* a-1 (car_dynamics.py:93-132 / dynamics.py:67-119,:144-173): dx[B][nx] = f(x[B][nx], u[B][2]) */
 int mpc_rhs(mpc_handle *h, int B, const double *x, const double *u, double *dx, void *stream);
 

@@ -48,9 +48,12 @@ EXPORTS = [
     "mpc_eval_cost_grad_wave", "mpc_centerline_blocks", "mpc_set_nearest_blocks", "mpc_set_memo",
     "mpc_set_round_limit", "mpc_stream_concurrency", "mpc_last_solo_ms",
     "mpc_set_poll_timeout", "mpc_debug_spin", "mpc_debug_records", "mpc_debug_record_names", "mpc_source_hash",
-    "mpc_last_lookahead", "mpc_step_lds_plan",
+    "mpc_last_lookahead", "mpc_step_lds_plan", "mpc_default_params", "mpc_set_agent_params",
 ]
 NREC = 64
+NPARAM = 31     # MPC_NPARAM: doubles per row of the per-agent parameter table
+# columns of a row, by field name (include/mpc_hip.h: mpc_set_agent_params)
+PARAM_FIELDS = {"veh": (0, 22), "accel": (22, 1), "friction": (23, 1), "v_ref": (24, 1), "cost_w": (25, 6)}
 
 
 class MpcConfig(C.Structure):
@@ -140,6 +143,8 @@ def load():
     L.mpc_last_solve_info2.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.mpc_last_speculation.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.mpc_last_lookahead.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.mpc_default_params.argtypes = [cp, C.POINTER(C.c_double)]
+    L.mpc_set_agent_params.argtypes = [vp, vp, ci, vp, vp, ci]
     L.mpc_step_lds_plan.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     L.mpc_math_probe.argtypes = [vp, ci, ci, vp, vp, vp, vp]
     L.mpc_lane_payoff.argtypes = [vp, ci, ci, C.POINTER(C.c_double), vp, vp, vp, vp, vp]
@@ -180,6 +185,45 @@ def default_config(model=MODEL_PACEJKA, N=12, **overrides):
         else:
             setattr(cfg, k, v)
     return cfg
+
+
+def default_params(cfg):
+    """mpc_default_params: the row of the per-agent parameter table that `cfg` describes, float64 [NPARAM]."""
+    import numpy as np
+    row = (C.c_double * NPARAM)()
+    rc = load().mpc_default_params(C.byref(cfg), row)
+    if rc != 0:
+        raise ValueError(load().mpc_last_error().decode())
+    return np.array(row[:], dtype=np.float64)
+
+
+def param_rows(cfg, P, **overrides):
+    """A parameter table for BatchedMPC.set_agent_params, on the host: float64 [P, NPARAM] whose rows are
+    default_params(cfg) with overrides by field name -- `veh` [P, 22] (or [22]: every row), `cost_w` [P, 6] (or [6]),
+    `accel`, `friction`, `v_ref` [P] (or a scalar).  Pure host code: usable without a GPU."""
+    import numpy as np
+    P = int(P)
+    if P < 1:
+        raise ValueError("param_rows: P must be >= 1")
+    tab = np.tile(default_params(cfg), (P, 1))
+    for name, val in overrides.items():
+        if name not in PARAM_FIELDS:
+            raise ValueError(f"param_rows: unknown field {name!r} (one of {sorted(PARAM_FIELDS)})")
+        off, width = PARAM_FIELDS[name]
+        v = np.asarray(val, dtype=np.float64)
+        if width == 1:
+            if v.ndim == 0:
+                v = np.full(P, float(v))
+            if v.shape != (P,):
+                raise ValueError(f"param_rows: {name} must be a scalar or have shape ({P},), got {v.shape}")
+            tab[:, off] = v
+        else:
+            if v.shape == (width,):
+                v = np.tile(v, (P, 1))
+            if v.shape != (P, width):
+                raise ValueError(f"param_rows: {name} must have shape ({width},) or ({P}, {width}), got {v.shape}")
+            tab[:, off:off + width] = v
+    return tab
 
 
 def library_hash():

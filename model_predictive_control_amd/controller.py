@@ -58,6 +58,8 @@ class MPCController:
             max_total_inner=int(getattr(problem, "max_total_inner", 5000)))
         self.solver = BatchedMPC(self.cfg)
         self.device = self.solver.device
+        self._veh0 = veh.copy()      # the vehicle part of problem.param the handle was created from
+        self._nx, self._S = nx, S
         self._constrained = constrained
         self.last_stats = None
 
@@ -73,8 +75,21 @@ class MPCController:
         U0 = torch.as_tensor(np.asarray(self.U, dtype=np.float64)[None, :], device=dev)
         lam0 = torch.as_tensor(np.asarray(self.λ, dtype=np.float64)[None, :], device=dev) \
             if self._constrained else None
-        # controller.py:57: warm start from the previous solution and multipliers
-        U, lam, stats = self.solver.solve(x0.contiguous(), cl.contiguous(), U0.contiguous(), lam0)
+        # main.py:119: the vehicle parameters are run-time data of the problem.  A caller who has rewritten them in
+        # problem.param since construction is served through a one-row parameter table holding the new values;
+        # unchanged parameters take the handle's own path.
+        veh = np.asarray(self.problem.param[self._nx + 2 * self._S:], dtype=np.float64)
+        changed = veh.shape != self._veh0.shape or not np.array_equal(veh, self._veh0)
+        if changed:
+            row = _lib.param_rows(self.cfg, 1, veh=veh)
+            self.solver.set_agent_params(torch.as_tensor(row, device=dev).contiguous(),
+                                         torch.zeros(1, dtype=torch.int32, device=dev))
+        try:
+            # controller.py:57: warm start from the previous solution and multipliers
+            U, lam, stats = self.solver.solve(x0.contiguous(), cl.contiguous(), U0.contiguous(), lam0)
+        finally:
+            if changed:
+                self.solver.clear_agent_params()
         st = stats.cpu().numpy()[0]
         self.U = U.cpu().numpy()[0]
         if lam is not None:
@@ -87,8 +102,10 @@ class MPCController:
         return self.U                                          # controller.py:69
 
     # ------------------------------------------------------------------ batched entry points
-    def solve(self, Y0, centerline, U0=None, lam0=None, cl_index=None):
-        """Batched solve: Y0 [B, nx], centerline [2S] or [C, 2S] (+ cl_index[B]) -> (U [B, 2N], stats)."""
+    def solve(self, Y0, centerline, U0=None, lam0=None, cl_index=None, params=None, param_index=None):
+        """Batched solve: Y0 [B, nx], centerline [2S] or [C, 2S] (+ cl_index[B]) -> (U [B, 2N], stats).
+        params [P, 31] (rows as _lib.param_rows makes them) + param_index [B] (None: agent b uses row b % P): this
+        solve runs agent b on its own vehicle and cost parameters (BatchedMPC.set_agent_params)."""
         dev = self.device
         Y0 = torch.as_tensor(Y0, dtype=torch.float64, device=dev).contiguous()
         B = Y0.shape[0]
@@ -101,15 +118,27 @@ class MPCController:
             cl_index = torch.as_tensor(cl_index, dtype=torch.int32, device=dev).contiguous()
         if lam0 is not None:
             lam0 = torch.as_tensor(lam0, dtype=torch.float64, device=dev).contiguous()
-        U, lam, stats = self.solver.solve(Y0, cl, U0, lam0 if self._constrained else None, cl_index)
+        if params is None and param_index is not None:
+            raise ValueError("param_index needs params")
+        if params is not None:
+            params = torch.as_tensor(params, dtype=torch.float64, device=dev).contiguous()
+            if param_index is None:
+                param_index = torch.arange(B, device=dev) % params.shape[0]
+            param_index = torch.as_tensor(param_index, device=dev).to(torch.int32).contiguous()
+            self.solver.set_agent_params(params, param_index)
+        try:
+            U, lam, stats = self.solver.solve(Y0, cl, U0, lam0 if self._constrained else None, cl_index)
+        finally:
+            if params is not None:
+                self.solver.clear_agent_params()
         self.last_stats = stats
         self.tot_it += int(stats[:, 2].sum().item())
         self.failures += int((stats[:, 0] != _lib.ST_CONVERGED).sum().item())
         return U, stats
 
-    def step(self, Y0, centerline, U0=None, lam0=None, cl_index=None):
+    def step(self, Y0, centerline, U0=None, lam0=None, cl_index=None, params=None, param_index=None):
         """First control of every agent, u0 [B, 2] (main.py:141 input_to_matrix(U)[:, 0])."""
-        U, _ = self.solve(Y0, centerline, U0, lam0, cl_index)
+        U, _ = self.solve(Y0, centerline, U0, lam0, cl_index, params, param_index)
         return U[:, :2].contiguous()
 
 

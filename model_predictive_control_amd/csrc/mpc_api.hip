@@ -66,9 +66,9 @@ struct mpc_handle {
                                 // Default 1024 (kinematic model, measured in round 2, also for N = 40: profiles/r02c_*),
                                 // 128 on the Pacejka model (round 4: mpc_create)
     int Bp_alloc = 0;      // workspace capacity (agents)
-    char *arena = nullptr; // one device allocation carved into the Workspace arrays
+    char *arena = nullptr; // one device allocation carved into the WorkspacePA arrays
     size_t arena_bytes = 0;
-    Workspace ws{};
+    WorkspacePA ws{};
     int *host_counts = nullptr; // pinned, 512 B: [2 poll windows][MPC_MAX_GROUPS][2] ints, then (byte 128) the sixteen totals of a
                                 // solve (16 x 8 B) and (byte 256) the persistent kernel's counters -- copies into pageable memory would
                                 // block the host until the stream has drained, whatever the wall-clock bound says
@@ -113,6 +113,12 @@ struct mpc_handle {
     bool spin = false;             // the round loop busy-waits instead of napping (MPC_SPIN)
     bool host_timing = false;      // the round loop prints its host-side times to stderr (MPC_HOST_TIMING)
     std::string host_trace;        // file the round loop appends one line per polled window to (MPC_HOST_TRACE; empty: none)
+    // mpc_set_agent_params: the caller's parameter table and row indices (device memory, read at every call; all null:
+    // none bound, every agent runs the handle's values through the kernels that have always run)
+    const double *ptab = nullptr;          // [ptab_rows][MPC_NPARAM]
+    const int32_t *pidx = nullptr;         // [ptab_B] the controller's row per agent
+    const int32_t *pidx_plant = nullptr;   // [ptab_B] the plant's row per agent (mpc_closed_loop), null: pidx
+    int ptab_rows = 0, ptab_B = 0;
     // staging buffers for the standalone entry points
     double *stage = nullptr;
     size_t stage_bytes = 0;
@@ -169,6 +175,16 @@ static int stage_m(const mpc_config *c)
     return c->constr_mode == MPC_CONSTR_STATE_SQ ? mpc_nx(c) : c->constr_mode == MPC_CONSTR_LANE ? 1 : 0;
 }
 extern "C" int mpc_m(const mpc_config *c) { return stage_m(c) * c->N; }
+
+static_assert(MPC_NPARAM == mpc::NPARAM, "row layout: include/mpc_hip.h and mpc_device.hpp");
+extern "C" int mpc_default_params(const mpc_config *c, double *row)
+{
+    if (!c || !row) return fail(MPC_E_ARG, "mpc_default_params: null argument");
+    for (int i = 0; i < 22; i++) row[i] = c->veh[i];
+    row[22] = c->accel; row[23] = c->friction; row[24] = c->v_ref;
+    for (int i = 0; i < 6; i++) row[25 + i] = c->cost_w[i];
+    return MPC_OK;
+}
 
 static int make_devcfg(const mpc_config &c, DevCfg &d)
 {
@@ -400,7 +416,7 @@ static int reserve(mpc_handle *h, int B)
     hipError_t e = hipMalloc((void **)&base, bytes);
     if (e != hipSuccess) return fail(MPC_E_ALLOC, "workspace hipMalloc failed: " + std::string(hipGetErrorString(e)));
     h->arena = base; h->arena_bytes = bytes; h->Bp_alloc = Bp;
-    Workspace &w = h->ws;
+    WorkspacePA &w = h->ws;
     double *dp = (double *)base;
     auto takeD = [&](size_t cnt) { double *r = dp; dp += cnt * (size_t)Bp; return r; };
     w.xk = takeD(n); w.gk = takeD(n); w.q = takeD(n); w.xn = takeD(n); w.xe = takeD(n); w.ge = takeD(n);
@@ -434,15 +450,25 @@ static int reserve_stage(mpc_handle *h, size_t bytes)
     return MPC_OK;
 }
 
+// a handle with a parameter table serves the batch size the table's indices were bound for, and no other
+static int check_bound(const mpc_handle *h, int B, const char *who)
+{
+    if (h->ptab && B != h->ptab_B)
+        return fail(MPC_E_ARG, std::string(who) + ": the bound parameter table is for a batch of " + std::to_string(h->ptab_B) +
+                               " agents, this call has " + std::to_string(B) + " (mpc_set_agent_params)");
+    return MPC_OK;
+}
+
 static inline dim3 grid_for(int B, int block) { return dim3((unsigned)((B + block - 1) / block)); }
 
 template <int MODEL>
-static bool launch_eval_t(mpc_handle *h, const Workspace &w, hipStream_t s, const int *lists, const int *counts,
+static bool launch_eval_t(mpc_handle *h, const WorkspacePA &w, hipStream_t s, const int *lists, const int *counts,
                           int nG, int nC, hipEvent_t eva = nullptr, hipEvent_t evb = nullptr, int slot_bound = -1,
                           int *desc = nullptr)
 {
     const DevCfg &c = h->dc;
     const bool shared = w.cl_index == nullptr;
+    const bool pa = w.ptab != nullptr;   // a parameter table is bound: the per-agent instantiation of every K1 kernel
     // list mode: the grid covers the most requests the round can hold -- every agent on both lists
     // (cost + speculative gradient), or the caller's tighter bound (blocks beyond the lists exit at once,
     // but late in a solve dispatching thousands of them costs more than the work)
@@ -454,15 +480,20 @@ static bool launch_eval_t(mpc_handle *h, const Workspace &w, hipStream_t s, cons
     if constexpr (MODEL == KIN) {
         // few requests (late rounds of a solve, small batches): one wave per request, see rollout_wide_kernel
         wide = counts && slot_bound >= 0 && slot_bound <= h->wide_max && c.nfe == 4 && c.N <= 64;
-        if (wide)
-            hipLaunchKernelGGL(rollout_wide_kernel, dim3((unsigned)(nblk * 16)), dim3(256), 0, s, c, w, lists, counts);
+        if (wide && pa)
+            hipLaunchKernelGGL(rollout_wide_kernel<true>, dim3((unsigned)(nblk * 16)), dim3(256), 0, s, c, w, lists, counts);
+        else if (wide)
+            hipLaunchKernelGGL(rollout_wide_kernel<false>, dim3((unsigned)(nblk * 16)), dim3(256), 0, s, c, w, lists, counts);
     }
     bool quad = false;
     if constexpr (MODEL == KIN) {
         // two lanes per request (rollout_pair_kernel); the wave-per-request kernel keeps the rounds with few requests
         quad = !wide && h->quad_rollout && c.nfe == 4 && c.N <= 64;   // (its wave-wide redo of a request: kin_wide_rollout)
-        if (quad)
-            hipLaunchKernelGGL(rollout_pair_kernel, dim3((unsigned)(nblk * 2)), dim3(64),
+        if (quad && pa)
+            hipLaunchKernelGGL(rollout_pair_kernel<true>, dim3((unsigned)(nblk * 2)), dim3(64),
+                               sizeof(double) * 32 * (size_t)(c.n + 1), s, c, w, lists, counts, nG, nC);
+        else if (quad)
+            hipLaunchKernelGGL(rollout_pair_kernel<false>, dim3((unsigned)(nblk * 2)), dim3(64),
                                sizeof(double) * 32 * (size_t)(c.n + 1), s, c, w, lists, counts, nG, nC);
     }
     if constexpr (MODEL == PAC) {
@@ -471,12 +502,17 @@ static bool launch_eval_t(mpc_handle *h, const Workspace &w, hipStream_t s, cons
         // (pac_quad_max: requests bound up to which the four-lane kernel runs; since the lost stages are parked no
         // request drags its wave, and the full rounds are bound by what they execute: profiles/r03_experiments.txt 34)
         quad = h->quad_rollout && !(counts && slot_bound >= 0 && slot_bound > h->pac_quad_max);
-        if (quad)
-            hipLaunchKernelGGL(rollout_quad_kernel, dim3((unsigned)(nblk * 4)), dim3(64),
+        if (quad && pa)
+            hipLaunchKernelGGL(rollout_quad_kernel<true>, dim3((unsigned)(nblk * 4)), dim3(64),
+                               sizeof(double) * 16 * (size_t)(c.n + 1), s, c, w, lists, counts, nG, nC);
+        else if (quad)
+            hipLaunchKernelGGL(rollout_quad_kernel<false>, dim3((unsigned)(nblk * 4)), dim3(64),
                                sizeof(double) * 16 * (size_t)(c.n + 1), s, c, w, lists, counts, nG, nC);
     }
-    if (!wide && !quad)
-        hipLaunchKernelGGL((rollout_kernel<MODEL>), dim3((unsigned)nblk), dim3(64), lds, s, c, w, lists, counts, nG, nC);
+    if (!wide && !quad && pa)
+        hipLaunchKernelGGL((rollout_kernel<MODEL, true>), dim3((unsigned)nblk), dim3(64), lds, s, c, w, lists, counts, nG, nC);
+    else if (!wide && !quad)
+        hipLaunchKernelGGL((rollout_kernel<MODEL, false>), dim3((unsigned)nblk), dim3(64), lds, s, c, w, lists, counts, nG, nC);
     if (eva) (void)hipEventRecord(eva, s);
     // (kinematic model only: the Pacejka stage needs more registers than the fused kernel leaves it)
     if constexpr (MODEL == KIN) {
@@ -486,7 +522,11 @@ static bool launch_eval_t(mpc_handle *h, const Workspace &w, hipStream_t s, cons
             const int spb = FUSED_BLK / c.N;
             const int gb = (nblk * 64 + spb - 1) / spb;
             const size_t flds = sizeof(double) * (size_t)(JS + 1) * c.N * spb;
-            if (shared)
+            if (shared && pa)
+                hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, true, true>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c, w, counts, nG, nC, desc);
+            else if (pa)
+                hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, false, true>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c, w, counts, nG, nC, desc);
+            else if (shared)
                 hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, true>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c, w, counts, nG, nC, desc);
             else
                 hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, false>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c, w, counts, nG, nC, desc);
@@ -498,7 +538,11 @@ static bool launch_eval_t(mpc_handle *h, const Workspace &w, hipStream_t s, cons
     // block on XCD sb % 8 so that K1c could read records from the L2 they were written to -- no change: the 13 MB
     // of records per XCD and launch pass through a 4 MB L2 long before K1c starts)
     const size_t xy_lds = (shared && w.near.gmeta && c.S <= GRID_LDS_MAX_S) ? sizeof(double) * 2 * (size_t)c.S : 0;
-    if (shared)
+    if (shared && pa)
+        hipLaunchKernelGGL((stage_kernel<MODEL, true, true>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c, w, counts, nG, nC, nblk);
+    else if (pa)
+        hipLaunchKernelGGL((stage_kernel<MODEL, false, true>), dim3((unsigned)(nblk * c.N)), dim3(64), 0, s, c, w, counts, nG, nC, nblk);
+    else if (shared)
         hipLaunchKernelGGL((stage_kernel<MODEL, true>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c, w, counts, nG, nC, nblk);
     else
         hipLaunchKernelGGL((stage_kernel<MODEL, false>), dim3((unsigned)(nblk * c.N)), dim3(64), 0, s, c, w, counts, nG, nC, nblk);
@@ -507,7 +551,7 @@ static bool launch_eval_t(mpc_handle *h, const Workspace &w, hipStream_t s, cons
     return false;
 }
 // returns true when K1b and K1c ran as one launch
-static bool launch_eval(mpc_handle *h, const Workspace &w, hipStream_t s, const int *lists, const int *counts,
+static bool launch_eval(mpc_handle *h, const WorkspacePA &w, hipStream_t s, const int *lists, const int *counts,
                         int nG, int nC, hipEvent_t eva = nullptr, hipEvent_t evb = nullptr, int slot_bound = -1,
                         int *desc = nullptr)
 {
@@ -569,14 +613,46 @@ extern "C" int mpc_centerline_blocks(mpc_handle *h, const double *cl, int C, voi
     return MPC_OK;
 }
 
+// Binds (table != NULL) or unbinds the per-agent parameter table.  The rows are checked once, here, through a
+// synchronous copy (binding is not on the hot path; rows rewritten in place later are the caller's to keep valid):
+// what the model divides by must be positive and everything finite.  Nothing else is done: the kernels read the
+// caller's memory at every call.
+extern "C" int mpc_set_agent_params(mpc_handle *h, const double *table, int P, const int32_t *index,
+                                    const int32_t *plant_index, int B)
+{
+    if (!h) return fail(MPC_E_ARG, "mpc_set_agent_params: null handle");
+    { const int rb = refuse_if_busy(h, "mpc_set_agent_params"); if (rb) return rb; }
+    if (!table) { h->ptab = nullptr; h->pidx = h->pidx_plant = nullptr; h->ptab_rows = h->ptab_B = 0; return MPC_OK; }
+    if (P < 1 || B < 1 || !index) return fail(MPC_E_ARG, "mpc_set_agent_params: need P >= 1 rows, B >= 1 agents and an index");
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<double> rows((size_t)P * MPC_NPARAM);
+    HIPCHK(hipMemcpy(rows.data(), table, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int p = 0; p < P; p++) {
+        const double *r = rows.data() + (size_t)p * MPC_NPARAM;
+        for (int i = 0; i < MPC_NPARAM; i++)
+            if (!std::isfinite(r[i]))
+                return fail(MPC_E_ARG, "mpc_set_agent_params: row " + std::to_string(p) + ", value " + std::to_string(i) + " is not finite");
+        if (!(r[1] + r[2] > 0.0))
+            return fail(MPC_E_ARG, "mpc_set_agent_params: row " + std::to_string(p) + ": lf + lr (veh[1] + veh[2]) must be positive");
+        if (h->cfg.model == MPC_MODEL_PACEJKA && (!(r[7] > 0.0) || !(r[8] > 0.0)))
+            return fail(MPC_E_ARG, "mpc_set_agent_params: row " + std::to_string(p) + ": mass and inertia (veh[7], veh[8]) must be positive");
+    }
+    h->ptab = table; h->ptab_rows = P; h->pidx = index; h->pidx_plant = plant_index; h->ptab_B = B;
+    return MPC_OK;
+}
+
 extern "C" int mpc_rhs(mpc_handle *h, int B, const double *x, const double *u, double *dx, void *stream)
 {
     int rc = check_common(h, B, "mpc_rhs"); if (rc) return rc;
     if (B == 0) return MPC_OK;
     if (!x || !u || !dx) return fail(MPC_E_ARG, "mpc_rhs: null buffer");
+    rc = check_bound(h, B, "mpc_rhs"); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (h->dc.model == PAC) hipLaunchKernelGGL(rhs_kernel<PAC>, grid_for(B, 64), dim3(64), 0, s, h->dc, B, x, u, dx);
-    else hipLaunchKernelGGL(rhs_kernel<KIN>, grid_for(B, 64), dim3(64), 0, s, h->dc, B, x, u, dx);
+    const double *pt = h->ptab; const int *pi = h->pidx;
+    if (pt && h->dc.model == PAC) hipLaunchKernelGGL((rhs_kernel<PAC, true, const double *, const int *>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, x, u, dx, pt, pi);
+    else if (pt) hipLaunchKernelGGL((rhs_kernel<KIN, true, const double *, const int *>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, x, u, dx, pt, pi);
+    else if (h->dc.model == PAC) hipLaunchKernelGGL((rhs_kernel<PAC, false>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, x, u, dx);
+    else hipLaunchKernelGGL((rhs_kernel<KIN, false>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, x, u, dx);
     HIPCHK(hipGetLastError());
     return MPC_OK;
 }
@@ -587,9 +663,13 @@ extern "C" int mpc_rollout(mpc_handle *h, int B, int Nsim, const double *x0, con
     int rc = check_common(h, B, "mpc_rollout"); if (rc) return rc;
     if (B == 0 || Nsim == 0) return MPC_OK;
     if (Nsim < 0 || !x0 || !U || !X) return fail(MPC_E_ARG, "mpc_rollout: bad argument");
+    rc = check_bound(h, B, "mpc_rollout"); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (h->dc.model == PAC) hipLaunchKernelGGL(simulate_kernel<PAC>, grid_for(B, 64), dim3(64), 0, s, h->dc, B, Nsim, x0, U, X);
-    else hipLaunchKernelGGL(simulate_kernel<KIN>, grid_for(B, 64), dim3(64), 0, s, h->dc, B, Nsim, x0, U, X);
+    const double *pt = h->ptab; const int *pi = h->pidx;
+    if (pt && h->dc.model == PAC) hipLaunchKernelGGL((simulate_kernel<PAC, true, const double *, const int *>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, Nsim, x0, U, X, pt, pi);
+    else if (pt) hipLaunchKernelGGL((simulate_kernel<KIN, true, const double *, const int *>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, Nsim, x0, U, X, pt, pi);
+    else if (h->dc.model == PAC) hipLaunchKernelGGL((simulate_kernel<PAC, false>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, Nsim, x0, U, X);
+    else hipLaunchKernelGGL((simulate_kernel<KIN, false>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, Nsim, x0, U, X);
     HIPCHK(hipGetLastError());
     return MPC_OK;
 }
@@ -638,9 +718,13 @@ extern "C" int mpc_stage_cost(mpc_handle *h, int B, const double *x, const doubl
     int rc = check_common(h, B, "mpc_stage_cost"); if (rc) return rc;
     if (B == 0) return MPC_OK;
     if (!x || !u || !cl || !out) return fail(MPC_E_ARG, "mpc_stage_cost: null buffer");
+    rc = check_bound(h, B, "mpc_stage_cost"); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (h->dc.model == PAC) hipLaunchKernelGGL(stage_cost_kernel<PAC>, grid_for(B, 64), dim3(64), 0, s, h->dc, B, x, u, cl, cl_index, out);
-    else hipLaunchKernelGGL(stage_cost_kernel<KIN>, grid_for(B, 64), dim3(64), 0, s, h->dc, B, x, u, cl, cl_index, out);
+    const double *pt = h->ptab; const int *pi = h->pidx;
+    if (pt && h->dc.model == PAC) hipLaunchKernelGGL((stage_cost_kernel<PAC, true, const double *, const int *>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, x, u, cl, cl_index, out, pt, pi);
+    else if (pt) hipLaunchKernelGGL((stage_cost_kernel<KIN, true, const double *, const int *>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, x, u, cl, cl_index, out, pt, pi);
+    else if (h->dc.model == PAC) hipLaunchKernelGGL((stage_cost_kernel<PAC, false>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, x, u, cl, cl_index, out);
+    else hipLaunchKernelGGL((stage_cost_kernel<KIN, false>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, x, u, cl, cl_index, out);
     HIPCHK(hipGetLastError());
     return MPC_OK;
 }
@@ -669,25 +753,30 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     if (!x0 || !cl || !U || !psi) return fail(MPC_E_ARG, "mpc_eval_cost_grad: null buffer");
     const DevCfg &c = h->dc;
     if (c.m && (!y || !Sigma)) return fail(MPC_E_ARG, "mpc_eval_cost_grad: y and Sigma are required when m > 0");
+    rc = check_bound(h, B, "mpc_eval_cost_grad"); if (rc) return rc;
     rc = reserve(h, B); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     // direct mode: the kernel reads and writes the caller's agent-major buffers in place
-    Workspace w = h->ws;
+    WorkspacePA w = h->ws;
     w.cl = cl; w.cl_index = cl_index; w.x0 = x0; w.near = near_for(h, cl);
     w.xe = const_cast<double *>(U); w.ge = grad ? grad : h->ws.ws_ge;
     w.y = const_cast<double *>(y); w.Sig = c.m ? const_cast<double *>(Sigma) : h->ws.ws_Sig;
     w.yhe = (yhat && c.m) ? yhat : h->ws.ws_yhe;
     w.psi_direct = psi;
-    Workspace saved = h->ws;
+    w.ptab = h->ptab; w.pidx = h->pidx;
+    const bool pa = w.ptab != nullptr;
+    WorkspacePA saved = h->ws;
     h->ws = w;
     if (wave_path) {
         // one wave per agent, the evaluation as the persistent kernel runs it (mpc_solo.hpp)
         if (c.model == PAC) {
             const size_t lds = sizeof(double) * solo_lds_doubles<PAC>(c.nfe, c.N, c.n, c.M, false);
-            hipLaunchKernelGGL(solo_eval_kernel<PAC>, dim3((unsigned)B), dim3(64), lds, s, c, h->ws, grad ? 1 : 0);
+            if (pa) hipLaunchKernelGGL((solo_eval_kernel<PAC, true>), dim3((unsigned)B), dim3(64), lds, s, c, h->ws, grad ? 1 : 0);
+            else hipLaunchKernelGGL((solo_eval_kernel<PAC, false>), dim3((unsigned)B), dim3(64), lds, s, c, h->ws, grad ? 1 : 0);
         } else {
             const size_t lds = sizeof(double) * solo_lds_doubles<KIN>(c.nfe, c.N, c.n, c.M, false);
-            hipLaunchKernelGGL(solo_eval_kernel<KIN>, dim3((unsigned)B), dim3(64), lds, s, c, h->ws, grad ? 1 : 0);
+            if (pa) hipLaunchKernelGGL((solo_eval_kernel<KIN, true>), dim3((unsigned)B), dim3(64), lds, s, c, h->ws, grad ? 1 : 0);
+            else hipLaunchKernelGGL((solo_eval_kernel<KIN, false>), dim3((unsigned)B), dim3(64), lds, s, c, h->ws, grad ? 1 : 0);
         }
     } else
         launch_eval(h, h->ws, s, nullptr, nullptr, grad ? B : 0, grad ? 0 : B);
@@ -769,7 +858,7 @@ static size_t step_dyn_lds(int ne, int n, int P, bool chain)
 }
 
 template <int NE, int MC>
-static void launch_step_t(mpc_handle *h, const Workspace &w, hipStream_t s, int *lists, int *counts, int *counts_next,
+static void launch_step_t(mpc_handle *h, const WorkspacePA &w, hipStream_t s, int *lists, int *counts, int *counts_next,
                           int slot_bound, int par)
 {
     const int P = MC < 0 ? step_lds_pairs(NE, h->dc.n, h->dc.M, h->dc.m, h->lds_pairs) : h->dc.M;
@@ -809,7 +898,7 @@ static void launch_step_t(mpc_handle *h, const Workspace &w, hipStream_t s, int 
         hipLaunchKernelGGL((step_kernel<NE, MC, true>), dim3((unsigned)(nstep + nchain)), dim3(64 * STEP_WAVES), lds, s,
                            dcl, w, lists, counts, counts_next, apb, nstep, par, P);
 }
-static void launch_step(mpc_handle *h, const Workspace &w, hipStream_t s, int *lists, int *counts, int *counts_next,
+static void launch_step(mpc_handle *h, const WorkspacePA &w, hipStream_t s, int *lists, int *counts, int *counts_next,
                         int slot_bound, int par)
 {
     const DevCfg &c = h->dc;
@@ -836,7 +925,7 @@ extern "C" int mpc_step_lds_plan(int n, int M, int m, int chain, int lds_pairs, 
 // a list of them is built first; otherwise every agent of the view is claimed).  `bound` = an upper
 // bound on the number of agents it will find.
 template <int MODEL, int NE, int MC>
-static void launch_solo_t(mpc_handle *h, const Workspace &v, hipStream_t s, int *ctr, bool listed, int bound,
+static void launch_solo_t(mpc_handle *h, const WorkspacePA &v, hipStream_t s, int *ctr, bool listed, int bound,
                           long long max_trips)
 {
     const DevCfg &c = h->dc;
@@ -847,18 +936,27 @@ static void launch_solo_t(mpc_handle *h, const Workspace &v, hipStream_t s, int 
     const size_t lds = sizeof(double) * SOLO_WAVES * solo_lds_doubles<MODEL>(c.nfe, c.N, c.n, c.M, MC < 0, la);
     int nblk = (bound + SOLO_WAVES - 1) / SOLO_WAVES;
     nblk = std::max(1, std::min(nblk, 4 * SoloOcc<MODEL>::WPS * h->num_cus)); // what is resident (registers); the rest queues
+    const bool pa = v.ptab != nullptr;   // a parameter table is bound: the per-agent variant
     if constexpr (MODEL == PAC && NE == 1) {
         if (la) {
+            if (pa)
+                hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, true, true>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c, v, list,
+                                   ctr, max_trips);
+            else
             hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, true>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c, v, list,
                                ctr, max_trips);
             return;
         }
     }
+    if (pa)
+        hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c, v, list,
+                           ctr, max_trips);
+    else
     hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c, v, list,
                        ctr, max_trips);
 }
 template <int MODEL>
-static void launch_solo_m(mpc_handle *h, const Workspace &v, hipStream_t s, int *ctr, bool listed, int bound,
+static void launch_solo_m(mpc_handle *h, const WorkspacePA &v, hipStream_t s, int *ctr, bool listed, int bound,
                           long long max_trips)
 {
     const DevCfg &c = h->dc;
@@ -867,7 +965,7 @@ static void launch_solo_m(mpc_handle *h, const Workspace &v, hipStream_t s, int 
         else launch_solo_t<MODEL, 1, 0>(h, v, s, ctr, listed, bound, max_trips);
     } else launch_solo_t<MODEL, 2, 0>(h, v, s, ctr, listed, bound, max_trips);
 }
-static void launch_solo(mpc_handle *h, const Workspace &v, hipStream_t s, int *ctr, bool listed, int bound,
+static void launch_solo(mpc_handle *h, const WorkspacePA &v, hipStream_t s, int *ctr, bool listed, int bound,
                         long long max_trips)
 {
     if (h->dc.model == PAC) launch_solo_m<PAC>(h, v, s, ctr, listed, bound, max_trips);
@@ -908,9 +1006,9 @@ static int bounded_sync(mpc_handle *h, hipStream_t s, const char *what)
 }
 
 // a view of the workspace restricted to agents [lo, hi): local agent ids, own lists / scratch
-static Workspace group_view(const Workspace &w, const DevCfg &c, int g, int lo, int hi)
+static WorkspacePA group_view(const WorkspacePA &w, const DevCfg &c, int g, int lo, int hi)
 {
-    Workspace v = w;
+    WorkspacePA v = w;
     const size_t n = c.n, m = c.m, M = c.M;
     v.x0 = w.x0 + (size_t)lo * c.nx; v.xo = w.xo + (size_t)lo * n;
     v.xk = w.xk + (size_t)lo * n; v.gk = w.gk + (size_t)lo * n; v.q = w.q + (size_t)lo * n;
@@ -923,6 +1021,7 @@ static Workspace group_view(const Workspace &w, const DevCfg &c, int g, int lo, 
     v.yhe = w.yhe + (size_t)lo * m;
     v.rec = w.rec + (size_t)lo * REC;
     if (w.cl_index) v.cl_index = w.cl_index + lo;
+    if (w.pidx) v.pidx = w.pidx + lo;
     const size_t soff = 2 * (size_t)lo + 64 * (size_t)g; // disjoint slot intervals inside the shared scratch
     v.trajx = w.trajx + soff; v.useq = w.useq + soff; v.stage_L = w.stage_L + soff; v.jac = w.jac + soff;
     v.agent_of = w.agent_of + soff;
@@ -954,7 +1053,7 @@ static int run_solver(mpc_handle *h, hipStream_t s)
 static int run_solver_rounds(mpc_handle *h, hipStream_t s)
 {
     const DevCfg &c = h->dc;
-    Workspace &w = h->ws;
+    WorkspacePA &w = h->ws;
     const int B = w.B;
     HIPCHK(hipMemsetAsync(w.counts, 0, 8 * MPC_MAX_GROUPS * sizeof(int) + 16 * sizeof(unsigned long long) +
                                            2 * MPC_MAX_GROUPS * sizeof(int), s));
@@ -987,7 +1086,7 @@ static int run_solver_rounds(mpc_handle *h, hipStream_t s)
         // small batch: every agent is solved by one wave of the persistent kernel from the start
         all_solo = true;
     }
-    Workspace gv[MPC_MAX_GROUPS];
+    WorkspacePA gv[MPC_MAX_GROUPS];
     hipStream_t gs[MPC_MAX_GROUPS];
     // groups: contiguous agent ranges (multiples of 64), each with its own stream; measured at
     // B = 65536 (round 1): 1 group 0.258 s, 2 groups 0.224 s, 3 groups 0.220 s per solve.  The HIP runtime
@@ -1047,7 +1146,7 @@ static int run_solver_rounds(mpc_handle *h, hipStream_t s)
     const auto t_loop0 = std::chrono::steady_clock::now();
     auto queue_window_impl = [&](int g) {       // `check_every` rounds of group g, then the copy of its counters
         GroupRun &r = gr[g];
-        const Workspace &v = gv[g];
+        const WorkspacePA &v = gv[g];
         int cur = 0;
         for (int i = 0; i < check_every && r.round < max_rounds; i++) {
             cur = (int)(r.round & 1);
@@ -1247,11 +1346,13 @@ static int solve_batch_impl(mpc_handle *h, int B, const double *x0, const double
     if (!x0 || !cl || !U) return fail(MPC_E_ARG, "mpc_solve_batch: null buffer");
     const DevCfg &c = h->dc;
     if (c.m && !lambda) return fail(MPC_E_ARG, "mpc_solve_batch: lambda is required when m > 0");
+    rc = check_bound(h, B, "mpc_solve_batch"); if (rc) return rc;
     rc = reserve(h, B); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    Workspace &w = h->ws;
+    WorkspacePA &w = h->ws;
     w.cl = cl; w.cl_index = cl_index; w.x0 = x0; w.xo = U; w.y = lambda; w.psi_direct = nullptr;
     w.near = near_for(h, cl);
+    w.ptab = h->ptab; w.pidx = h->pidx;
     w.xe = w.ws_xe; w.ge = w.ws_ge; w.yhe = w.ws_yhe; w.Sig = w.ws_Sig;
     rc = run_solver(h, s); if (rc) return rc;
     if (stats) hipLaunchKernelGGL(stats_kernel, grid_for(B, 256), dim3(256), 0, s, w, stats);
@@ -1317,6 +1418,9 @@ extern "C" int mpc_closed_loop(mpc_handle *h, int B, int T, int shift, double *x
     if (T < 0 || !x || !cl || !U) return fail(MPC_E_ARG, "mpc_closed_loop: bad argument");
     const DevCfg &c = h->dc;
     if (c.m && !lambda) return fail(MPC_E_ARG, "mpc_closed_loop: lambda is required when m > 0");
+    rc = check_bound(h, B, "mpc_closed_loop"); if (rc) return rc;
+    // bound table: the controller solves with row pidx[b], the plant advances with row pidx_plant[b] (null: the same)
+    const double *pt = h->ptab; const int *pi = h->pidx_plant ? h->pidx_plant : h->pidx;
     hipStream_t s = (hipStream_t)stream;
     double *st = stats;
     if (!st) {
@@ -1325,11 +1429,17 @@ extern "C" int mpc_closed_loop(mpc_handle *h, int B, int T, int shift, double *x
     }
     for (int t = 0; t < T; t++) {
         rc = mpc_solve_batch(h, B, x, cl, cl_index, U, lambda, st, stream); if (rc) return rc;
-        if (c.model == PAC)
-            hipLaunchKernelGGL(plant_step_kernel<PAC>, grid_for(B, 64), dim3(64), 0, s, c, B, t, T, shift, x, U,
+        if (pt && c.model == PAC)
+            hipLaunchKernelGGL((plant_step_kernel<PAC, true, const double *, const int *>), grid_for(B, 64), dim3(64), 0, s, c, B, t, T, shift, x, U,
+                               traj_x, traj_u, st, fail_count, pt, pi);
+        else if (pt)
+            hipLaunchKernelGGL((plant_step_kernel<KIN, true, const double *, const int *>), grid_for(B, 64), dim3(64), 0, s, c, B, t, T, shift, x, U,
+                               traj_x, traj_u, st, fail_count, pt, pi);
+        else if (c.model == PAC)
+            hipLaunchKernelGGL((plant_step_kernel<PAC, false>), grid_for(B, 64), dim3(64), 0, s, c, B, t, T, shift, x, U,
                                traj_x, traj_u, st, fail_count);
         else
-            hipLaunchKernelGGL(plant_step_kernel<KIN>, grid_for(B, 64), dim3(64), 0, s, c, B, t, T, shift, x, U,
+            hipLaunchKernelGGL((plant_step_kernel<KIN, false>), grid_for(B, 64), dim3(64), 0, s, c, B, t, T, shift, x, U,
                                traj_x, traj_u, st, fail_count);
     }
     HIPCHK(hipGetLastError());

@@ -6,13 +6,18 @@
 namespace mpc {
 
 // a-1 standalone: dx = f(x, u), agent-major arrays
-template <int MODEL>
-__global__ void __launch_bounds__(64) rhs_kernel(const DevCfg c, int B, const double *__restrict__ x,
-                           const double *__restrict__ u, double *__restrict__ dx)
+// (PA, here and below: the per-agent instantiation, which takes two more arguments `pt` = (table, index): agent a's
+// parameters are row index[a] of the table, see agent_cfg.  The shared instantiation keeps its argument list.)
+template <int MODEL, bool PA = false, class... PT>
+__global__ void __launch_bounds__(64) rhs_kernel(const DevCfg c_, int B, const double *__restrict__ x,
+                           const double *__restrict__ u, double *__restrict__ dx, PT... pt)
 {
     constexpr int NX = ModelDim<MODEL>::NX;
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= B) return;
+    DevCfg cm_;
+    if constexpr (PA) { cm_ = c_; agent_cfg(cm_, pt..., a); }
+    const DevCfg &c = PA ? cm_ : c_;
     double xv[NX], k[NX];
     for (int i = 0; i < NX; i++) xv[i] = x[(size_t)a * NX + i];
     StageInput<MODEL> s;
@@ -23,13 +28,16 @@ __global__ void __launch_bounds__(64) rhs_kernel(const DevCfg c, int B, const do
 }
 
 // a-2/a-3 standalone: X[B][Nsim][nx]
-template <int MODEL>
-__global__ void __launch_bounds__(64) simulate_kernel(const DevCfg c, int B, int Nsim, const double *__restrict__ x0,
-                               const double *__restrict__ U, double *__restrict__ X)
+template <int MODEL, bool PA = false, class... PT>
+__global__ void __launch_bounds__(64) simulate_kernel(const DevCfg c_, int B, int Nsim, const double *__restrict__ x0,
+                               const double *__restrict__ U, double *__restrict__ X, PT... pt)
 {
     constexpr int NX = ModelDim<MODEL>::NX;
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= B) return;
+    DevCfg cm_;
+    if constexpr (PA) { cm_ = c_; agent_cfg(cm_, pt..., a); }
+    const DevCfg &c = PA ? cm_ : c_;
     double xv[NX];
     for (int i = 0; i < NX; i++) xv[i] = x0[(size_t)a * NX + i];
     for (int n = 0; n < Nsim; n++) {
@@ -134,14 +142,17 @@ __global__ void errors_kernel(const DevCfg c, int B, const double *__restrict__ 
 }
 
 // a-6 standalone: L[b] = stage cost of (x[b], u[b]) against its centerline (car_dynamics.py:252-258)
-template <int MODEL>
-__global__ void __launch_bounds__(64) stage_cost_kernel(const DevCfg c, int B, const double *__restrict__ x,
+template <int MODEL, bool PA = false, class... PT>
+__global__ void __launch_bounds__(64) stage_cost_kernel(const DevCfg c_, int B, const double *__restrict__ x,
                                   const double *__restrict__ u, const double *__restrict__ cl,
-                                  const int *__restrict__ cl_index, double *__restrict__ out)
+                                  const int *__restrict__ cl_index, double *__restrict__ out, PT... pt)
 {
     constexpr int NX = ModelDim<MODEL>::NX;
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= B) return;
+    DevCfg cm_;
+    if constexpr (PA) { cm_ = c_; agent_cfg(cm_, pt..., a); }
+    const DevCfg &c = PA ? cm_ : c_;
     const double *clp = cl + (size_t)(cl_index ? cl_index[a] : 0) * 2 * (size_t)c.S;
     double xv[NX], xb[NX], ub[2];
     for (int i = 0; i < NX; i++) xv[i] = x[(size_t)a * NX + i];
@@ -172,15 +183,20 @@ __global__ void prox_kernel(const DevCfg c, int B, const double *__restrict__ x,
 }
 
 // closed loop helpers (main.py:141-146): u0 = U[:, 0], x <- f_d(x, u0), optional warm-start shift
-template <int MODEL>
-__global__ void __launch_bounds__(64) plant_step_kernel(const DevCfg c, int B, int t, int T, int shift,
+// (PA: the plant's parameters are row index[a] of the table -- mpc_closed_loop hands it the PLANT's index, which may
+// differ from the controller's: main.py:145's separate `param`)
+template <int MODEL, bool PA = false, class... PT>
+__global__ void __launch_bounds__(64) plant_step_kernel(const DevCfg c_, int B, int t, int T, int shift,
                                   double *__restrict__ x, double *__restrict__ U,
                                   double *__restrict__ traj_x, double *__restrict__ traj_u,
-                                  const double *__restrict__ stats, int *__restrict__ fail_count)
+                                  const double *__restrict__ stats, int *__restrict__ fail_count, PT... pt)
 {
     constexpr int NX = ModelDim<MODEL>::NX;
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= B) return;
+    DevCfg cm_;
+    if constexpr (PA) { cm_ = c_; agent_cfg(cm_, pt..., a); }
+    const DevCfg &c = PA ? cm_ : c_;
     double xv[NX];
     for (int i = 0; i < NX; i++) xv[i] = x[(size_t)a * NX + i];
     double *Ua = U + (size_t)a * c.n;

@@ -47,6 +47,45 @@ struct DevCfg {
 
 #define MPC_DEV __device__ __forceinline__
 
+// ---------------------------------------------------------------------------------- per-agent parameters
+// mpc_set_agent_params: a table [P][NPARAM] of rows in device memory and one row index per agent.  A row holds what
+// mpc_config holds per handle -- [0..21] veh, [22] accel, [23] friction, [24] v_ref, [25..30] cost_w -- and
+// replaces exactly the DevCfg fields make_devcfg derives from those (the input box, the constraint data and every
+// solver parameter stay the handle's).  The per-agent kernels (template flag PA) run the model functions on a
+// private DevCfg: the handle's, with these fields from the agent's row.  The reciprocals are IEEE divisions, the
+// correctly rounded quotients the host computes for the shared path: a row equal to the handle's values gives the
+// shared path's bits.
+constexpr int NPARAM = 31;
+
+template <class Ld> MPC_DEV void agent_cfg_from(DevCfg &c, Ld ld)
+{
+    c.lf = ld(1); c.lr = ld(2);
+    const double mass = ld(7), iz = ld(8);
+    c.mass = mass; c.inv_mass = 1.0 / mass; c.inv_iz = 1.0 / iz;
+    c.max_steer = ld(9); c.max_drive = ld(10);
+    c.bf = ld(11); c.cf = ld(12); c.df = ld(13); c.br = ld(14); c.cr = ld(15); c.dr = ld(16);
+    c.cm1 = ld(17); c.cm2 = ld(18); c.cr0 = ld(19); c.cr2 = ld(21);
+    c.accel = ld(22); c.friction = ld(23); c.v_ref = ld(24);
+#pragma unroll
+    for (int i = 0; i < 6; i++) c.w[i] = ld(25 + i);
+}
+// a different agent in every lane (or lane group): the row's values are vector values, loaded where the kernel
+// learns its agent (only the fields a kernel's model code reads survive: ~11 doubles kinematic, ~17 Pacejka)
+MPC_DEV void agent_cfg(DevCfg &c, const double *__restrict__ tab, const int *__restrict__ idx, int a)
+{
+    const double *__restrict__ r = tab + (size_t)idx[a] * NPARAM;
+    agent_cfg_from(c, [=](int f) { return r[f]; });
+}
+// one agent per wave: the row is wave-uniform and is read by scalar loads into scalar registers (the table is
+// read-only while a kernel runs, so the loads go through the constant address space, as kernel arguments do)
+MPC_DEV void agent_cfg_uniform(DevCfg &c, const double *__restrict__ tab, const int *__restrict__ idx, int a)
+{
+    const int row = __builtin_amdgcn_readfirstlane(idx[a]);
+    const __attribute__((address_space(4))) double *r =
+        (const __attribute__((address_space(4))) double *)(tab + (size_t)row * NPARAM);
+    agent_cfg_from(c, [=](int f) { return r[f]; });
+}
+
 // ---------------------------------------------------------------------------------- math
 // The OCML double-precision transcendentals are full-range (Payne-Hanek reduction, dozens of
 // 64-bit literals each) and dominate this kernel's instruction count.  The angles of this problem

@@ -40,9 +40,11 @@ struct SlotMap {
     }
 };
 
-template <int MODEL>
+// PA (here and in every K1 kernel below): the per-agent instantiation, launched when a parameter table is bound
+// (mpc_set_agent_params) -- the model functions run on `cm`, the handle's DevCfg with the fields of the agent's row
+template <int MODEL, bool PA = false>
 __global__ void __launch_bounds__(64, 2)
-rollout_kernel(const DevCfg c, const Workspace w, const int *__restrict__ lists,
+rollout_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ lists,
                const int *__restrict__ counts, int nG_imm, int nC_imm)
 {
     constexpr int NX = ModelDim<MODEL>::NX;
@@ -84,6 +86,9 @@ rollout_kernel(const DevCfg c, const Workspace w, const int *__restrict__ lists,
     }
     __syncthreads();
     if (!active) return;
+    DevCfg cm_;
+    if constexpr (PA) { cm_ = c; agent_cfg(cm_, w.ptab, w.pidx, a); }
+    const DevCfg &cm = PA ? cm_ : c;
     const size_t St = (size_t)w.St; // scratch stride
     const double *urow = tile + lane * ld;
     double x[NX];
@@ -94,8 +99,8 @@ rollout_kernel(const DevCfg c, const Workspace w, const int *__restrict__ lists,
         w.useq[(size_t)(2 * k) * St + uslot] = d;
         w.useq[(size_t)(2 * k + 1) * St + uslot] = dl;
         StageInput<MODEL> u;
-        prep_input(c, d, dl, u);
-        stage_forward<MODEL>(c, u, x);
+        prep_input(cm, d, dl, u);
+        stage_forward<MODEL>(cm, u, x);
 #pragma unroll
         for (int i = 0; i < NX; i++) w.trajx[(size_t)((k + 1) * NX + i) * St + uslot] = x[i];
     }
@@ -113,8 +118,9 @@ rollout_kernel(const DevCfg c, const Workspace w, const int *__restrict__ lists,
 #endif
 template <class Put>
 __device__ __forceinline__ void kin_wide_rollout(const DevCfg &c, const double (&x0)[4], double d, double dl, int lane, Put put);
+template <bool PA = false>
 __global__ void __launch_bounds__(64, MPC_K1A_WAVES)
-rollout_pair_kernel(const DevCfg c, const Workspace w, const int *__restrict__ lists,
+rollout_pair_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ lists,
                     const int *__restrict__ counts, int nG_imm, int nC_imm)
 {
 #pragma clang fp contract(off)
@@ -150,6 +156,10 @@ rollout_pair_kernel(const DevCfg c, const Workspace w, const int *__restrict__ l
     }
     __builtin_amdgcn_wave_barrier();                     // one wave per workgroup: LDS is in order
     const int a = active ? raw & AGENT_MASK : 0;
+    // (pairs without a request walk along on the handle's values)
+    DevCfg cm_;
+    if constexpr (PA) { cm_ = c; if (active) agent_cfg(cm_, w.ptab, w.pidx, a); }
+    const DevCfg &cm = PA ? cm_ : c;
     const size_t St = (size_t)w.St;
     const double *urow = lds + q * ld;
     double x[4];
@@ -173,17 +183,17 @@ rollout_pair_kernel(const DevCfg c, const Workspace w, const int *__restrict__ l
     auto stage = [&](int k, const StageInput<KIN> &u) {
         const double d = urow[2 * k], dl = urow[2 * k + 1];
         if (active) w.useq[(size_t)(2 * k + half) * St + uslot] = half ? dl : d;
-        redo = redo || !kin4_in_range(c, u, x);          // (both lanes of a pair hold the same state)
+        redo = redo || !kin4_in_range(cm, u, x);          // (both lanes of a pair hold the same state)
 #if MPC_DEV_STAMP == 1
         if (__ballot(redo) != 0ull) stamp.nfall++;
 #endif
         // heading / speed at the start of the four RK4 steps, and the stage values of each
         double ph = x[2], v = x[3];
         KinRK k0, k1, k2, k3;
-        const double ph0 = ph; kin_rk(c, u, v, k0); kin_next(c, k0, ph, v);
-        const double ph1 = ph; kin_rk(c, u, v, k1); kin_next(c, k1, ph, v);
-        const double ph2 = ph; kin_rk(c, u, v, k2); kin_next(c, k2, ph, v);
-        const double ph3 = ph; kin_rk(c, u, v, k3); kin_next(c, k3, ph, v);
+        const double ph0 = ph; kin_rk(cm, u, v, k0); kin_next(cm, k0, ph, v);
+        const double ph1 = ph; kin_rk(cm, u, v, k1); kin_next(cm, k1, ph, v);
+        const double ph2 = ph; kin_rk(cm, u, v, k2); kin_next(cm, k2, ph, v);
+        const double ph3 = ph; kin_rk(cm, u, v, k3); kin_next(cm, k3, ph, v);
         // this lane's two increments: steps 2 half and 2 half + 1
         KinRK ka, kb;
         ka.v1 = half ? k2.v1 : k0.v1; ka.v2 = half ? k2.v2 : k0.v2; ka.v3 = half ? k2.v3 : k0.v3; ka.v4 = half ? k2.v4 : k0.v4;
@@ -191,8 +201,8 @@ rollout_pair_kernel(const DevCfg c, const Workspace w, const int *__restrict__ l
         kb.v1 = half ? k3.v1 : k1.v1; kb.v2 = half ? k3.v2 : k1.v2; kb.v3 = half ? k3.v3 : k1.v3; kb.v4 = half ? k3.v4 : k1.v4;
         kb.kp1 = half ? k3.kp1 : k1.kp1; kb.kp2 = half ? k3.kp2 : k1.kp2; kb.kp3 = half ? k3.kp3 : k1.kp3;
         double dxa, dya, dxb, dyb;
-        kin_increment(c, u, half ? ph2 : ph0, ka, !redo, dxa, dya);
-        kin_increment(c, u, half ? ph3 : ph1, kb, !redo, dxb, dyb);
+        kin_increment(cm, u, half ? ph2 : ph0, ka, !redo, dxa, dya);
+        kin_increment(cm, u, half ? ph3 : ph1, kb, !redo, dxb, dyb);
         const double oxa = dpp_xchg<0xB1>(dxa), oya = dpp_xchg<0xB1>(dya);   // the partner's (quad_perm [1,0,3,2])
         const double oxb = dpp_xchg<0xB1>(dxb), oyb = dpp_xchg<0xB1>(dyb);
         // the position is lane 0's to keep (it stores x and y, lane 1 heading and speed, which never see
@@ -213,7 +223,7 @@ rollout_pair_kernel(const DevCfg c, const Workspace w, const int *__restrict__ l
         if (__ballot(!(fabs(urow[2 * km + 1]) <= 0.75)) != 0ull) stamp.nmid++;
         if (__ballot(!(fabs(urow[2 * km + 1]) < 1.0e5)) != 0ull) stamp.nslow++;
 #endif
-        prep_input(c, urow[2 * km], urow[2 * km + 1], um);
+        prep_input(cm, urow[2 * km], urow[2 * km + 1], um);
         up.ad = dpp_xchg<0xB1>(um.ad); up.beta = dpp_xchg<0xB1>(um.beta);
         up.sb_lr = dpp_xchg<0xB1>(um.sb_lr); up.cb_lr = dpp_xchg<0xB1>(um.cb_lr);
         up.dbeta = dpp_xchg<0xB1>(um.dbeta); up.mk0 = dpp_xchg<0xB1>(um.mk0); up.mk1 = dpp_xchg<0xB1>(um.mk1);
@@ -242,6 +252,11 @@ rollout_pair_kernel(const DevCfg c, const Workspace w, const int *__restrict__ l
 #pragma unroll
         for (int i = 0; i < 4; i++) xq[i] = w.x0[(size_t)aq * 4 + i];
         double *const tj = w.trajx + uq;
+        if constexpr (PA) {
+            DevCfg cq = c;
+            agent_cfg_uniform(cq, w.ptab, w.pidx, aq);
+            kin_wide_rollout(cq, xq, dq, dlq, lane, [=](int k, int i, double v) { tj[(size_t)(k * 4 + i) * St] = v; });
+        } else
         kin_wide_rollout(c, xq, dq, dlq, lane, [=](int k, int i, double v) { tj[(size_t)(k * 4 + i) * St] = v; });
     }
 }
@@ -252,8 +267,9 @@ rollout_pair_kernel(const DevCfg c, const Workspace w, const int *__restrict__ l
 // 65 536 agents in three groups gives the thread-per-request kernel half a wave per SIMD: four times
 // the waves at 0.56 of the chain length fill the chip where it was idle, and shorten the chain where
 // a tail of few agents waits for it.  Same bits as rollout_kernel<PAC>.
+template <bool PA = false>
 __global__ void __launch_bounds__(64, MPC_QUAD_WAVES)
-rollout_quad_kernel(const DevCfg c, const Workspace w, const int *__restrict__ lists,
+rollout_quad_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ lists,
                     const int *__restrict__ counts, int nG_imm, int nC_imm)
 {
     constexpr int NX = 6, RPB = 16;                      // requests per block
@@ -286,6 +302,9 @@ rollout_quad_kernel(const DevCfg c, const Workspace w, const int *__restrict__ l
     __builtin_amdgcn_wave_barrier();                     // one wave per workgroup: LDS is in order
     if (!active) return;                                 // whole quads leave together
     const int a = raw & AGENT_MASK;
+    DevCfg cm_;
+    if constexpr (PA) { cm_ = c; agent_cfg(cm_, w.ptab, w.pidx, a); }
+    const DevCfg &cm = PA ? cm_ : c;
     const size_t St = (size_t)w.St;
     const double *urow = lds + q * ld;
     double x[NX];
@@ -302,7 +321,7 @@ rollout_quad_kernel(const DevCfg c, const Workspace w, const int *__restrict__ l
         if (role == 0) w.useq[(size_t)(2 * k) * St + uslot] = d;
         if (role == 1) w.useq[(size_t)(2 * k + 1) * St + uslot] = dl;
         StageInput<PAC> u;
-        prep_input(c, d, dl, u);
+        prep_input(cm, d, dl, u);
 #if MPC_DEV_STAMP == 4
         {   // stages that START from a state with a non-finite component / from a finite one outside the fast ranges
             bool fin = true;
@@ -314,7 +333,7 @@ rollout_quad_kernel(const DevCfg c, const Workspace w, const int *__restrict__ l
             if (__ballot(!fin) != 0ull && k == 0) stamp.nslow++;
         }
 #endif
-        stage_forward_quad(c, u, x, role);
+        stage_forward_quad(cm, u, x, role);
         put(k + 1);
     }
 }
@@ -408,8 +427,9 @@ __device__ __forceinline__ void kin_wide_rollout(const DevCfg &c, const double (
     if (stage_lane) { put(lane + 1, 0, epx); put(lane + 1, 1, epy); put(lane + 1, 2, eph); put(lane + 1, 3, ev); }
 }
 
+template <bool PA = false>
 __global__ void __launch_bounds__(256)
-rollout_wide_kernel(const DevCfg c, const Workspace w, const int *__restrict__ lists,
+rollout_wide_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ lists,
                     const int *__restrict__ counts)
 {
     const SlotMap sm(counts, 0, 0);
@@ -437,6 +457,11 @@ rollout_wide_kernel(const DevCfg c, const Workspace w, const int *__restrict__ l
 #pragma unroll
     for (int i = 0; i < 4; i++) x0[i] = w.x0[(size_t)a * 4 + i];
     double *const tj = w.trajx + uslot;
+    if constexpr (PA) {
+        DevCfg cm = c;
+        agent_cfg_uniform(cm, w.ptab, w.pidx, a);
+        kin_wide_rollout(cm, x0, d, dl, lane, [=](int k, int i, double v) { tj[(size_t)(k * 4 + i) * St] = v; });
+    } else
     kin_wide_rollout(c, x0, d, dl, lane,
                      [=](int k, int i, double v) { tj[(size_t)(k * 4 + i) * St] = v; });
 }
@@ -648,9 +673,9 @@ __device__ __forceinline__ void adjoint_rec_quad_kin(const DevCfg &c, bool is_g,
 // (tried: the gradient blocks and the cost blocks by kernels of their own -- the cost-only variant needs 55
 // registers and runs eight waves per SIMD, 13 us per launch against 75 us for the gradient blocks -- but
 // the pair of launches is slower than the one: 180.2 vs 175.6 ms per solve)
-template <int MODEL, bool SHARED_CL>
+template <int MODEL, bool SHARED_CL, bool PA = false>
 __global__ void __launch_bounds__(64, (MODEL == KIN ? MPC_K1B_WAVES : MPC_K1B_WAVES_PAC))
-stage_kernel(const DevCfg c, const Workspace w, const int *__restrict__ counts, int nG_imm, int nC_imm,
+stage_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, int nG_imm, int nC_imm,
              int nblk_max)
 {
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE;
@@ -687,7 +712,10 @@ stage_kernel(const DevCfg c, const Workspace w, const int *__restrict__ counts, 
     double *const jr = w.jac + (size_t)k * JS * St + uslot;
     double *const sl = w.stage_L + (size_t)k * St + uslot;
     const auto put = [=](int f, double v) { *(f == JS ? sl : jr + (size_t)f * St) = v; };
-    if (is_g) stage_sens_record<MODEL>(c, xs, xe, d, dl, put);
+    DevCfg cm_;
+    if constexpr (PA) { cm_ = c; agent_cfg(cm_, w.ptab, w.pidx, a); }
+    const DevCfg &cm = PA ? cm_ : c;
+    if (is_g) stage_sens_record<MODEL>(cm, xs, xe, d, dl, put);
     Geom g;
     if (lds_xy) {
         const int idx = nearest_index_grid(c, clp, w.near.gmeta, w.near.gcells, [=](int i) { return s_xy[i]; }, xe[0], xe[1]);
@@ -695,7 +723,7 @@ stage_kernel(const DevCfg c, const Workspace w, const int *__restrict__ counts, 
     } else {
         stage_geom(c, w, clp, SHARED_CL ? 0 : w.cl_index[a], xe[0], xe[1], g);
     }
-    stage_record<MODEL>(c, w, a, ch2, is_g, k, xs, xe, d, dl, g, put);
+    stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put);
 }
 
 // (tried: four lanes per gradient request -- lane `role` of a DPP quad owning lambda[role] and one row of the
@@ -736,9 +764,9 @@ constexpr int FUSED_BLK = 256;
 #ifndef MPC_FUSED_WAVES
 #define MPC_FUSED_WAVES 3
 #endif
-template <int MODEL, bool SHARED_CL>
+template <int MODEL, bool SHARED_CL, bool PA = false>
 __global__ void __launch_bounds__(FUSED_BLK, MPC_FUSED_WAVES)
-stage_adjoint_kernel(const DevCfg c, const Workspace w, const int *__restrict__ counts, int nG_imm, int nC_imm,
+stage_adjoint_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, int nG_imm, int nC_imm,
                      int *__restrict__ desc)
 {
     static_assert(MODEL == KIN, "the fused K1b + K1c kernel is the kinematic model's");
@@ -772,10 +800,13 @@ stage_adjoint_kernel(const DevCfg c, const Workspace w, const int *__restrict__ 
             const double *__restrict__ clp = SHARED_CL ? w.cl : w.cl + (size_t)w.cl_index[a] * 2 * (size_t)c.S;
             double *const r = s_rec + k * SPB + j;
             const auto put = [=](int f, double v) { r[(size_t)f * NS] = v; };
-            if (is_g) stage_sens_record<MODEL>(c, xs, xe, d, dl, put);
+            DevCfg cm_;
+            if constexpr (PA) { cm_ = c; agent_cfg(cm_, w.ptab, w.pidx, a); }
+            const DevCfg &cm = PA ? cm_ : c;
+            if (is_g) stage_sens_record<MODEL>(cm, xs, xe, d, dl, put);
             Geom g;
             stage_geom(c, w, clp, SHARED_CL ? 0 : w.cl_index[a], xe[0], xe[1], g);
-            stage_record<MODEL>(c, w, a, ch2, is_g, k, xs, xe, d, dl, g, put);
+            stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put);
         }
     }
     __syncthreads();

@@ -231,10 +231,14 @@ __global__ void __launch_bounds__(256) solo_list_kernel(const Workspace w, int *
 }
 
 // K1 alone through the wave-per-agent evaluation (standalone entry point, parity tests): agent = block
-template <int MODEL>
-__global__ void __launch_bounds__(64, 1) solo_eval_kernel(const DevCfg c, const Workspace w, int want_grad)
+template <int MODEL, bool PA = false>
+__global__ void __launch_bounds__(64, 1) solo_eval_kernel(const DevCfg c_, const WsArg<PA> w, int want_grad)
 {
     extern __shared__ double s_solo[];
+    // (PA: the agent's row is wave-uniform -- scalar loads into the private DevCfg: agent_cfg_uniform)
+    DevCfg cm_;
+    if constexpr (PA) { cm_ = c_; agent_cfg_uniform(cm_, w.ptab, w.pidx, blockIdx.x); }
+    const DevCfg &c = PA ? cm_ : c_;
     double *traj = s_solo;
     double *rec = traj + (size_t)(c.N + 1) * ModelDim<MODEL>::NX;
 #if MPC_DEV_STAMP == 5
@@ -247,8 +251,9 @@ __global__ void __launch_bounds__(64, 1) solo_eval_kernel(const DevCfg c, const 
 
 // One agent's solve with the lookahead (Pacejka, NE = 1): the loop of solo_kernel with a cache lookup before every
 // evaluation trip and candidates riding in the free slots of the trip.
+// (cm: the DevCfg the evaluations run on -- c itself, or the agent's private one when a parameter table is bound)
 template <int MC>
-__device__ __forceinline__ void solo_agent_la(const DevCfg &c, const Workspace &w, int a, int lane, double *hist,
+__device__ __forceinline__ void solo_agent_la(const DevCfg &c, const DevCfg &cm, const Workspace &w, int a, int lane, double *hist,
                                               double *traj, double *rec, double *la_base, long long max_trips)
 {
 #pragma clang fp contract(off)   // the candidate points are formed by the state machine's own functions: same roundings
@@ -367,7 +372,7 @@ __device__ __forceinline__ void solo_agent_la(const DevCfg &c, const Workspace &
             }
         }
         __builtin_amdgcn_wave_barrier();
-        solo_eval_la(c, w, a, lane, slots, traj, rec);
+        solo_eval_la(cm, w, a, lane, slots, traj, rec);
         for (int j = 0; j < ncand; j++) if (lane == 0) cache.fl[cand_e[j]] = cand_g[j] ? 2 : 1;
         la_evals += (double)ncand;
         __builtin_amdgcn_wave_barrier();
@@ -388,9 +393,11 @@ __device__ __forceinline__ void solo_agent_la(const DevCfg &c, const Workspace &
 template <int MODEL> struct SoloOcc { static constexpr int WPS = MODEL == KIN ? MPC_SOLO_WPS_KIN : 1; };
 
 // LA: the lookahead variant (host: solo_lookahead) -- a kernel of its own, so that neither holds the other's code
-template <int MODEL, int NE, int MC, bool LA = false>
+// PA: the per-agent variant (a parameter table is bound): the evaluations of agent a run on the handle's DevCfg with
+// the fields of a's row, read by scalar loads when the wave claims the agent; the state machine keeps the handle's
+template <int MODEL, int NE, int MC, bool LA = false, bool PA = false>
 __global__ void __launch_bounds__(64 * SOLO_WAVES, SoloOcc<MODEL>::WPS)
-solo_kernel(const DevCfg c, const Workspace w, const int *__restrict__ list, int *__restrict__ ctr,
+solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int *__restrict__ ctr,
             long long max_trips)
 {
     extern __shared__ double s_solo[];
@@ -412,7 +419,13 @@ solo_kernel(const DevCfg c, const Workspace w, const int *__restrict__ list, int
             if (lane == 0) i = atomicAdd(&ctr[0], 1);
             i = __builtin_amdgcn_readfirstlane(i);
             if (i >= total) break;
-            solo_agent_la<MC>(c, w, list ? list[i] : i, lane, hist, traj, rec, la_base, max_trips);
+            const int a = list ? list[i] : i;
+            if constexpr (PA) {
+                DevCfg cm = c;
+                agent_cfg_uniform(cm, w.ptab, w.pidx, a);
+                solo_agent_la<MC>(c, cm, w, a, lane, hist, traj, rec, la_base, max_trips);
+            } else
+            solo_agent_la<MC>(c, c, w, a, lane, hist, traj, rec, la_base, max_trips);
         }
         return;
     }
@@ -422,6 +435,9 @@ solo_kernel(const DevCfg c, const Workspace w, const int *__restrict__ list, int
         i = __builtin_amdgcn_readfirstlane(i);
         if (i >= total) break;
         const int a = list ? list[i] : i;
+        DevCfg cm_;
+        if constexpr (PA) { cm_ = c; agent_cfg_uniform(cm_, w.ptab, w.pidx, a); }
+        const DevCfg &cm = PA ? cm_ : c;
 #if MPC_DEV_STAMP == 5
         const long long st0 = __builtin_amdgcn_s_memrealtime();
         long long ntrip = 0, t_adv = 0;
@@ -436,10 +452,10 @@ solo_kernel(const DevCfg c, const Workspace w, const int *__restrict__ list, int
             if ((req & (REQ_GRAD | REQ_COST)) == 0) break;              // uniform: the agent is done
 #if MPC_DEV_STAMP == 5
             t_adv += __builtin_amdgcn_s_memrealtime() - ta;
-            solo_eval<MODEL>(c, w, a, lane, req, traj, rec, clk);
+            solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk);
             ntrip++;
 #else
-            solo_eval<MODEL>(c, w, a, lane, req, traj, rec);
+            solo_eval<MODEL>(cm, w, a, lane, req, traj, rec);
 #endif
         }
 #if MPC_DEV_STAMP == 5

@@ -96,6 +96,16 @@ struct Workspace {
     int St;                                        // stride of the slot-indexed K1 scratch
     int Ls;                                        // stride between the two work lists
 };
+// The workspace as the host keeps it and as the per-agent kernels (template flag PA) receive it: with the parameter
+// table of mpc_set_agent_params (both null: none bound).  Every other kernel takes the Workspace part alone, so its
+// argument segment -- and its code -- is what it was before the table existed.
+struct WorkspacePA : Workspace {
+    const double *ptab;                            // [P][NPARAM] caller's table
+    const int *pidx;                               // [B]         caller's row index per agent
+};
+template <bool PA> struct WsArgT { using type = Workspace; };
+template <> struct WsArgT<true> { using type = WorkspacePA; };
+template <bool PA> using WsArg = typename WsArgT<PA>::type;
 
 // The DevCfg and Workspace of a kernel whose first two parameters they are (`const DevCfg c, const Workspace w`),
 // read where a loop body uses them.  Left to itself the compiler loads their words once, before the loop, and keeps

@@ -40,6 +40,7 @@ class BatchedMPC:
         self._h = h
         self._pending = False       # an asynchronous solve is in flight: the worker thread owns the handle
         self._cl_key, self._cl_keep = None, None   # the centerline table the search tables were last built for
+        self._params_keep = None    # (table, index, plant_index) of set_agent_params, alive while bound
         import os
         # nearest-point search of K1b as the library chose it at mpc_create: 2 grid of index ranges (default), 0 the
         # full scan (MPC_NEAREST_SCAN) -- which needs no tables
@@ -116,6 +117,40 @@ class BatchedMPC:
                     _lib.check(self.lib.mpc_centerline_blocks(self._h, _ptr(cl), int(cl.shape[0]), self._stream()))
                     self._cl_key, self._cl_keep = key, cl
         return cl
+
+    # ------------------------------------------------------------------ per-agent parameters
+    def set_agent_params(self, table, index, plant_index=None):
+        """Binds a per-agent parameter table (mpc_set_agent_params): table [P, 31] float64 (rows as
+        _lib.param_rows makes them), index [B] int32 = the row of agent b, plant_index [B] int32 = the row the PLANT
+        of closed_loop advances with (None: the same).  Bound, every model-dependent call (rhs, rollout, stage_cost,
+        eval_cost_grad, solve, solve_async, closed_loop) uses agent b's row and serves batches of exactly B agents.
+        The tensors stay the caller's: the library reads them at every call, so rows may be rewritten in place
+        between calls; the engine keeps them alive until clear_agent_params()."""
+        self._free()
+        if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] != _lib.NPARAM or table.shape[0] < 1:
+            raise ValueError(f"table: expected a tensor [P >= 1, {_lib.NPARAM}]")
+        self._chk(table, table.shape, "table")
+        if not isinstance(index, torch.Tensor) or index.dim() != 1 or index.shape[0] < 1:
+            raise ValueError("index: expected a tensor [B >= 1]")
+        B, P = int(index.shape[0]), int(table.shape[0])
+        for t, name in ((index, "index"), (plant_index, "plant_index")):
+            if t is None:
+                continue
+            self._chk(t, (B,), name, torch.int32)
+            if int(t.min()) < 0 or int(t.max()) >= P:
+                raise ValueError(f"{name} out of range")
+        _lib.check(self.lib.mpc_set_agent_params(self._h, _ptr(table), P, _ptr(index), _ptr(plant_index), B))
+        self._params_keep = (table, index, plant_index)
+
+    def clear_agent_params(self):
+        """Unbinds the parameter table: the engine is what it was before set_agent_params."""
+        self._free()
+        _lib.check(self.lib.mpc_set_agent_params(self._h, None, 0, None, None, 0))
+        self._params_keep = None
+
+    @property
+    def agent_params_bound(self):
+        return self._params_keep is not None
 
     def invalidate_centerline_tables(self):
         """Forget the nearest-point search tables: the next call rebuilds them for the table it is given."""

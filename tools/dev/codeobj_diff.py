@@ -1,0 +1,82 @@
+"""Compares the gfx950 code-object metadata of two builds of libmpc_hip.so, kernel by kernel.
+
+    python tools/dev/codeobj_diff.py OLD.so NEW.so
+
+For every kernel present in both: registers (vector, accumulator, scalar), spill counts, scratch and static LDS
+bytes must be equal; differences are listed.  Kernels only in NEW (the per-agent instantiations) are listed with
+the same figures and the waves per SIMD their registers allow (512 unified registers per SIMD lane on gfx950,
+allocated in blocks of 8; at most 8 waves).  A kernel that gained a trailing `false` template argument (the
+per-agent flag at its default) is matched with the old kernel of the same name without it.  No GPU needed.
+"""
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+
+import yaml
+
+KEYS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count",
+        ".private_segment_fixed_size", ".group_segment_fixed_size")
+
+
+def tool(name):
+    p = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", name)
+    return p if os.access(p, os.X_OK) else shutil.which(name)
+
+
+def kernels(lib):
+    with tempfile.TemporaryDirectory() as d:
+        fat, co = os.path.join(d, "fat"), os.path.join(d, "co.o")
+        subprocess.check_call([tool("llvm-objcopy"), "--dump-section=.hip_fatbin=" + fat, lib, os.path.join(d, "x")])
+        subprocess.check_call([tool("clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
+                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
+        notes = subprocess.check_output([tool("llvm-readelf"), "--notes", co], text=True)
+    doc = notes[notes.index("---"):notes.index("\n...", notes.index("---"))]
+    ks = yaml.safe_load(doc)["amdhsa.kernels"]
+    filt = tool("llvm-cxxfilt") or tool("c++filt")
+    names = subprocess.check_output([filt] + [k[".name"] for k in ks], text=True).split("\n")
+    out = {}
+    for k, nm in zip(ks, names):
+        out[re.sub(r"\(.*$", "", nm).replace("void ", "").replace("mpc::", "")] = k
+    return out
+
+
+def waves(k):
+    regs = k[".vgpr_count"]           # (the unified count: accumulator registers included)
+    regs = max(8, (regs + 7) // 8 * 8)
+    return min(8, 512 // regs)
+
+
+def fmt(k):
+    return "vgpr %3d  agpr %3d  sgpr %3d  spill v/s %3d/%3d  scratch %4d B  LDS %5d B" % tuple(k[x] for x in KEYS)
+
+
+def main():
+    old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+    same, diff, added = 0, [], []
+    for nm, k in sorted(new.items()):
+        o = old.get(nm)
+        if o is None:
+            o = old.get(re.sub(r", false>$", ">", nm)) or old.get(re.sub(r"<false>$", "", nm))
+        if o is None:
+            added.append((nm, k))
+        elif all(o[x] == k[x] for x in KEYS):
+            same += 1
+        else:
+            diff.append((nm, o, k))
+    gone = [nm for nm in old if nm not in new and not any(
+        re.sub(r", false>$", ">", n2) == nm or re.sub(r"<false>$", "", n2) == nm for n2 in new)]
+    print("kernels: %d old, %d new; %d in both with identical figures, %d in both that differ, %d only new, %d only old"
+          % (len(old), len(new), same, len(diff), len(added), len(gone)))
+    for nm, o, k in diff:
+        print("DIFFERS %s\n   old %s\n   new %s" % (nm, fmt(o), fmt(k)))
+    for nm in gone:
+        print("ONLY OLD %s" % nm)
+    for nm, k in added:
+        print("NEW %-62s %s  -> %d waves/SIMD" % (nm, fmt(k), waves(k)))
+
+
+if __name__ == "__main__":
+    main()
