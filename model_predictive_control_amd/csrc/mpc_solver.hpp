@@ -1264,7 +1264,7 @@ constexpr int STEP_WAVES = 4;
 
 // The occupancy target of a step kernel: its waves per SIMD, which -- a workgroup being one wave on each of a CU's
 // four SIMDs -- is also the number of its workgroups that share a CU.  The kernel is compiled for it (launch_bounds)
-// and the host sizes the LDS copy of the history from it (step_lds_pairs in mpc_api.hip), so the two cannot drift
+// and the host sizes the LDS copy of the history from it (step_lds_pairs: mpc_launch.hpp), so the two cannot drift
 // apart.  The unconstrained one-element-per-lane variant with the history in LDS -- the benchmark's -- runs five
 // (84 VGPRs, no spills); every other variant keeps its two or three.
 __host__ __device__ constexpr int step_waves_per_simd(int ne, int mc, bool hasm)

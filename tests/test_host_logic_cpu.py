@@ -198,3 +198,28 @@ def test_readme_switch_table_names_every_switch_read():
     assert len(table) == len(set(table)), "a switch is listed twice"
     assert set(table) == read
     assert "MPC_STEP_REGS" in read and "MPC_LIB_PATH" in read       # (both sources were searched)
+
+
+def test_library_sources_are_the_include_closure_of_the_translation_unit():
+    """_lib._SRC -- what the rebuild check looks at and what mpc_source_hash() covers -- is exactly csrc/mpc_api.hip,
+    the one file the build command compiles, plus every file of csrc/ it reaches through quoted #include lines.  A
+    header added to csrc/ and included, but missing from _SRC, would change the library without changing its hash."""
+    import re
+    from model_predictive_control_amd import _lib
+    csrc = os.path.dirname(_lib._SRC[0])
+    assert os.path.basename(_lib._SRC[0]) == "mpc_api.hip"       # (build() compiles _SRC[0])
+    closure, todo = set(), ["mpc_api.hip"]
+    while todo:
+        f = todo.pop()
+        if f in closure:
+            continue
+        closure.add(f)
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(csrc, f)).read(), re.M):
+            path = os.path.normpath(os.path.join(csrc, inc))
+            if os.path.dirname(path) == csrc:
+                todo.append(os.path.basename(path))
+            else:                                                # the one include that leaves csrc/: the C header
+                assert path == os.path.normpath(_lib._HDR), inc
+    assert len(_lib._SRC) == len(set(_lib._SRC)), "a source is listed twice"
+    assert all(os.path.dirname(p) == csrc for p in _lib._SRC)
+    assert {os.path.basename(p) for p in _lib._SRC} == closure
