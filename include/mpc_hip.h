@@ -18,7 +18,8 @@
  *  - centerlines: table cl [C][2S], each row flat [x_0..x_{S-1}, y_0..y_{S-1}]
  *    (main.py:113 ravel(order='F')); cl_index [B] int32 selects a row per agent, NULL = row 0.
  *  - every call is asynchronous on `stream` (a hipStream_t passed as void*) except
- *    mpc_solve_batch / mpc_closed_loop, which poll device counters and return when the batch is solved.
+ *    mpc_solve_batch / mpc_solve_active / mpc_closed_loop / mpc_closed_loop_event, which poll device counters and return
+ *    when the batch is solved.
  *  - between mpc_solve_batch_async and mpc_solve_wait the handle belongs to its worker thread: every
  *    other call on it returns MPC_E_ARG without touching it.
  *  - return value: 0 on success, negative MPC_E_* otherwise; mpc_last_error() explains.
@@ -106,8 +107,8 @@ int mpc_step_lds_plan(int n, int M, int m, int chain, int lds_pairs, int *pairs,
  * mpc_default_params (host only): the row `cfg` describes.
  * mpc_set_agent_params: table == NULL unbinds (the handle is then what it was before).  Bound, the calls that
  * evaluate the model -- mpc_rhs, mpc_rollout, mpc_stage_cost, mpc_eval_cost_grad(_wave), mpc_solve_batch(_async),
- * mpc_closed_loop -- use row index[b] for agent b and return MPC_E_ARG for a batch size other than B;
- * mpc_closed_loop advances the plant with row plant_index[b] (NULL: the same rows; main.py:145's separate `param`).
+ * mpc_solve_active, mpc_closed_loop(_event) -- use row index[b] for agent b and return MPC_E_ARG for a batch size other than B;
+ * mpc_closed_loop(_event) advance the plant with row plant_index[b] (NULL: the same rows; main.py:145's separate `param`).
  * The input box, the constraint data, Ts, N and every solver parameter stay the handle's.  table [P][MPC_NPARAM],
  * index [B] and plant_index [B] are DEVICE memory of the caller, read at every call: rows may be rewritten in place
  * between calls without binding again.  The P rows are checked once, at bind time, through a synchronous copy:
@@ -196,6 +197,46 @@ int mpc_solve_wait(mpc_handle *h);
 int mpc_closed_loop(mpc_handle *h, int B, int T, int shift, double *x, const double *cl,
                     const int32_t *cl_index, double *U, double *lambda, double *traj_x,
                     double *traj_u, int32_t *fail_count, double *stats, void *stream);
+
+/* The masked solve: active [B] is a DEVICE mask; the agents with active[b] != 0 are solved exactly as mpc_solve_batch
+ * solves them (warm start in, solution out, the same bits), and every byte of U, lambda and stats that belongs to
+ * another agent is left as it was.  *n_active (HOST int, NULL ok) receives the number of agents solved; none active:
+ * no solver kernel runs, MPC_OK.  By compaction: an index-ascending list of the active agents (two passes, no
+ * atomics: reproducible), their x0 / U / lambda / cl_index / parameter-row index gathered into buffers of the handle,
+ * the solve of mpc_solve_batch on those rows, U / lambda / stats scattered back.  With a parameter table bound B is the
+ * bound batch.  Blocking, like mpc_solve_batch. */
+int mpc_solve_active(mpc_handle *h, int B, const int32_t *active, const double *x0, const double *cl,
+                     const int32_t *cl_index, double *U, double *lambda, double *stats, int32_t *n_active,
+                     void *stream);
+
+/* The trigger of the event-triggered loop, on its own (asynchronous on `stream`): e = x - xhat, the heading component
+ * (index 2) reduced by e -= 2 pi rint(e / 2 pi); dev2[b] = sum_i w_i e_i^2 in index order, each operation rounded on
+ * its own; fire[b] = held[b] < 0 || held[b] >= max_hold || dev2[b] >= thr^2 (a non-finite dev2 fires; thr = 0 always
+ * fires; thr = +inf leaves the hold limit alone).  x, xhat [B][nx], held [B] int32, fire [B] int32, dev2 [B] (NULL ok):
+ * DEVICE memory; w [nx] is a HOST array.  MPC_E_ARG unless thr >= 0 and 1 <= max_hold <= N. */
+int mpc_trigger_eval(mpc_handle *h, int B, const double *x, const double *xhat, const int32_t *held,
+                     const double *w, double thr, int max_hold, double *dev2, int32_t *fire, void *stream);
+
+/* Event-triggered closed loop: an agent keeps applying the plan it holds until the plant has drifted from the plan's
+ * own prediction by thr or more (the trigger above) or max_hold stages of it have been applied; only then is it solved
+ * again (the masked solve above).  Per-agent state: the plan U as last solved; held [B] int32 inout, the stages of it
+ * already applied (-1: no plan yet); the nominal state xhat [B][nx], owned by the handle.  Step t:
+ *   1. fire = trigger(x, xhat, held);
+ *   2. shift != 0: a firing agent's plan is shifted in place by `held` stages, the last stage repeated into the tail;
+ *   3. the firing agents are solved (warm start U, lambda), then held = 0, xhat = x;
+ *   4. fail_count [B] accumulates status != Converged, solve_count [B] the solves, of the agents solved at this step;
+ *   5. every agent applies u = U[2 held .. 2 held + 1]: x <- f_d(x, u) on the plant's row (+ disturbance[b][t][:] when
+ *      that pointer is not NULL: [B][T][nx], the caller's data -- the library draws no random numbers),
+ *      xhat <- f_d(xhat, u) on the controller's row, held += 1; traj_x [B][T][nx], traj_u [B][T][2] and
+ *      solved [B][T] (uint8: the agent was solved at step t) are written (each NULL ok, as solve_count, fail_count).
+ * On return U is the plan as last solved and held says how far it is consumed: a later call on the same handle and
+ * batch continues from there (on a handle that holds no nominal states for this batch every agent is solved at the
+ * first step).  stats [B][MPC_NSTATS] (NULL ok) holds each agent's most recent solve.  thr = 0 is mpc_closed_loop,
+ * bit for bit.  Blocking. */
+int mpc_closed_loop_event(mpc_handle *h, int B, int T, int shift, const double *w, double thr, int max_hold,
+                          double *x, const double *cl, const int32_t *cl_index, double *U, double *lambda,
+                          int32_t *held, const double *disturbance, double *traj_x, double *traj_u,
+                          uint8_t *solved, int32_t *solve_count, int32_t *fail_count, double *stats, void *stream);
 
 /* profiling aid: rounds (eval launches) and kernel time of the last mpc_solve_batch */
 int mpc_last_solve_info(mpc_handle *h, int64_t *rounds, int64_t *evals_grad, int64_t *evals_cost,

@@ -31,7 +31,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPC_LIB_PATH", os.path.join(_HERE, "libmpc_hip.so"))  # override: dev experiments
 _SRC = [os.path.join(_HERE, "csrc", f) for f in ("mpc_api.hip", "mpc_handle.hpp", "mpc_launch.hpp", "mpc_rounds.hpp",
                                                   "mpc_aux.hpp", "mpc_eval.hpp", "mpc_solver.hpp", "mpc_device.hpp",
-                                                  "mpc_game.hpp", "mpc_solo.hpp")]
+                                                  "mpc_game.hpp", "mpc_solo.hpp", "mpc_event.hpp")]
 _HDR = os.path.join(os.path.dirname(_HERE), "include", "mpc_hip.h")
 
 MODEL_KINEMATIC, MODEL_PACEJKA = 0, 1
@@ -50,6 +50,7 @@ EXPORTS = [
     "mpc_set_round_limit", "mpc_stream_concurrency", "mpc_last_solo_ms",
     "mpc_set_poll_timeout", "mpc_debug_spin", "mpc_debug_records", "mpc_debug_record_names", "mpc_source_hash",
     "mpc_last_lookahead", "mpc_step_lds_plan", "mpc_default_params", "mpc_set_agent_params",
+    "mpc_solve_active", "mpc_trigger_eval", "mpc_closed_loop_event",
 ]
 NREC = 64
 NPARAM = 31     # MPC_NPARAM: doubles per row of the per-agent parameter table
@@ -138,6 +139,10 @@ def load():
     L.mpc_solve_batch_async.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.mpc_solve_wait.argtypes = [vp]
     L.mpc_closed_loop.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mpc_solve_active.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int32), vp]
+    L.mpc_trigger_eval.argtypes = [vp, ci, vp, vp, vp, C.POINTER(C.c_double), C.c_double, ci, vp, vp, vp]
+    L.mpc_closed_loop_event.argtypes = [vp, ci, ci, ci, C.POINTER(C.c_double), C.c_double, ci, vp, vp, vp, vp, vp, vp,
+                                        vp, vp, vp, vp, vp, vp, vp, vp]
     L.mpc_last_solve_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                       C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double)]

@@ -109,6 +109,8 @@ extern "C" int mpc_destroy(mpc_handle *h)
     (void)hipSetDevice(h->device);
     if (h->arena) (void)hipFree(h->arena);
     if (h->stage) (void)hipFree(h->stage);
+    if (h->ev.base) (void)hipFree(h->ev.base);
+    if (h->ev.xhat) (void)hipFree(h->ev.xhat);
     if (h->cl_gmeta) (void)hipFree(h->cl_gmeta);
     if (h->cl_gxy) (void)hipFree(h->cl_gxy);
     if (h->cl_gcells) (void)hipFree(h->cl_gcells);
@@ -334,26 +336,31 @@ extern "C" int mpc_step_lds_plan(int n, int M, int m, int chain, int lds_pairs, 
     return MPC_OK;
 }
 
+// the solve proper on B agents whose parameter rows (table bound) are pidx[b]: the caller's batch and the handle's
+// bound index (mpc_solve_batch), or the gathered rows of a masked solve and their gathered indices
+static int solve_core(mpc_handle *h, int B, const double *x0, const double *cl, const int32_t *cl_index, const int32_t *pidx,
+                      double *U, double *lambda, double *stats, hipStream_t s)
+{
+    int rc = reserve(h, B); if (rc) return rc;
+    WorkspacePA &w = h->ws;
+    w.cl = cl; w.cl_index = cl_index; w.x0 = x0; w.xo = U; w.y = lambda; w.psi_direct = nullptr;
+    w.near = near_for(h, cl);
+    w.ptab = h->ptab; w.pidx = pidx;
+    w.xe = w.ws_xe; w.ge = w.ws_ge; w.yhe = w.ws_yhe; w.Sig = w.ws_Sig;
+    rc = run_solver(h, s); if (rc) return rc;
+    if (stats) hipLaunchKernelGGL(stats_kernel, grid_for(B, 256), dim3(256), 0, s, w, stats);
+    HIPCHK(hipGetLastError());
+    return bounded_sync(h, s, "mpc_solve_batch");
+}
 static int solve_batch_impl(mpc_handle *h, int B, const double *x0, const double *cl, const int32_t *cl_index,
                             double *U, double *lambda, double *stats, void *stream, bool from_worker)
 {
     int rc = check_common(h, B, "mpc_solve_batch", from_worker); if (rc) return rc;
     if (B == 0) return MPC_OK;
     if (!x0 || !cl || !U) return fail(MPC_E_ARG, "mpc_solve_batch: null buffer");
-    const DevCfg &c = h->dc;
-    if (c.m && !lambda) return fail(MPC_E_ARG, "mpc_solve_batch: lambda is required when m > 0");
+    if (h->dc.m && !lambda) return fail(MPC_E_ARG, "mpc_solve_batch: lambda is required when m > 0");
     rc = check_bound(h, B, "mpc_solve_batch"); if (rc) return rc;
-    rc = reserve(h, B); if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    WorkspacePA &w = h->ws;
-    w.cl = cl; w.cl_index = cl_index; w.x0 = x0; w.xo = U; w.y = lambda; w.psi_direct = nullptr;
-    w.near = near_for(h, cl);
-    w.ptab = h->ptab; w.pidx = h->pidx;
-    w.xe = w.ws_xe; w.ge = w.ws_ge; w.yhe = w.ws_yhe; w.Sig = w.ws_Sig;
-    rc = run_solver(h, s); if (rc) return rc;
-    if (stats) hipLaunchKernelGGL(stats_kernel, grid_for(B, 256), dim3(256), 0, s, w, stats);
-    HIPCHK(hipGetLastError());
-    return bounded_sync(h, s, "mpc_solve_batch");
+    return solve_core(h, B, x0, cl, cl_index, h->pidx, U, lambda, stats, (hipStream_t)stream);
 }
 extern "C" int mpc_solve_batch(mpc_handle *h, int B, const double *x0, const double *cl, const int32_t *cl_index, double *U,
                                double *lambda, double *stats, void *stream)
@@ -437,6 +444,143 @@ extern "C" int mpc_closed_loop(mpc_handle *h, int B, int T, int shift, double *x
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));
     return MPC_OK;
+}
+
+// The masked solve, by compaction: list the active agents (index-ascending, two passes, no atomics), gather their rows
+// into the handle's staging buffers, run the solve that mpc_solve_batch runs on those n_active agents, scatter U,
+// lambda and stats back.  The solver kernels see a plain batch; the rows of the other agents are never written.  The
+// count reaches the host behind the gather through pinned memory and the bounded wait every solve uses.
+static int solve_active_impl(mpc_handle *h, int B, const int32_t *active, const double *x0, const double *cl,
+                             const int32_t *cl_index, double *U, double *lambda, double *stats, int32_t *n_active,
+                             hipStream_t s, bool final_sync)
+{
+    int rc = reserve_event(h, B); if (rc) return rc;
+    const DevCfg &c = h->dc;
+    mpc_handle::EventBufs &e = h->ev;
+    const dim3 gblk = grid_for(B, EV_BLK), grows = grid_for(B, EV_BLK / 64);
+    hipLaunchKernelGGL(active_count_kernel, gblk, dim3(EV_BLK), 0, s, B, active, e.blk);
+    hipLaunchKernelGGL(active_list_kernel, gblk, dim3(EV_BLK), 0, s, B, active, e.blk, e.list, e.count);
+    ActiveRows r;
+    r.list = e.list; r.count = e.count; r.nx = c.nx; r.n = c.n; r.m = c.m;
+    r.x0 = const_cast<double *>(x0); r.U = U; r.lam = lambda; r.stats = stats;
+    r.cl_index = cl_index; r.pidx = h->ptab ? h->pidx : nullptr;
+    r.xs = e.xs; r.Us = e.Us; r.lams = e.lams; r.stats_s = e.stats_s; r.cis = e.cis; r.pis = e.pis;
+    hipLaunchKernelGGL(active_gather_kernel, grows, dim3(EV_BLK), 0, s, r);
+    int *cnt = (int *)((char *)h->host_counts + 384);   // pinned (see host_counts)
+    HIPCHK(hipMemcpyAsync(cnt, e.count, sizeof(int), hipMemcpyDeviceToHost, s));
+    rc = bounded_sync(h, s, "mpc_solve_active"); if (rc) return rc;
+    const int nA = *cnt;
+    if (nA < 0 || nA > B) return fail(MPC_E_HIP, "mpc_solve_active: the compaction counted " + std::to_string(nA) + " of " + std::to_string(B) + " agents");
+    if (n_active) *n_active = nA;
+    if (nA == 0) return MPC_OK;
+    rc = solve_core(h, nA, e.xs, cl, cl_index ? e.cis : nullptr, r.pidx ? e.pis : nullptr, e.Us, c.m ? e.lams : nullptr,
+                    stats ? e.stats_s : nullptr, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(active_scatter_kernel, grid_for(nA, EV_BLK / 64), dim3(EV_BLK), 0, s, r);
+    HIPCHK(hipGetLastError());
+    return final_sync ? bounded_sync(h, s, "mpc_solve_active") : MPC_OK;
+}
+
+extern "C" int mpc_solve_active(mpc_handle *h, int B, const int32_t *active, const double *x0, const double *cl,
+                                const int32_t *cl_index, double *U, double *lambda, double *stats, int32_t *n_active,
+                                void *stream)
+{
+    if (n_active) *n_active = 0;
+    int rc = check_common(h, B, "mpc_solve_active"); if (rc) return rc;
+    if (B == 0) return MPC_OK;
+    if (!active || !x0 || !cl || !U) return fail(MPC_E_ARG, "mpc_solve_active: null buffer");
+    if (h->dc.m && !lambda) return fail(MPC_E_ARG, "mpc_solve_active: lambda is required when m > 0");
+    rc = check_bound(h, B, "mpc_solve_active"); if (rc) return rc;   // the caller's B; the compact batch is the library's
+    return solve_active_impl(h, B, active, x0, cl, cl_index, U, lambda, stats, n_active, (hipStream_t)stream, true);
+}
+
+// what mpc_trigger_eval and mpc_closed_loop_event ask of the trigger's arguments, checked before anything else (and so
+// without a device); max_hold <= N needs the handle and is checked behind its null test
+static int check_trigger_args(const char *who, const double *w, double thr, int max_hold, const void *held)
+{
+    if (!w || !held) return fail(MPC_E_ARG, std::string(who) + ": null w or held");
+    if (!(thr >= 0.0)) return fail(MPC_E_ARG, std::string(who) + ": thr must be >= 0 (+inf: the hold limit alone)");
+    if (max_hold < 1) return fail(MPC_E_ARG, std::string(who) + ": max_hold must be in [1, N]");
+    return MPC_OK;
+}
+static int check_max_hold(const mpc_handle *h, const char *who, int max_hold)
+{
+    if (max_hold > h->cfg.N) return fail(MPC_E_ARG, std::string(who) + ": max_hold must be in [1, N]");
+    return MPC_OK;
+}
+static TrigW trigger_weights(const mpc_handle *h, const double *w)
+{
+    TrigW tw{};
+    for (int i = 0; i < h->dc.nx; i++) tw.w[i] = w[i];
+    return tw;
+}
+static void launch_trigger(mpc_handle *h, hipStream_t s, int B, const double *x, const double *xhat, const int32_t *held,
+                           const TrigW &tw, double thr, int max_hold, int force, double *dev2, int32_t *fire, double *U)
+{
+    with_model(h->dc.model, [&](auto MODEL) {
+        hipLaunchKernelGGL((trigger_kernel<ModelDim<MODEL()>::NX>), grid_for(B, 64), dim3(64), 0, s, B, h->dc.N, x, xhat, held, tw,
+                           thr * thr, max_hold, force, dev2, fire, U);
+    });
+}
+
+extern "C" int mpc_trigger_eval(mpc_handle *h, int B, const double *x, const double *xhat, const int32_t *held,
+                                const double *w, double thr, int max_hold, double *dev2, int32_t *fire, void *stream)
+{
+    int rc = check_trigger_args("mpc_trigger_eval", w, thr, max_hold, held); if (rc) return rc;
+    if (!h) return fail(MPC_E_ARG, "mpc_trigger_eval: null handle");
+    rc = check_max_hold(h, "mpc_trigger_eval", max_hold); if (rc) return rc;
+    rc = check_common(h, B, "mpc_trigger_eval"); if (rc) return rc;
+    if (B == 0) return MPC_OK;
+    if (!x || !xhat || !fire) return fail(MPC_E_ARG, "mpc_trigger_eval: null buffer");
+    launch_trigger(h, (hipStream_t)stream, B, x, xhat, held, trigger_weights(h, w), thr, max_hold, 0, dev2, fire, nullptr);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
+// Event-triggered closed loop: per step the trigger (which also shifts a firing agent's plan by the stages it has
+// applied), the masked solve of the agents that fired, and one kernel that applies stage `held` of every agent's plan
+// to plant and nominal state.  Control returns to the host once per step for the count of firing agents (and, inside
+// the solve, once per round window, as in every solve); data never leaves the device.
+extern "C" int mpc_closed_loop_event(mpc_handle *h, int B, int T, int shift, const double *w, double thr, int max_hold,
+                                     double *x, const double *cl, const int32_t *cl_index, double *U, double *lambda,
+                                     int32_t *held, const double *disturbance, double *traj_x, double *traj_u,
+                                     uint8_t *solved, int32_t *solve_count, int32_t *fail_count, double *stats, void *stream)
+{
+    int rc = check_trigger_args("mpc_closed_loop_event", w, thr, max_hold, held); if (rc) return rc;
+    if (T < 0) return fail(MPC_E_ARG, "mpc_closed_loop_event: negative T");
+    if (!h) return fail(MPC_E_ARG, "mpc_closed_loop_event: null handle");
+    rc = check_max_hold(h, "mpc_closed_loop_event", max_hold); if (rc) return rc;
+    rc = check_common(h, B, "mpc_closed_loop_event"); if (rc) return rc;
+    if (B == 0 || T == 0) return MPC_OK;
+    if (!x || !cl || !U) return fail(MPC_E_ARG, "mpc_closed_loop_event: null buffer");
+    const DevCfg &c = h->dc;
+    if (c.m && !lambda) return fail(MPC_E_ARG, "mpc_closed_loop_event: lambda is required when m > 0");
+    rc = check_bound(h, B, "mpc_closed_loop_event"); if (rc) return rc;
+    rc = reserve_event(h, B); if (rc) return rc;
+    bool fresh = false;
+    rc = reserve_xhat(h, B, &fresh); if (rc) return rc;
+    mpc_handle::EventBufs &e = h->ev;
+    hipStream_t s = (hipStream_t)stream;
+    double *st = stats ? stats : e.stats_own;
+    const TrigW tw = trigger_weights(h, w);
+    for (int t = 0; t < T; t++) {
+        // (nominal states just allocated: every agent re-plans at the first step, whatever `held` says)
+        launch_trigger(h, s, B, x, e.xhat, held, tw, thr, max_hold, fresh && t == 0, nullptr, e.fire, shift ? U : nullptr);
+        rc = solve_active_impl(h, B, e.fire, x, cl, cl_index, U, lambda, st, nullptr, s, false); if (rc) return rc;
+        // bound table: the plant advances with row pidx_plant[b] (null: the controller's), the nominal state with pidx[b]
+        with_model_table(h, h->pidx_plant ? h->pidx_plant : h->pidx, [&](auto MODEL, auto PA, auto... pt) {
+            if constexpr (PA())
+                hipLaunchKernelGGL((event_step_kernel<MODEL(), true, decltype(pt)..., const int32_t *>), grid_for(B, 64), dim3(64), 0, s,
+                                   c, B, t, T, x, e.xhat, U, held, e.fire, disturbance, traj_x, traj_u, solved, solve_count,
+                                   st, fail_count, pt..., h->pidx);
+            else
+                hipLaunchKernelGGL((event_step_kernel<MODEL(), false>), grid_for(B, 64), dim3(64), 0, s,
+                                   c, B, t, T, x, e.xhat, U, held, e.fire, disturbance, traj_x, traj_u, solved, solve_count,
+                                   st, fail_count);
+        });
+    }
+    HIPCHK(hipGetLastError());
+    return bounded_sync(h, s, "mpc_closed_loop_event");
 }
 
 extern "C" int mpc_last_speculation(mpc_handle *h, int64_t *issued, int64_t *used)

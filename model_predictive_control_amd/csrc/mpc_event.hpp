@@ -1,0 +1,203 @@
+// mpc_event.hpp -- kernels of the masked solve and the event-triggered closed loop (mpc_solve_active,
+// mpc_trigger_eval, mpc_closed_loop_event): the stable compaction of an active mask into an agent list, the gather /
+// scatter between the caller's batch and the handle's staging rows, the trigger and the per-step kernel that advances
+// plant and nominal state.  The solver kernels are not touched: a masked solve IS the existing solve, run on the
+// gathered rows (agents are independent, so a sliced batch gives the sliced result bit for bit).
+#pragma once
+#include "mpc_aux.hpp"
+
+namespace mpc {
+
+constexpr int EV_BLK = 256;   // threads per workgroup of the compaction kernels (four waves)
+
+MPC_DEV int ev_wave_sum(int v)
+{
+    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// Compaction, pass 1: blk[g] = active agents among the EV_BLK agents of workgroup g (wave ballot + population count)
+__global__ void __launch_bounds__(EV_BLK) active_count_kernel(int B, const int *__restrict__ active, int *__restrict__ blk)
+{
+    __shared__ int s_w[EV_BLK / 64];
+    const int a = blockIdx.x * EV_BLK + threadIdx.x;
+    const bool on = a < B && active[a] != 0;
+    const unsigned long long m = __ballot(on);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) blk[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+// Compaction, pass 2: the index-ascending list.  Workgroup g starts at the sum of blk[0 .. g) (every workgroup sums
+// that prefix itself: 256 counts at 65 536 agents), a wave at the counts of the waves before it, a lane at the set
+// bits below it in its wave's ballot.  No atomics: the same mask gives the same list.  The last workgroup writes the
+// total.
+__global__ void __launch_bounds__(EV_BLK) active_list_kernel(int B, const int *__restrict__ active, const int *__restrict__ blk,
+                                                             int *__restrict__ list, int *__restrict__ count)
+{
+    __shared__ int s_pre[EV_BLK / 64], s_w[EV_BLK / 64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int part = 0;
+    for (int i = threadIdx.x; i < (int)blockIdx.x; i += EV_BLK) part += blk[i];
+    part = ev_wave_sum(part);
+    const int a = blockIdx.x * EV_BLK + threadIdx.x;
+    const bool on = a < B && active[a] != 0;
+    const unsigned long long m = __ballot(on);
+    if (lane == 0) { s_pre[wv] = part; s_w[wv] = __popcll(m); }
+    __syncthreads();
+    int off = s_pre[0] + s_pre[1] + s_pre[2] + s_pre[3];
+    for (int k = 0; k < wv; k++) off += s_w[k];
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+    if (on) list[off + rank] = a;      // off + rank < number of active agents <= B
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == EV_BLK - 1) *count = off + s_w[EV_BLK / 64 - 1];
+}
+
+// the rows the masked solve moves between the caller's batch ([B] agents) and the staging rows ([count] agents)
+struct ActiveRows {
+    const int *list, *count;
+    int nx, n, m;
+    double *x0, *U, *lam, *stats;      // caller's (x0 is only read; lam null when m == 0; stats may be null)
+    const int *cl_index, *pidx;        // caller's (either may be null)
+    double *xs, *Us, *lams, *stats_s;  // staging
+    int *cis, *pis;
+};
+
+// one wave per listed agent: x0, U, lambda, centerline row and parameter row into staging row i
+__global__ void __launch_bounds__(EV_BLK) active_gather_kernel(const ActiveRows r)
+{
+    const int lane = threadIdx.x & 63, i = blockIdx.x * (EV_BLK / 64) + (threadIdx.x >> 6);
+    if (i >= *r.count) return;
+    const int a = r.list[i];
+    for (int j = lane; j < r.nx; j += 64) r.xs[(size_t)i * r.nx + j] = r.x0[(size_t)a * r.nx + j];
+    for (int j = lane; j < r.n; j += 64) r.Us[(size_t)i * r.n + j] = r.U[(size_t)a * r.n + j];
+    for (int j = lane; j < r.m; j += 64) r.lams[(size_t)i * r.m + j] = r.lam[(size_t)a * r.m + j];
+    if (lane == 0) {
+        if (r.cl_index) r.cis[i] = r.cl_index[a];
+        if (r.pidx) r.pis[i] = r.pidx[a];
+    }
+}
+
+// ... and U, lambda and the statistics back; rows of agents that are not listed are not written
+__global__ void __launch_bounds__(EV_BLK) active_scatter_kernel(const ActiveRows r)
+{
+    const int lane = threadIdx.x & 63, i = blockIdx.x * (EV_BLK / 64) + (threadIdx.x >> 6);
+    if (i >= *r.count) return;
+    const int a = r.list[i];
+    for (int j = lane; j < r.n; j += 64) r.U[(size_t)a * r.n + j] = r.Us[(size_t)i * r.n + j];
+    for (int j = lane; j < r.m; j += 64) r.lam[(size_t)a * r.m + j] = r.lams[(size_t)i * r.m + j];
+    if (r.stats && lane < 8) r.stats[(size_t)a * 8 + lane] = r.stats_s[(size_t)i * 8 + lane];
+}
+
+// The trigger.  e = x - xhat, the heading component (index 2 in both models) reduced to (-pi, pi] by
+// e -= 2 pi rint(e / 2 pi) (the models may wrap phi); dev2 = sum_i w_i e_i^2 in index order, every operation rounded
+// on its own (contraction off: a host loop in IEEE doubles gets the same bits); fire = held < 0 || held >= max_hold ||
+// dev2 >= thr2, written as !(dev2 < thr2) so that a non-finite dev2 fires.
+struct TrigW { double w[6]; };
+template <int NX> MPC_DEV double trigger_dev2(const double *__restrict__ x, const double *__restrict__ xhat, const TrigW &w)
+{
+#pragma clang fp contract(off)
+    const double two_pi = 6.283185307179586476925286766559;
+    double d2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < NX; i++) {
+        double e = x[i] - xhat[i];
+        if (i == 2) e = e - two_pi * rint(e / two_pi);
+        d2 = d2 + w.w[i] * (e * e);
+    }
+    return d2;
+}
+// a + b rounded once, never contracted with the operation that made a (the disturbance is added to the plant's state
+// as a host loop adds it to mpc_rollout's result)
+MPC_DEV double add_rounded(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a + b;
+}
+MPC_DEV bool trigger_fire(int held, int max_hold, double dev2, double thr2) { return held < 0 || held >= max_hold || !(dev2 < thr2); }
+
+// mpc_trigger_eval, and step 1 - 2 of mpc_closed_loop_event (U != null: a firing agent's plan is shifted in place by
+// the `held` stages it has applied, the last stage repeated into the tail -- `held` applications of plant_step_kernel's
+// one-stage shift; force != 0: every agent fires, the nominal states are not known)
+template <int NX>
+__global__ void __launch_bounds__(64) trigger_kernel(int B, int N, const double *__restrict__ x, const double *__restrict__ xhat,
+                                                     const int *__restrict__ held, const TrigW w, double thr2, int max_hold,
+                                                     int force, double *__restrict__ dev2, int *__restrict__ fire,
+                                                     double *__restrict__ U)
+{
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= B) return;
+    const double d2 = trigger_dev2<NX>(x + (size_t)a * NX, xhat + (size_t)a * NX, w);
+    const int hd = held[a];
+    const bool f = force != 0 || trigger_fire(hd, max_hold, d2, thr2);
+    if (dev2) dev2[a] = d2;
+    fire[a] = f ? 1 : 0;
+    if (U && f && hd > 0) {
+        double *Ua = U + (size_t)a * 2 * N;
+        const int k = min(hd, N - 1);
+        for (int j = 0; j < N; j++) {           // ascending: a stage is read before it is overwritten
+            const int src = min(j + k, N - 1);
+            Ua[2 * j] = Ua[2 * src]; Ua[2 * j + 1] = Ua[2 * src + 1];
+        }
+    }
+}
+
+// plant's and controller's parameters of agent a: rows plant_index[a] and index[a] of the bound table
+MPC_DEV void event_cfgs(DevCfg &cp, DevCfg &cc, const double *__restrict__ tab, const int *__restrict__ plant_index,
+                        const int *__restrict__ index, int a)
+{
+    agent_cfg(cp, tab, plant_index, a);
+    agent_cfg(cc, tab, index, a);
+}
+
+// Steps 3 - 5 of mpc_closed_loop_event for one agent per thread: an agent that fired has just been solved (held = 0,
+// xhat = x); every agent applies stage `held` of its plan -- the plant x <- f_d(x, u) on the plant's row (+ the caller's
+// disturbance), the nominal state xhat <- f_d(xhat, u) on the controller's row, both in this thread, so no predicted
+// trajectory is stored or re-rolled -- and moves on one stage.  PA: pt = (table, plant_index, index).
+template <int MODEL, bool PA = false, class... PT>
+__global__ void __launch_bounds__(64) event_step_kernel(const DevCfg c_, int B, int t, int T, double *__restrict__ x,
+                                  double *__restrict__ xhat, const double *__restrict__ U, int *__restrict__ held,
+                                  const int *__restrict__ fire, const double *__restrict__ disturbance,
+                                  double *__restrict__ traj_x, double *__restrict__ traj_u, uint8_t *__restrict__ solved,
+                                  int *__restrict__ solve_count, const double *__restrict__ stats,
+                                  int *__restrict__ fail_count, PT... pt)
+{
+    constexpr int NX = ModelDim<MODEL>::NX;
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= B) return;
+    DevCfg cp_, cc_;
+    if constexpr (PA) { cp_ = c_; cc_ = c_; event_cfgs(cp_, cc_, pt..., a); }
+    const DevCfg &cp = PA ? cp_ : c_, &cc = PA ? cc_ : c_;
+    const bool f = fire[a] != 0;
+    int hd = f ? 0 : held[a];
+    hd = max(0, min(hd, c_.N - 1));            // (a held agent has 0 <= held < max_hold <= N: the clamp guards the read)
+    double xv[NX], xh[NX];
+    for (int i = 0; i < NX; i++) xv[i] = x[(size_t)a * NX + i];
+    for (int i = 0; i < NX; i++) xh[i] = f ? xv[i] : xhat[(size_t)a * NX + i];
+    const double d = U[(size_t)a * c_.n + 2 * hd], dl = U[(size_t)a * c_.n + 2 * hd + 1];
+    {
+        StageInput<MODEL> s;
+        prep_input(cp, d, dl, s);
+        stage_forward<MODEL>(cp, s, xv);
+    }
+    if (disturbance)
+        for (int i = 0; i < NX; i++) xv[i] = add_rounded(xv[i], disturbance[((size_t)a * T + t) * NX + i]);
+    {
+        StageInput<MODEL> s;
+        prep_input(cc, d, dl, s);
+        stage_forward<MODEL>(cc, s, xh);
+    }
+    for (int i = 0; i < NX; i++) {
+        x[(size_t)a * NX + i] = xv[i];
+        xhat[(size_t)a * NX + i] = xh[i];
+        if (traj_x) traj_x[((size_t)a * T + t) * NX + i] = xv[i];
+    }
+    if (traj_u) { traj_u[((size_t)a * T + t) * 2] = d; traj_u[((size_t)a * T + t) * 2 + 1] = dl; }
+    held[a] = hd + 1;
+    if (solved) solved[(size_t)a * T + t] = f ? 1 : 0;
+    if (f) {
+        if (solve_count) solve_count[a] += 1;
+        if (fail_count) fail_count[a] += stats[(size_t)a * 8] != (double)ST_CONVERGED;
+    }
+}
+
+} // namespace mpc

@@ -6,6 +6,7 @@
 #include "mpc_aux.hpp"
 #include "mpc_solo.hpp"
 #include "mpc_game.hpp"
+#include "mpc_event.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -72,7 +73,7 @@ struct mpc_handle {
     size_t arena_bytes = 0;
     WorkspacePA ws{};
     int *host_counts = nullptr; // pinned, 512 B: [2 poll windows][MPC_MAX_GROUPS][2] ints, then (byte 128) the sixteen totals of a
-                                // solve (16 x 8 B) and (byte 256) the persistent kernel's counters -- copies into pageable memory would
+                                // solve (16 x 8 B), (byte 256) the persistent kernel's counters and (byte 384) a masked solve's count -- copies into pageable memory would
                                 // block the host until the stream has drained, whatever the wall-clock bound says
     hipEvent_t pollev[2][MPC_MAX_GROUPS] = {{nullptr}};
     hipEvent_t soloev[MPC_MAX_GROUPS][2] = {{nullptr}}; // profile mode: around a group's persistent-kernel launch
@@ -124,6 +125,17 @@ struct mpc_handle {
     // staging buffers for the standalone entry points
     double *stage = nullptr;
     size_t stage_bytes = 0;
+    // mpc_solve_active / mpc_closed_loop_event: the compaction's list and counters, the staging rows the active agents
+    // are solved on (one allocation, grown like the workspace), and the nominal states of the event-triggered loop
+    // (their own allocation: they are STATE between calls and must outlive a regrown staging arena)
+    struct EventBufs {
+        char *base = nullptr;
+        int cap = 0;                                   // agents the arena holds
+        int *list = nullptr, *blk = nullptr, *count = nullptr, *fire = nullptr, *cis = nullptr, *pis = nullptr;
+        double *xs = nullptr, *Us = nullptr, *lams = nullptr, *stats_s = nullptr, *stats_own = nullptr;
+        double *xhat = nullptr;                        // [xhat_B][nx]
+        int xhat_B = 0;
+    } ev;
 };
 
 static int stage_m(const mpc_config *c) { return c->constr_mode == MPC_CONSTR_STATE_SQ ? mpc_nx(c) : c->constr_mode == MPC_CONSTR_LANE ? 1 : 0; }
@@ -328,6 +340,44 @@ static int reserve_stage(mpc_handle *h, size_t bytes)
     hipError_t e = hipMalloc((void **)&h->stage, bytes);
     if (e != hipSuccess) return fail(MPC_E_ALLOC, "staging hipMalloc failed");
     h->stage_bytes = bytes;
+    return MPC_OK;
+}
+
+// staging of the masked solve for up to B agents (see mpc_handle::EventBufs)
+static int reserve_event(mpc_handle *h, int B)
+{
+    mpc_handle::EventBufs &e = h->ev;
+    if (B <= e.cap) return MPC_OK;
+    HIPCHK(hipSetDevice(h->device));
+    if (e.base) { HIPCHK(hipFree(e.base)); e.base = nullptr; e.cap = 0; }
+    const DevCfg &c = h->dc;
+    const size_t Bp = ((size_t)B + 63) & ~(size_t)63, m = c.m ? c.m : 1, nblk = (Bp + EV_BLK - 1) / EV_BLK;
+    const size_t nd = (size_t)c.nx + c.n + m + 8 + 8;            // doubles per agent: xs, Us, lams, stats_s, stats_own
+    const size_t bytes = nd * 8 * Bp + 4 * (4 * Bp + nblk + 64);  // ints: list, fire, cis, pis [Bp], blk [nblk], count
+    char *base = nullptr;
+    if (hipMalloc((void **)&base, bytes) != hipSuccess) return fail(MPC_E_ALLOC, "masked-solve staging hipMalloc failed");
+    e.base = base; e.cap = (int)Bp;
+    double *dp = (double *)base;
+    auto takeD = [&](size_t cnt) { double *r = dp; dp += cnt * Bp; return r; };
+    e.xs = takeD(c.nx); e.Us = takeD(c.n); e.lams = takeD(m); e.stats_s = takeD(8); e.stats_own = takeD(8);
+    int *ip = (int *)dp;
+    auto takeI = [&](size_t cnt) { int *r = ip; ip += cnt; return r; };
+    e.list = takeI(Bp); e.fire = takeI(Bp); e.cis = takeI(Bp); e.pis = takeI(Bp); e.blk = takeI(nblk); e.count = takeI(64);
+    HIPCHK(hipMemset(base, 0, bytes));
+    return MPC_OK;
+}
+// the nominal states for a batch of B agents; *fresh = they were (re)allocated: no agent's nominal state is known
+static int reserve_xhat(mpc_handle *h, int B, bool *fresh)
+{
+    mpc_handle::EventBufs &e = h->ev;
+    *fresh = false;
+    if (e.xhat && e.xhat_B == B) return MPC_OK;
+    HIPCHK(hipSetDevice(h->device));
+    if (e.xhat) { HIPCHK(hipFree(e.xhat)); e.xhat = nullptr; e.xhat_B = 0; }
+    const size_t bytes = sizeof(double) * (size_t)B * h->dc.nx;
+    if (hipMalloc((void **)&e.xhat, bytes) != hipSuccess) return fail(MPC_E_ALLOC, "nominal-state hipMalloc failed");
+    HIPCHK(hipMemset(e.xhat, 0, bytes));
+    e.xhat_B = B; *fresh = true;
     return MPC_OK;
 }
 

@@ -4,6 +4,7 @@ Holds no arithmetic of its own: it checks shapes/dtypes/devices on the host (a
 wrong shape handed to a hand-written kernel is a GPU fault) and forwards raw
 device pointers plus the current HIP stream.
 """
+import collections
 import ctypes as C
 
 import torch
@@ -13,6 +14,13 @@ from . import _lib
 
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+# what BatchedMPC.closed_loop_event returns: the final states x [B, nx], the plans U as last solved, the multipliers,
+# held [B] (stages of the plan already applied), traj_x [B, T, nx], traj_u [B, T, 2], solved [B, T] uint8,
+# solve_count [B], failures [B] and stats [B, 8] of each agent's most recent solve
+EventLoopResult = collections.namedtuple(
+    "EventLoopResult", "x U lam held traj_x traj_u solved solve_count failures stats")
 
 
 class BatchedMPC:
@@ -309,6 +317,98 @@ class BatchedMPC:
                                             _ptr(cl_index), _ptr(U), _ptr(lam), _ptr(tx), _ptr(tu),
                                             _ptr(fails), _ptr(stats), self._stream()))
         return x, U, lam, tx, tu, fails, stats
+
+    # ------------------------------------------------------------------ masked solve, event-triggered loop
+    def _weights(self, w):
+        w = [float(v) for v in (w.tolist() if hasattr(w, "tolist") else w)]
+        if len(w) != self.nx:
+            raise ValueError(f"w: expected {self.nx} weights, got {len(w)}")
+        return (C.c_double * self.nx)(*w)
+
+    def _trigger_args(self, thr, max_hold):
+        thr, max_hold = float(thr), int(max_hold)
+        if not thr >= 0.0:
+            raise ValueError("thr must be >= 0 (inf: the hold limit alone)")
+        if not 1 <= max_hold <= self.N:
+            raise ValueError(f"max_hold must be in [1, {self.N}]")
+        return thr, max_hold
+
+    def solve_active(self, x0, centerline, U, active, lam=None, cl_index=None, stats=None, inplace=False):
+        """mpc_solve_active: solves the agents with active[b] != 0 (int32 or bool [B]) exactly as solve() would and
+        leaves every other agent's rows of U, lam and stats as they are.  Returns (U, lam, stats, n_active); the
+        tensors are copies unless inplace (stats=None: zeros for the agents that are not solved)."""
+        B = x0.shape[0]
+        self._chk(x0, (B, self.nx), "x0"); self._chk(U, (B, self.n), "U")
+        if isinstance(active, torch.Tensor) and active.dtype == torch.bool:
+            active = active.to(torch.int32)
+        self._chk(active, (B,), "active", torch.int32)
+        cl = self._centerline(centerline, cl_index, B)
+        if not inplace:
+            U = U.clone()
+        if self.m:
+            lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None \
+                else (lam if inplace else lam.clone())
+            self._chk(lam, (B, self.m), "lam")
+        else:
+            lam = None
+        if stats is None:
+            stats = torch.zeros(B, _lib.NSTATS, dtype=torch.float64, device=self.device)
+        elif not inplace:
+            stats = stats.clone()
+        self._chk(stats, (B, _lib.NSTATS), "stats")
+        n = C.c_int32(0)
+        _lib.check(self.lib.mpc_solve_active(self._h, B, _ptr(active), _ptr(x0), _ptr(cl), _ptr(cl_index), _ptr(U),
+                                             _ptr(lam), _ptr(stats), C.byref(n), self._stream()))
+        return U, lam, stats, int(n.value)
+
+    def trigger_eval(self, x, xhat, held, w, thr, max_hold):
+        """mpc_trigger_eval: (dev2 [B], fire [B] int32) with e = x - xhat (heading reduced by whole turns),
+        dev2 = sum_i w_i e_i^2, fire = held < 0 or held >= max_hold or dev2 >= thr^2.  w: nx host floats."""
+        self._free()
+        B = x.shape[0]
+        self._chk(x, (B, self.nx), "x"); self._chk(xhat, (B, self.nx), "xhat")
+        self._chk(held, (B,), "held", torch.int32)
+        thr, max_hold = self._trigger_args(thr, max_hold)
+        dev2 = self._empty(B)
+        fire = self._empty(B, dtype=torch.int32)
+        _lib.check(self.lib.mpc_trigger_eval(self._h, B, _ptr(x), _ptr(xhat), _ptr(held), self._weights(w), thr, max_hold,
+                                             _ptr(dev2), _ptr(fire), self._stream()))
+        return dev2, fire
+
+    def closed_loop_event(self, x, centerline, U, T, w, thr, max_hold, held=None, lam=None, cl_index=None,
+                          shift=False, disturbance=None, stats=None):
+        """mpc_closed_loop_event for B agents: T steps in which an agent is solved again only when its state has left
+        the plan's own prediction by thr (weights w, heading by whole turns) or max_hold stages of the plan have been
+        applied.  held [B] int32 (None: -1, no plan yet) and the returned U / held / lam / stats continue a loop
+        on this engine: pass them to the next call.  disturbance [B, T, nx] is added to the plant's state at every
+        step.  Returns an EventLoopResult (copies; the arguments are not written)."""
+        B, T = x.shape[0], int(T)
+        self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
+        thr, max_hold = self._trigger_args(thr, max_hold)
+        if T < 0:
+            raise ValueError("T must be >= 0")
+        cl = self._centerline(centerline, cl_index, B)
+        x, U = x.clone(), U.clone()
+        held = torch.full((B,), -1, dtype=torch.int32, device=self.device) if held is None else held.clone()
+        self._chk(held, (B,), "held", torch.int32)
+        if self.m:
+            lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None else lam.clone()
+            self._chk(lam, (B, self.m), "lam")
+        else:
+            lam = None
+        if disturbance is not None:
+            self._chk(disturbance, (B, T, self.nx), "disturbance")
+        stats = torch.zeros(B, _lib.NSTATS, dtype=torch.float64, device=self.device) if stats is None else stats.clone()
+        self._chk(stats, (B, _lib.NSTATS), "stats")
+        tx, tu = self._empty(B, T, self.nx), self._empty(B, T, 2)
+        solved = torch.zeros(B, T, dtype=torch.uint8, device=self.device)
+        count = torch.zeros(B, dtype=torch.int32, device=self.device)
+        fails = torch.zeros(B, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.mpc_closed_loop_event(
+            self._h, B, T, int(bool(shift)), self._weights(w), thr, max_hold, _ptr(x), _ptr(cl), _ptr(cl_index), _ptr(U),
+            _ptr(lam), _ptr(held), _ptr(disturbance), _ptr(tx), _ptr(tu), _ptr(solved), _ptr(count), _ptr(fails),
+            _ptr(stats), self._stream()))
+        return EventLoopResult(x, U, lam, held, tx, tu, solved, count, fails, stats)
 
     def lane_payoff(self, ego, cars, ncars, params):
         """f-3: out[B, 2, 4] = target lane 1, 2 -> [total, safety, velocity, comfort] (game_theory.py:115-244)."""
