@@ -119,6 +119,26 @@ int mpc_default_params(const mpc_config *cfg, double *row);
 int mpc_set_agent_params(mpc_handle *h, const double *table, int P, const int32_t *index,
                          const int32_t *plant_index, int B);
 
+/* Per-agent input bounds: a table of P boxes in device memory and one row index per agent, beside the parameter table.
+ * One row, all doubles: [u_lb[0], u_lb[1], u_ub[0], u_ub[1]] = [d_min, delta_min, d_max, delta_max] -- in the reference
+ * the box C is run-time data of the problem (main.py:55-56 `prob.C.lowerbound / upperbound`), not part of its
+ * construction.
+ * mpc_default_bounds (host only): the row `cfg` describes.
+ * mpc_set_agent_bounds: table == NULL unbinds (the handle is then what it was before).  Bound, the calls that project
+ * onto the box -- mpc_prox_step, mpc_solve_batch(_async), mpc_solve_active, mpc_closed_loop(_event) -- use row index[b]
+ * for agent b and return MPC_E_ARG for a batch size other than B; no other entry point reads the box (clip_inputs
+ * clips to veh's max_drive / max_steer, which the parameter row carries).  Ts, N, the constraint data and every solver
+ * parameter stay the handle's.  The table is independent of the parameter table: either, both or neither may be bound;
+ * bound together they are for the same B (MPC_E_ARG otherwise), each with its own index.  table [P][MPC_NBOUND] and
+ * index [B] are DEVICE memory of the caller, read at every call: rows may be rewritten in place between calls without
+ * binding again.  The P rows are checked once, at bind time, through a synchronous copy, by the rule mpc_create applies
+ * to the handle's box: u_lb[i] <= u_ub[i] (a NaN fails it, infinities pass); index ranges are the caller's to check
+ * (the Python front end does).  Refused (MPC_E_ARG) while an asynchronous solve is in flight.  A table whose rows equal
+ * the handle's box gives the bits of the solve without a table. */
+#define MPC_NBOUND 4
+int mpc_default_bounds(const mpc_config *cfg, double *row);
+int mpc_set_agent_bounds(mpc_handle *h, const double *table, int P, const int32_t *index, int B);
+
 /* a-1 (car_dynamics.py:93-132 / dynamics.py:67-119,:144-173): dx[B][nx] = f(x[B][nx], u[B][2]) */
 int mpc_rhs(mpc_handle *h, int B, const double *x, const double *u, double *dx, void *stream);
 

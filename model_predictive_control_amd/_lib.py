@@ -31,7 +31,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPC_LIB_PATH", os.path.join(_HERE, "libmpc_hip.so"))  # override: dev experiments
 _SRC = [os.path.join(_HERE, "csrc", f) for f in ("mpc_api.hip", "mpc_handle.hpp", "mpc_launch.hpp", "mpc_rounds.hpp",
                                                   "mpc_aux.hpp", "mpc_eval.hpp", "mpc_solver.hpp", "mpc_device.hpp",
-                                                  "mpc_game.hpp", "mpc_solo.hpp", "mpc_event.hpp")]
+                                                  "mpc_game.hpp", "mpc_solo.hpp", "mpc_event.hpp", "mpc_step_body.hpp")]
 _HDR = os.path.join(os.path.dirname(_HERE), "include", "mpc_hip.h")
 
 MODEL_KINEMATIC, MODEL_PACEJKA = 0, 1
@@ -51,10 +51,12 @@ EXPORTS = [
     "mpc_set_poll_timeout", "mpc_debug_spin", "mpc_debug_records", "mpc_debug_record_names", "mpc_source_hash",
     "mpc_last_lookahead", "mpc_step_lds_plan", "mpc_default_params", "mpc_set_agent_params",
     "mpc_solve_active", "mpc_trigger_eval", "mpc_closed_loop_event",
+    "mpc_default_bounds", "mpc_set_agent_bounds",
 ]
 NREC = 64
 NPARAM = 31     # MPC_NPARAM: doubles per row of the per-agent parameter table
 # columns of a row, by field name (include/mpc_hip.h: mpc_set_agent_params)
+NBOUND = 4      # MPC_NBOUND: doubles per row of the per-agent bounds table, [u_lb[0], u_lb[1], u_ub[0], u_ub[1]]
 PARAM_FIELDS = {"veh": (0, 22), "accel": (22, 1), "friction": (23, 1), "v_ref": (24, 1), "cost_w": (25, 6)}
 
 
@@ -151,6 +153,8 @@ def load():
     L.mpc_last_lookahead.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.mpc_default_params.argtypes = [cp, C.POINTER(C.c_double)]
     L.mpc_set_agent_params.argtypes = [vp, vp, ci, vp, vp, ci]
+    L.mpc_default_bounds.argtypes = [cp, C.POINTER(C.c_double)]
+    L.mpc_set_agent_bounds.argtypes = [vp, vp, ci, vp, ci]
     L.mpc_step_lds_plan.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     L.mpc_math_probe.argtypes = [vp, ci, ci, vp, vp, vp, vp]
     L.mpc_lane_payoff.argtypes = [vp, ci, ci, C.POINTER(C.c_double), vp, vp, vp, vp, vp]
@@ -229,6 +233,37 @@ def param_rows(cfg, P, **overrides):
             if v.shape != (P, width):
                 raise ValueError(f"param_rows: {name} must have shape ({width},) or ({P}, {width}), got {v.shape}")
             tab[:, off:off + width] = v
+    return tab
+
+
+def default_bounds(cfg):
+    """mpc_default_bounds: the row of the per-agent bounds table that `cfg` describes, float64 [NBOUND]."""
+    import numpy as np
+    row = (C.c_double * NBOUND)()
+    rc = load().mpc_default_bounds(C.byref(cfg), row)
+    if rc != 0:
+        raise ValueError(load().mpc_last_error().decode())
+    return np.array(row[:], dtype=np.float64)
+
+
+def bound_rows(cfg, P, u_lb=None, u_ub=None):
+    """A bounds table for BatchedMPC.set_agent_bounds, on the host: float64 [P, NBOUND] whose rows are
+    default_bounds(cfg) with `u_lb` / `u_ub` [P, 2] (or [2]: every row) in their place.  Pure host code: usable
+    without a GPU."""
+    import numpy as np
+    P = int(P)
+    if P < 1:
+        raise ValueError("bound_rows: P must be >= 1")
+    tab = np.tile(default_bounds(cfg), (P, 1))
+    for name, val, off in (("u_lb", u_lb, 0), ("u_ub", u_ub, 2)):
+        if val is None:
+            continue
+        v = np.asarray(val, dtype=np.float64)
+        if v.shape == (2,):
+            v = np.tile(v, (P, 1))
+        if v.shape != (P, 2):
+            raise ValueError(f"bound_rows: {name} must have shape (2,) or ({P}, 2), got {v.shape}")
+        tab[:, off:off + 2] = v
     return tab
 
 

@@ -102,10 +102,13 @@ class MPCController:
         return self.U                                          # controller.py:69
 
     # ------------------------------------------------------------------ batched entry points
-    def solve(self, Y0, centerline, U0=None, lam0=None, cl_index=None, params=None, param_index=None):
+    def solve(self, Y0, centerline, U0=None, lam0=None, cl_index=None, params=None, param_index=None,
+              bounds=None, bound_index=None):
         """Batched solve: Y0 [B, nx], centerline [2S] or [C, 2S] (+ cl_index[B]) -> (U [B, 2N], stats).
         params [P, 31] (rows as _lib.param_rows makes them) + param_index [B] (None: agent b uses row b % P): this
-        solve runs agent b on its own vehicle and cost parameters (BatchedMPC.set_agent_params)."""
+        solve runs agent b on its own vehicle and cost parameters (BatchedMPC.set_agent_params).
+        bounds [P', 4] (rows as _lib.bound_rows makes them) + bound_index [B] (None: agent b uses row b % P'): this solve
+        projects agent b's inputs onto its own box (BatchedMPC.set_agent_bounds)."""
         dev = self.device
         Y0 = torch.as_tensor(Y0, dtype=torch.float64, device=dev).contiguous()
         B = Y0.shape[0]
@@ -125,20 +128,33 @@ class MPCController:
             if param_index is None:
                 param_index = torch.arange(B, device=dev) % params.shape[0]
             param_index = torch.as_tensor(param_index, device=dev).to(torch.int32).contiguous()
-            self.solver.set_agent_params(params, param_index)
+        if bounds is None and bound_index is not None:
+            raise ValueError("bound_index needs bounds")
+        if bounds is not None:
+            bounds = torch.as_tensor(bounds, dtype=torch.float64, device=dev).contiguous()
+            if bound_index is None:
+                bound_index = torch.arange(B, device=dev) % bounds.shape[0]
+            bound_index = torch.as_tensor(bound_index, device=dev).to(torch.int32).contiguous()
         try:
+            if params is not None:
+                self.solver.set_agent_params(params, param_index)
+            if bounds is not None:
+                self.solver.set_agent_bounds(bounds, bound_index)
             U, lam, stats = self.solver.solve(Y0, cl, U0, lam0 if self._constrained else None, cl_index)
         finally:
             if params is not None:
                 self.solver.clear_agent_params()
+            if bounds is not None:
+                self.solver.clear_agent_bounds()
         self.last_stats = stats
         self.tot_it += int(stats[:, 2].sum().item())
         self.failures += int((stats[:, 0] != _lib.ST_CONVERGED).sum().item())
         return U, stats
 
-    def step(self, Y0, centerline, U0=None, lam0=None, cl_index=None, params=None, param_index=None):
+    def step(self, Y0, centerline, U0=None, lam0=None, cl_index=None, params=None, param_index=None,
+             bounds=None, bound_index=None):
         """First control of every agent, u0 [B, 2] (main.py:141 input_to_matrix(U)[:, 0])."""
-        U, _ = self.solve(Y0, centerline, U0, lam0, cl_index, params, param_index)
+        U, _ = self.solve(Y0, centerline, U0, lam0, cl_index, params, param_index, bounds, bound_index)
         return U[:, :2].contiguous()
 
 

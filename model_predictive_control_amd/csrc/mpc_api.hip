@@ -62,6 +62,14 @@ extern "C" int mpc_default_params(const mpc_config *c, double *row)
     return MPC_OK;
 }
 
+static_assert(MPC_NBOUND == mpc::NBOUND, "row layout: include/mpc_hip.h and mpc_device.hpp");
+extern "C" int mpc_default_bounds(const mpc_config *c, double *row)
+{
+    if (!c || !row) return fail(MPC_E_ARG, "mpc_default_bounds: null argument");
+    row[0] = c->u_lb[0]; row[1] = c->u_lb[1]; row[2] = c->u_ub[0]; row[3] = c->u_ub[1];
+    return MPC_OK;
+}
+
 extern "C" int mpc_create(const mpc_config *cfg, int device, mpc_handle **out)
 {
     if (!cfg || !out) return fail(MPC_E_ARG, "mpc_create: null argument");
@@ -111,6 +119,7 @@ extern "C" int mpc_destroy(mpc_handle *h)
     if (h->stage) (void)hipFree(h->stage);
     if (h->ev.base) (void)hipFree(h->ev.base);
     if (h->ev.xhat) (void)hipFree(h->ev.xhat);
+    if (h->own_ptab) (void)hipFree(h->own_ptab);
     if (h->cl_gmeta) (void)hipFree(h->cl_gmeta);
     if (h->cl_gxy) (void)hipFree(h->cl_gxy);
     if (h->cl_gcells) (void)hipFree(h->cl_gcells);
@@ -161,6 +170,8 @@ extern "C" int mpc_set_agent_params(mpc_handle *h, const double *table, int P, c
     { const int rb = refuse_if_busy(h, "mpc_set_agent_params"); if (rb) return rb; }
     if (!table) { h->ptab = nullptr; h->pidx = h->pidx_plant = nullptr; h->ptab_rows = h->ptab_B = 0; return MPC_OK; }
     if (P < 1 || B < 1 || !index) return fail(MPC_E_ARG, "mpc_set_agent_params: need P >= 1 rows, B >= 1 agents and an index");
+    if (h->btab && B != h->btab_B)
+        return fail(MPC_E_ARG, "mpc_set_agent_params: the bound bounds table is for a batch of " + std::to_string(h->btab_B) + " agents");
     HIPCHK(hipSetDevice(h->device));
     std::vector<double> rows((size_t)P * MPC_NPARAM);
     HIPCHK(hipMemcpy(rows.data(), table, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -175,6 +186,39 @@ extern "C" int mpc_set_agent_params(mpc_handle *h, const double *table, int P, c
             return fail(MPC_E_ARG, "mpc_set_agent_params: row " + std::to_string(p) + ": mass and inertia (veh[7], veh[8]) must be positive");
     }
     h->ptab = table; h->ptab_rows = P; h->pidx = index; h->pidx_plant = plant_index; h->ptab_B = B;
+    return MPC_OK;
+}
+
+// Binds (table != NULL) or unbinds the per-agent table of input boxes, as mpc_set_agent_params binds the parameter
+// table: the rows are checked once, here, through a synchronous copy, by the rule mpc_create applies to the handle's
+// box; the kernels read the caller's memory at every call.
+extern "C" int mpc_set_agent_bounds(mpc_handle *h, const double *table, int P, const int32_t *index, int B)
+{
+    { const int rb = refuse_if_busy(h, "mpc_set_agent_bounds"); if (rb) return rb; }
+    if (!table) { h->btab = nullptr; h->bidx = nullptr; h->btab_rows = h->btab_B = 0; return MPC_OK; }
+    if (P < 1 || B < 1 || !index) return fail(MPC_E_ARG, "mpc_set_agent_bounds: need P >= 1 rows, B >= 1 agents and an index");
+    if (h->ptab && B != h->ptab_B)
+        return fail(MPC_E_ARG, "mpc_set_agent_bounds: the bound parameter table is for a batch of " + std::to_string(h->ptab_B) + " agents");
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<double> rows((size_t)P * MPC_NBOUND);
+    HIPCHK(hipMemcpy(rows.data(), table, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int p = 0; p < P; p++)
+        if (!box_ok(rows.data() + (size_t)p * MPC_NBOUND, rows.data() + (size_t)p * MPC_NBOUND + 2))
+            return fail(MPC_E_ARG, "mpc_set_agent_bounds: row " + std::to_string(p) + ": u_lb must not exceed u_ub");
+    // the handle's own one-row parameter table and an index of B zeros (see mpc_handle::own_ptab)
+    if (B > h->own_cap) {
+        if (h->own_ptab) { HIPCHK(hipFree(h->own_ptab)); h->own_ptab = nullptr; h->own_pidx = nullptr; h->own_cap = 0; }
+        const size_t cap = ((size_t)B + 63) & ~(size_t)63;
+        char *base = nullptr;
+        if (hipMalloc((void **)&base, sizeof(double) * MPC_NPARAM + 8 + sizeof(int32_t) * cap) != hipSuccess)
+            return fail(MPC_E_ALLOC, "mpc_set_agent_bounds: hipMalloc failed");
+        double own[MPC_NPARAM + 1] = {0};
+        (void)mpc_default_params(&h->cfg, own);
+        h->own_ptab = (double *)base; h->own_pidx = (int32_t *)(base + sizeof(double) * (MPC_NPARAM + 1)); h->own_cap = (int)cap;
+        HIPCHK(hipMemcpy(base, own, sizeof own, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(h->own_pidx, 0, sizeof(int32_t) * cap));
+    }
+    h->btab = table; h->btab_rows = P; h->bidx = index; h->btab_B = B;
     return MPC_OK;
 }
 
@@ -274,7 +318,7 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     rc = reserve(h, B); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     // direct mode: the kernel reads and writes the caller's agent-major buffers in place
-    WorkspacePA w = h->ws;
+    WorkspaceHost w = h->ws;
     w.cl = cl; w.cl_index = cl_index; w.x0 = x0; w.near = near_for(h, cl);
     w.xe = const_cast<double *>(U); w.ge = grad ? grad : h->ws.ws_ge;
     w.y = const_cast<double *>(y); w.Sig = c.m ? const_cast<double *>(Sigma) : h->ws.ws_Sig;
@@ -303,7 +347,12 @@ extern "C" int mpc_prox_step(mpc_handle *h, int B, const double *x, const double
     int rc = check_common(h, B, "mpc_prox_step"); if (rc) return rc;
     if (B == 0) return MPC_OK;
     if (!x || !grad || !gamma || !out) return fail(MPC_E_ARG, "mpc_prox_step: null buffer");
-    hipLaunchKernelGGL(prox_kernel, grid_for(B, 64), dim3(64), 0, (hipStream_t)stream, h->dc, B, x, grad, gamma, xhat, p, out);
+    rc = check_box_bound(h, B, "mpc_prox_step"); if (rc) return rc;
+    if (h->btab)
+        hipLaunchKernelGGL(prox_box_kernel, grid_for(B, 64), dim3(64), 0, (hipStream_t)stream, h->dc, B, x, grad, gamma, xhat, p, out,
+                           BoxTab{h->btab, h->bidx});
+    else
+        hipLaunchKernelGGL(prox_kernel, grid_for(B, 64), dim3(64), 0, (hipStream_t)stream, h->dc, B, x, grad, gamma, xhat, p, out);
     HIPCHK(hipGetLastError());
     return MPC_OK;
 }
@@ -336,16 +385,18 @@ extern "C" int mpc_step_lds_plan(int n, int M, int m, int chain, int lds_pairs, 
     return MPC_OK;
 }
 
-// the solve proper on B agents whose parameter rows (table bound) are pidx[b]: the caller's batch and the handle's
-// bound index (mpc_solve_batch), or the gathered rows of a masked solve and their gathered indices
+// the solve proper on B agents whose parameter rows (table bound) are pidx[b] and whose boxes (bounds table bound) are
+// rows bidx[b]: the caller's batch and the handle's bound indices (mpc_solve_batch), or the gathered rows of a masked
+// solve and their gathered indices
 static int solve_core(mpc_handle *h, int B, const double *x0, const double *cl, const int32_t *cl_index, const int32_t *pidx,
-                      double *U, double *lambda, double *stats, hipStream_t s)
+                      const int32_t *bidx, double *U, double *lambda, double *stats, hipStream_t s)
 {
     int rc = reserve(h, B); if (rc) return rc;
-    WorkspacePA &w = h->ws;
+    WorkspaceHost &w = h->ws;
     w.cl = cl; w.cl_index = cl_index; w.x0 = x0; w.xo = U; w.y = lambda; w.psi_direct = nullptr;
     w.near = near_for(h, cl);
     w.ptab = h->ptab; w.pidx = pidx;
+    w.btab = h->btab; w.bidx = h->btab ? bidx : nullptr;
     w.xe = w.ws_xe; w.ge = w.ws_ge; w.yhe = w.ws_yhe; w.Sig = w.ws_Sig;
     rc = run_solver(h, s); if (rc) return rc;
     if (stats) hipLaunchKernelGGL(stats_kernel, grid_for(B, 256), dim3(256), 0, s, w, stats);
@@ -360,7 +411,8 @@ static int solve_batch_impl(mpc_handle *h, int B, const double *x0, const double
     if (!x0 || !cl || !U) return fail(MPC_E_ARG, "mpc_solve_batch: null buffer");
     if (h->dc.m && !lambda) return fail(MPC_E_ARG, "mpc_solve_batch: lambda is required when m > 0");
     rc = check_bound(h, B, "mpc_solve_batch"); if (rc) return rc;
-    return solve_core(h, B, x0, cl, cl_index, h->pidx, U, lambda, stats, (hipStream_t)stream);
+    rc = check_box_bound(h, B, "mpc_solve_batch"); if (rc) return rc;
+    return solve_core(h, B, x0, cl, cl_index, h->pidx, h->bidx, U, lambda, stats, (hipStream_t)stream);
 }
 extern "C" int mpc_solve_batch(mpc_handle *h, int B, const double *x0, const double *cl, const int32_t *cl_index, double *U,
                                double *lambda, double *stats, void *stream)
@@ -427,6 +479,7 @@ extern "C" int mpc_closed_loop(mpc_handle *h, int B, int T, int shift, double *x
     const DevCfg &c = h->dc;
     if (c.m && !lambda) return fail(MPC_E_ARG, "mpc_closed_loop: lambda is required when m > 0");
     rc = check_bound(h, B, "mpc_closed_loop"); if (rc) return rc;
+    rc = check_box_bound(h, B, "mpc_closed_loop"); if (rc) return rc;
     // bound table: the controller solves with row pidx[b], the plant advances with row pidx_plant[b] (null: the same)
     hipStream_t s = (hipStream_t)stream;
     double *st = stats;
@@ -466,6 +519,7 @@ static int solve_active_impl(mpc_handle *h, int B, const int32_t *active, const 
     r.cl_index = cl_index; r.pidx = h->ptab ? h->pidx : nullptr;
     r.xs = e.xs; r.Us = e.Us; r.lams = e.lams; r.stats_s = e.stats_s; r.cis = e.cis; r.pis = e.pis;
     hipLaunchKernelGGL(active_gather_kernel, grows, dim3(EV_BLK), 0, s, r);
+    if (h->btab) hipLaunchKernelGGL(active_index_kernel, gblk, dim3(EV_BLK), 0, s, e.list, e.count, h->bidx, e.bis);
     int *cnt = (int *)((char *)h->host_counts + 384);   // pinned (see host_counts)
     HIPCHK(hipMemcpyAsync(cnt, e.count, sizeof(int), hipMemcpyDeviceToHost, s));
     rc = bounded_sync(h, s, "mpc_solve_active"); if (rc) return rc;
@@ -473,7 +527,7 @@ static int solve_active_impl(mpc_handle *h, int B, const int32_t *active, const 
     if (nA < 0 || nA > B) return fail(MPC_E_HIP, "mpc_solve_active: the compaction counted " + std::to_string(nA) + " of " + std::to_string(B) + " agents");
     if (n_active) *n_active = nA;
     if (nA == 0) return MPC_OK;
-    rc = solve_core(h, nA, e.xs, cl, cl_index ? e.cis : nullptr, r.pidx ? e.pis : nullptr, e.Us, c.m ? e.lams : nullptr,
+    rc = solve_core(h, nA, e.xs, cl, cl_index ? e.cis : nullptr, r.pidx ? e.pis : nullptr, h->btab ? e.bis : nullptr, e.Us, c.m ? e.lams : nullptr,
                     stats ? e.stats_s : nullptr, s);
     if (rc) return rc;
     hipLaunchKernelGGL(active_scatter_kernel, grid_for(nA, EV_BLK / 64), dim3(EV_BLK), 0, s, r);
@@ -491,6 +545,7 @@ extern "C" int mpc_solve_active(mpc_handle *h, int B, const int32_t *active, con
     if (!active || !x0 || !cl || !U) return fail(MPC_E_ARG, "mpc_solve_active: null buffer");
     if (h->dc.m && !lambda) return fail(MPC_E_ARG, "mpc_solve_active: lambda is required when m > 0");
     rc = check_bound(h, B, "mpc_solve_active"); if (rc) return rc;   // the caller's B; the compact batch is the library's
+    rc = check_box_bound(h, B, "mpc_solve_active"); if (rc) return rc;
     return solve_active_impl(h, B, active, x0, cl, cl_index, U, lambda, stats, n_active, (hipStream_t)stream, true);
 }
 
@@ -556,6 +611,7 @@ extern "C" int mpc_closed_loop_event(mpc_handle *h, int B, int T, int shift, con
     const DevCfg &c = h->dc;
     if (c.m && !lambda) return fail(MPC_E_ARG, "mpc_closed_loop_event: lambda is required when m > 0");
     rc = check_bound(h, B, "mpc_closed_loop_event"); if (rc) return rc;
+    rc = check_box_bound(h, B, "mpc_closed_loop_event"); if (rc) return rc;
     rc = reserve_event(h, B); if (rc) return rc;
     bool fresh = false;
     rc = reserve_xhat(h, B, &fresh); if (rc) return rc;

@@ -174,7 +174,29 @@ __global__ void prox_kernel(const DevCfg c, int B, const double *__restrict__ x,
     const double gm = gamma[a];
     for (int j = 0; j < c.n; j++) {
         const double xv = x[(size_t)a * c.n + j], gv = g[(size_t)a * c.n + j];
-        const double pv = prox_p(c, j & 1, xv, gv, gm);
+        const double pv = prox_p(c, CfgBox(), j & 1, xv, gv, gm);
+        if (xhat) xhat[(size_t)a * c.n + j] = xv + pv;
+        if (p) p[(size_t)a * c.n + j] = pv;
+        pp += pv * pv; gp += gv * pv;
+    }
+    out[2 * (size_t)a] = pp; out[2 * (size_t)a + 1] = gp;
+}
+// ... onto every agent's own box, row bt.bidx[a] of the bounds table (mpc_set_agent_bounds)
+__global__ void prox_box_kernel(const DevCfg c, int B, const double *__restrict__ x,
+                                const double *__restrict__ g, const double *__restrict__ gamma,
+                                double *__restrict__ xhat, double *__restrict__ p,
+                                double *__restrict__ out, const BoxTab bt)
+{
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= B) return;
+    const double *__restrict__ row = bt.btab + (size_t)bt.bidx[a] * NBOUND;
+    AgentBox bx;
+    bx.lb[0] = row[0]; bx.lb[1] = row[1]; bx.ub[0] = row[2]; bx.ub[1] = row[3];
+    double pp = 0.0, gp = 0.0;
+    const double gm = gamma[a];
+    for (int j = 0; j < c.n; j++) {
+        const double xv = x[(size_t)a * c.n + j], gv = g[(size_t)a * c.n + j];
+        const double pv = prox_p(c, bx, j & 1, xv, gv, gm);
         if (xhat) xhat[(size_t)a * c.n + j] = xv + pv;
         if (p) p[(size_t)a * c.n + j] = pv;
         pp += pv * pv; gp += gv * pv;

@@ -86,6 +86,12 @@ MPC_DEV void agent_cfg_uniform(DevCfg &c, const double *__restrict__ tab, const 
     agent_cfg_from(c, [=](int f) { return r[f]; });
 }
 
+// mpc_set_agent_bounds: a table [P][NBOUND] of input boxes in device memory and one row index per agent.  A row is
+// [u_lb[0], u_lb[1], u_ub[0], u_ub[1]] and replaces exactly DevCfg::u_lb / u_ub, which nothing but the projection of
+// the solver's state machine reads (prox_p / in_J: mpc_solver.hpp).  The values are used as they are -- no
+// arithmetic on the way -- so a row equal to the handle's box gives the shared path's bits.
+constexpr int NBOUND = 4;
+
 // ---------------------------------------------------------------------------------- math
 // The OCML double-precision transcendentals are full-range (Payne-Hanek reduction, dozens of
 // 64-bit literals each) and dominate this kernel's instruction count.  The angles of this problem

@@ -35,6 +35,15 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
             return fail(MPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
     } while (0)
 
+// The workspace as the host keeps it: the kernels' Workspace, the parameter table the per-agent kernels get with it
+// (WorkspacePA), and the bounds table of mpc_set_agent_bounds (both null: none bound), which reaches the per-agent-box
+// kernels as an argument of its own (BoxTab) and no other kernel at all.
+struct WorkspaceHost : WorkspacePA {
+    const double *btab;                            // [P][MPC_NBOUND] caller's table
+    const int *bidx;                               // [B]             caller's row index per agent
+    BoxTab box() const { return BoxTab{btab, bidx}; }
+};
+
 struct mpc_handle {
     mpc_config cfg;
     DevCfg dc;
@@ -71,7 +80,7 @@ struct mpc_handle {
     int Bp_alloc = 0;      // workspace capacity (agents)
     char *arena = nullptr; // one device allocation carved into the WorkspacePA arrays
     size_t arena_bytes = 0;
-    WorkspacePA ws{};
+    WorkspaceHost ws{};
     int *host_counts = nullptr; // pinned, 512 B: [2 poll windows][MPC_MAX_GROUPS][2] ints, then (byte 128) the sixteen totals of a
                                 // solve (16 x 8 B), (byte 256) the persistent kernel's counters and (byte 384) a masked solve's count -- copies into pageable memory would
                                 // block the host until the stream has drained, whatever the wall-clock bound says
@@ -122,6 +131,17 @@ struct mpc_handle {
     const int32_t *pidx = nullptr;         // [ptab_B] the controller's row per agent
     const int32_t *pidx_plant = nullptr;   // [ptab_B] the plant's row per agent (mpc_closed_loop), null: pidx
     int ptab_rows = 0, ptab_B = 0;
+    // mpc_set_agent_bounds: the caller's table of input boxes and row indices (device memory, read at every call; both
+    // null: none bound, every agent projects onto the handle's box through the kernels that have always run)
+    const double *btab = nullptr;          // [btab_rows][MPC_NBOUND]
+    const int32_t *bidx = nullptr;         // [btab_B]
+    int btab_rows = 0, btab_B = 0;
+    // The persistent kernel has its box form together with the parameter form alone.  With a bounds table but no
+    // parameter table it runs on this one-row parameter table of the handle's own values (bit for bit the shared
+    // path: tests/test_gpu_agent_params.py) and an index of zeros; made at the first such bind, one allocation.
+    double *own_ptab = nullptr;            // [MPC_NPARAM], then the zeros
+    int32_t *own_pidx = nullptr;           // [own_cap] zeros
+    int own_cap = 0;
     // staging buffers for the standalone entry points
     double *stage = nullptr;
     size_t stage_bytes = 0;
@@ -131,7 +151,7 @@ struct mpc_handle {
     struct EventBufs {
         char *base = nullptr;
         int cap = 0;                                   // agents the arena holds
-        int *list = nullptr, *blk = nullptr, *count = nullptr, *fire = nullptr, *cis = nullptr, *pis = nullptr;
+        int *list = nullptr, *blk = nullptr, *count = nullptr, *fire = nullptr, *cis = nullptr, *pis = nullptr, *bis = nullptr;
         double *xs = nullptr, *Us = nullptr, *lams = nullptr, *stats_s = nullptr, *stats_own = nullptr;
         double *xhat = nullptr;                        // [xhat_B][nx]
         int xhat_B = 0;
@@ -139,6 +159,14 @@ struct mpc_handle {
 };
 
 static int stage_m(const mpc_config *c) { return c->constr_mode == MPC_CONSTR_STATE_SQ ? mpc_nx(c) : c->constr_mode == MPC_CONSTR_LANE ? 1 : 0; }
+
+// the input box rule of mpc_create and mpc_set_agent_bounds: u_lb[i] <= u_ub[i] (a NaN fails it, infinities pass)
+static bool box_ok(const double *lb, const double *ub)
+{
+    for (int i = 0; i < 2; i++)
+        if (!(lb[i] <= ub[i])) return false;
+    return true;
+}
 
 static int make_devcfg(const mpc_config &c, DevCfg &d)
 {
@@ -162,8 +190,7 @@ static int make_devcfg(const mpc_config &c, DevCfg &d)
         return fail(MPC_E_ARG, "tolerances alm_eps, alm_delta, eps0 must be positive");
     if (!(c.tau_min > 0.0) || !(c.tau_min <= 1.0)) return fail(MPC_E_ARG, "tau_min must be in (0, 1]");
     if (!(c.Lgamma_factor > 0.0) || !(c.Lgamma_factor < 1.0)) return fail(MPC_E_ARG, "Lgamma_factor must be in (0, 1)");
-    for (int i = 0; i < 2; i++)
-        if (!(c.u_lb[i] <= c.u_ub[i])) return fail(MPC_E_ARG, "input box: u_lb must not exceed u_ub");
+    if (!box_ok(c.u_lb, c.u_ub)) return fail(MPC_E_ARG, "input box: u_lb must not exceed u_ub");
     std::memset(&d, 0, sizeof d);
     d.model = c.model; d.N = c.N; d.S = c.S; d.nfe = c.nfe; d.wrap_mode = c.wrap_mode;
     d.clip_inputs = c.clip_inputs; d.constr_mode = c.constr_mode; d.sm = stage_m(&c);
@@ -309,7 +336,7 @@ static int reserve(mpc_handle *h, int B)
     hipError_t e = hipMalloc((void **)&base, bytes);
     if (e != hipSuccess) return fail(MPC_E_ALLOC, "workspace hipMalloc failed: " + std::string(hipGetErrorString(e)));
     h->arena = base; h->arena_bytes = bytes; h->Bp_alloc = Bp;
-    WorkspacePA &w = h->ws;
+    WorkspaceHost &w = h->ws;
     double *dp = (double *)base;
     auto takeD = [&](size_t cnt) { double *r = dp; dp += cnt * (size_t)Bp; return r; };
     w.xk = takeD(n); w.gk = takeD(n); w.q = takeD(n); w.xn = takeD(n); w.xe = takeD(n); w.ge = takeD(n);
@@ -353,7 +380,7 @@ static int reserve_event(mpc_handle *h, int B)
     const DevCfg &c = h->dc;
     const size_t Bp = ((size_t)B + 63) & ~(size_t)63, m = c.m ? c.m : 1, nblk = (Bp + EV_BLK - 1) / EV_BLK;
     const size_t nd = (size_t)c.nx + c.n + m + 8 + 8;            // doubles per agent: xs, Us, lams, stats_s, stats_own
-    const size_t bytes = nd * 8 * Bp + 4 * (4 * Bp + nblk + 64);  // ints: list, fire, cis, pis [Bp], blk [nblk], count
+    const size_t bytes = nd * 8 * Bp + 4 * (5 * Bp + nblk + 64);  // ints: list, fire, cis, pis, bis [Bp], blk [nblk], count
     char *base = nullptr;
     if (hipMalloc((void **)&base, bytes) != hipSuccess) return fail(MPC_E_ALLOC, "masked-solve staging hipMalloc failed");
     e.base = base; e.cap = (int)Bp;
@@ -362,7 +389,7 @@ static int reserve_event(mpc_handle *h, int B)
     e.xs = takeD(c.nx); e.Us = takeD(c.n); e.lams = takeD(m); e.stats_s = takeD(8); e.stats_own = takeD(8);
     int *ip = (int *)dp;
     auto takeI = [&](size_t cnt) { int *r = ip; ip += cnt; return r; };
-    e.list = takeI(Bp); e.fire = takeI(Bp); e.cis = takeI(Bp); e.pis = takeI(Bp); e.blk = takeI(nblk); e.count = takeI(64);
+    e.list = takeI(Bp); e.fire = takeI(Bp); e.cis = takeI(Bp); e.pis = takeI(Bp); e.bis = takeI(Bp); e.blk = takeI(nblk); e.count = takeI(64);
     HIPCHK(hipMemset(base, 0, bytes));
     return MPC_OK;
 }
@@ -390,6 +417,14 @@ static int check_bound(const mpc_handle *h, int B, const char *who)
     return MPC_OK;
 }
 
+// ... and so does one with a bounds table, in the calls that read the box (`who`)
+static int check_box_bound(const mpc_handle *h, int B, const char *who)
+{
+    if (h->btab && B != h->btab_B)
+        return fail(MPC_E_ARG, std::string(who) + ": the bound bounds table is for a batch of " + std::to_string(h->btab_B) +
+                               " agents, this call has " + std::to_string(B) + " (mpc_set_agent_bounds)");
+    return MPC_OK;
+}
 static inline dim3 grid_for(int B, int block) { return dim3((unsigned)((B + block - 1) / block)); }
 
 // Every entry point that touches the handle's tables, workspace or streams goes through here.  While an

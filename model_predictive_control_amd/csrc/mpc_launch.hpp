@@ -40,7 +40,7 @@ template <bool SOLO, class F> static void with_hist_variant(int n, int M, bool s
 
 // returns true when K1b and K1c ran as one launch
 template <int MODEL>
-static bool launch_eval_t(mpc_handle *h, const WorkspacePA &w, hipStream_t s, const int *lists, const int *counts,
+static bool launch_eval_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, const int *lists, const int *counts,
                           int nG, int nC, hipEvent_t eva, hipEvent_t evb, int slot_bound, int *desc)
 {
     const DevCfg &c = h->dc;
@@ -103,14 +103,14 @@ static bool launch_eval_t(mpc_handle *h, const WorkspacePA &w, hipStream_t s, co
     hipLaunchKernelGGL((adjoint_kernel<MODEL>), dim3((unsigned)nblk), dim3(64), 0, s, c, w, counts, nG, nC, desc);
     return false;
 }
-static bool launch_eval(mpc_handle *h, const WorkspacePA &w, hipStream_t s, const int *lists, const int *counts, int nG, int nC,
+static bool launch_eval(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, const int *lists, const int *counts, int nG, int nC,
                         hipEvent_t eva = nullptr, hipEvent_t evb = nullptr, int slot_bound = -1, int *desc = nullptr)
 {
     return with_model(h->dc.model, [&](auto MODEL) { return launch_eval_t<MODEL()>(h, w, s, lists, counts, nG, nC, eva, evb, slot_bound, desc); });
 }
 
 // K1 alone, one wave per agent: the evaluation as the persistent kernel runs it (mpc_solo.hpp)
-static void launch_solo_eval(mpc_handle *h, const WorkspacePA &w, hipStream_t s, int want_grad)
+static void launch_solo_eval(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, int want_grad)
 {
     const DevCfg &c = h->dc;
     with_model_table(h, h->pidx, [&](auto MODEL, auto PA, auto...) {
@@ -145,7 +145,7 @@ static size_t step_dyn_lds(int ne, int n, int P, bool chain)
 }
 
 template <int NE, int MC>
-static void launch_step_t(mpc_handle *h, const WorkspacePA &w, hipStream_t s, int *lists, int *counts, int *counts_next,
+static void launch_step_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, int *lists, int *counts, int *counts_next,
                           int slot_bound, int par)
 {
     const int P = MC < 0 ? step_lds_pairs(NE, h->dc.n, h->dc.M, h->dc.m, h->lds_pairs) : h->dc.M;
@@ -178,12 +178,17 @@ static void launch_step_t(mpc_handle *h, const WorkspacePA &w, hipStream_t s, in
     const int apb = apb_env == 64 || apb_env == 32 || apb_env == 16 || apb_env == 8 || apb_env == 4 ? apb_env
                   : w.B >= 32768 ? 64 : w.B >= 16384 ? (lean ? 32 : 64) : w.B >= 6144 ? 16 : 4;
     const int nstep = (w.B + apb - 1) / apb;
-    with_flag(h->dc.m != 0, [&](auto HASM) {
-        hipLaunchKernelGGL((step_kernel<NE, MC, HASM()>), dim3((unsigned)(nstep + nchain)), dim3(64 * STEP_WAVES), lds,
-                           s, dcl, w, lists, counts, counts_next, apb, nstep, par, P);
+    // (w.btab: a bounds table is bound, the per-agent-box form -- the one kernel of the round path that reads the box)
+    with_flags(h->dc.m != 0, w.btab != nullptr, [&](auto HASM, auto BA) {
+        if constexpr (BA())
+            hipLaunchKernelGGL((step_kernel_box<NE, MC, HASM()>), dim3((unsigned)(nstep + nchain)), dim3(64 * STEP_WAVES), lds,
+                               s, dcl, w, w.box(), lists, counts, counts_next, apb, nstep, par, P);
+        else
+            hipLaunchKernelGGL((step_kernel<NE, MC, HASM()>), dim3((unsigned)(nstep + nchain)), dim3(64 * STEP_WAVES), lds,
+                               s, dcl, w, lists, counts, counts_next, apb, nstep, par, P);
     });
 }
-static void launch_step(mpc_handle *h, const WorkspacePA &w, hipStream_t s, int *lists, int *counts, int *counts_next,
+static void launch_step(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, int *lists, int *counts, int *counts_next,
                         int slot_bound, int par)
 {
     with_hist_variant<false>(h->dc.n, h->dc.M, h->step_regs, [&](auto NE, auto MC) {
@@ -195,7 +200,7 @@ static void launch_step(mpc_handle *h, const WorkspacePA &w, hipStream_t s, int 
 // a list of them is built first; otherwise every agent of the view is claimed).  `bound` = an upper
 // bound on the number of agents it will find.
 template <int MODEL, int NE, int MC>
-static void launch_solo_t(mpc_handle *h, const WorkspacePA &v, hipStream_t s, int *ctr, bool listed, int bound,
+static void launch_solo_t(mpc_handle *h, const WorkspaceHost &v, hipStream_t s, int *ctr, bool listed, int bound,
                           long long max_trips)
 {
     const DevCfg &c = h->dc;
@@ -208,12 +213,23 @@ static void launch_solo_t(mpc_handle *h, const WorkspacePA &v, hipStream_t s, in
     nblk = std::max(1, std::min(nblk, 4 * SoloOcc<MODEL>::WPS * h->num_cus)); // what is resident (registers); the rest queues
     // (v.ptab: a parameter table is bound, the per-agent variant.  The lookahead kernel exists where solo_lookahead can
     // say yes: Pacejka model, one element per lane)
+    // v.btab: a bounds table is bound, the box form, which exists together with the parameter form alone -- without a
+    // parameter table of the caller's it runs on the handle's own one-row table (mpc_set_agent_bounds made it)
+    if (v.btab) {
+        WorkspacePA vp = v;
+        if (!vp.ptab) { vp.ptab = h->own_ptab; vp.pidx = h->own_pidx; }
+        with_flag(la, [&](auto LA) {
+            if constexpr (!LA() || (MODEL == PAC && NE == 1))
+                hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, LA(), true, BoxTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c, vp, list, ctr, max_trips, v.box());
+        });
+        return;
+    }
     with_flags(la, v.ptab != nullptr, [&](auto LA, auto PA) {
         if constexpr (!LA() || (MODEL == PAC && NE == 1))
             hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, LA(), PA()>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c, v, list, ctr, max_trips);
     });
 }
-static void launch_solo(mpc_handle *h, const WorkspacePA &v, hipStream_t s, int *ctr, bool listed, int bound,
+static void launch_solo(mpc_handle *h, const WorkspaceHost &v, hipStream_t s, int *ctr, bool listed, int bound,
                         long long max_trips)
 {
     const DevCfg &c = h->dc;

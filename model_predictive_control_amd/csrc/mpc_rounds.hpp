@@ -5,9 +5,9 @@
 #include "mpc_launch.hpp"
 
 // a view of the workspace restricted to agents [lo, hi): local agent ids, own lists / scratch
-static WorkspacePA group_view(const WorkspacePA &w, const DevCfg &c, int g, int lo, int hi)
+static WorkspaceHost group_view(const WorkspaceHost &w, const DevCfg &c, int g, int lo, int hi)
 {
-    WorkspacePA v = w;
+    WorkspaceHost v = w;
     const size_t n = c.n, m = c.m, M = c.M;
     v.x0 = w.x0 + (size_t)lo * c.nx; v.xo = w.xo + (size_t)lo * n;
     v.xk = w.xk + (size_t)lo * n; v.gk = w.gk + (size_t)lo * n; v.q = w.q + (size_t)lo * n;
@@ -21,6 +21,7 @@ static WorkspacePA group_view(const WorkspacePA &w, const DevCfg &c, int g, int 
     v.rec = w.rec + (size_t)lo * REC;
     if (w.cl_index) v.cl_index = w.cl_index + lo;
     if (w.pidx) v.pidx = w.pidx + lo;
+    if (w.bidx) v.bidx = w.bidx + lo;
     const size_t soff = 2 * (size_t)lo + 64 * (size_t)g; // disjoint slot intervals inside the shared scratch
     v.trajx = w.trajx + soff; v.useq = w.useq + soff; v.stage_L = w.stage_L + soff; v.jac = w.jac + soff;
     v.agent_of = w.agent_of + soff;
@@ -35,13 +36,13 @@ struct SolveRun {
     mpc_handle *const h;
     const hipStream_t s;                 // the caller's stream: the solve begins and ends on it
     const DevCfg &c;
-    WorkspacePA &w;
+    WorkspaceHost &w;
     const int B, check_every;
     long long max_rounds = 0;
     bool solo_ok = false, all_solo = false;
     // the sub-batch groups: views of the workspace, streams, progress
     int ng = 0, nactive = 0;
-    WorkspacePA gv[MPC_MAX_GROUPS];
+    WorkspaceHost gv[MPC_MAX_GROUPS];
     hipStream_t gs[MPC_MAX_GROUPS];      // (one group: the caller's stream)
     struct GroupRun { long long round = 0, window = 0; bool active = true; int slot_bound = 0; };
     GroupRun gr[MPC_MAX_GROUPS];
@@ -140,7 +141,7 @@ struct SolveRun {
     void queue_window_untimed(int g)            // `check_every` rounds of group g, then the copy of its counters
     {
         GroupRun &r = gr[g];
-        const WorkspacePA &v = gv[g];
+        const WorkspaceHost &v = gv[g];
         int cur = 0;
         for (int i = 0; i < check_every && r.round < max_rounds; i++) {
             cur = (int)(r.round & 1);

@@ -251,10 +251,11 @@ __global__ void __launch_bounds__(64, 1) solo_eval_kernel(const DevCfg c_, const
 
 // One agent's solve with the lookahead (Pacejka, NE = 1): the loop of solo_kernel with a cache lookup before every
 // evaluation trip and candidates riding in the free slots of the trip.
-// (cm: the DevCfg the evaluations run on -- c itself, or the agent's private one when a parameter table is bound)
-template <int MC>
+// (cm: the DevCfg the evaluations run on -- c itself, or the agent's private one when a parameter table is bound;
+// bx: the box the state machine and the candidate points project onto -- the DevCfg's, or the agent's own)
+template <int MC, class BOX>
 __device__ __forceinline__ void solo_agent_la(const DevCfg &c, const DevCfg &cm, const Workspace &w, int a, int lane, double *hist,
-                                              double *traj, double *rec, double *la_base, long long max_trips)
+                                              double *traj, double *rec, double *la_base, long long max_trips, const BOX &bx)
 {
 #pragma clang fp contract(off)   // the candidate points are formed by the state machine's own functions: same roundings
     const int n = c.n, par = lane & 1;
@@ -269,7 +270,7 @@ __device__ __forceinline__ void solo_agent_la(const DevCfg &c, const DevCfg &cm,
     const auto ldv = [&](const double *rowp) { return lane < n ? rowp[lane] : 0.0; };
     for (long long trip = 0; trip < max_trips; trip++) {
         const AgentIn<1> in = load_agent<1>(c, w, a, lane);
-        int req = advance_agent<1, MC>(c, w, a, lane, in, hist, false, /*allow_spec=*/true);
+        int req = advance_agent<1, MC, true, false, BOX>(c, w, a, lane, in, hist, false, /*allow_spec=*/true, false, 1 << 30, bx);
         if ((req & (REQ_GRAD | REQ_COST)) == 0) break;                // uniform: the agent is done
         // the record as the state machine left it (same wave, same addresses: ordered behind its stores)
         double rv = w.rec[(size_t)a * REC + lane];
@@ -336,7 +337,7 @@ __device__ __forceinline__ void solo_agent_la(const DevCfg &c, const DevCfg &cm,
             for (int j = 0; j < 3; j++) {
                 t = t / 2.0;
                 if (!(t >= c.tau_min)) break;
-                const Row<1> xt = trial_point<1>(c, par, X, G, Q, gam, t, t / 2.0 < c.tau_min);
+                const Row<1> xt = trial_point<1>(c, bx, par, X, G, Q, gam, t, t / 2.0 < c.tau_min);
                 add_candidate(xt.v[0], true);
             }
         } else if (ph == PH_W_LS_C || ph == PH_W_DL) {
@@ -351,14 +352,14 @@ __device__ __forceinline__ void solo_agent_la(const DevCfg &c, const DevCfg &cm,
                 const double t = tau / 2.0;
                 if (t >= c.tau_min) {
                     X.v[0] = ldv(w.xk + an); G.v[0] = ldv(w.gk + an); Q.v[0] = ldv(w.q + an);
-                    const Row<1> xt = trial_point<1>(c, par, X, G, Q, gam, t, t / 2.0 < c.tau_min);
+                    const Row<1> xt = trial_point<1>(c, bx, par, X, G, Q, gam, t, t / 2.0 < c.tau_min);
                     const int e = cache.find(lane, xt.v[0], true);
                     if (e >= 0) {
                         Row<1> gt; gt.v[0] = lane < n ? cache.gr[(size_t)e * n + lane] : 0.0;
-                        const double xh = xt.v[0] + prox_p(c, par, xt.v[0], gt.v[0], gam);       // prox_to_xe at the next trial
+                        const double xh = xt.v[0] + prox_p(c, bx, par, xt.v[0], gt.v[0], gam);       // prox_to_xe at the next trial
                         add_candidate(xh, false);
                         Row<1> sp; sp.v[0] = 0.0;
-                        const int nj = spec_point<1>(c, par, n, lane, xt, gt, gam, sp);
+                        const int nj = spec_point<1>(c, bx, par, n, lane, xt, gt, gam, sp);
                         if (!c.no_spec && nj > 0 && nj < n) add_candidate(sp.v[0], true);
                     }
                 }
@@ -368,7 +369,7 @@ __device__ __forceinline__ void solo_agent_la(const DevCfg &c, const DevCfg &cm,
             for (int j = 0; j < LA_SLOTS; j++) {
                 if (nslot >= LA_SLOTS || !(Ld * 2.0 <= c.L_max)) break;
                 gd = gd / 2.0; Ld = Ld * 2.0;
-                add_candidate(XN.v[0] + prox_p(c, par, XN.v[0], GE.v[0], gd), false);
+                add_candidate(XN.v[0] + prox_p(c, bx, par, XN.v[0], GE.v[0], gd), false);
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -395,11 +396,18 @@ template <int MODEL> struct SoloOcc { static constexpr int WPS = MODEL == KIN ? 
 // LA: the lookahead variant (host: solo_lookahead) -- a kernel of its own, so that neither holds the other's code
 // PA: the per-agent variant (a parameter table is bound): the evaluations of agent a run on the handle's DevCfg with
 // the fields of a's row, read by scalar loads when the wave claims the agent; the state machine keeps the handle's
-template <int MODEL, int NE, int MC, bool LA = false, bool PA = false>
+// BT: empty, or the bounds table (one trailing BoxTab argument: mpc_set_agent_bounds) -- the agent's box is read in the
+// same place, its row by scalar loads and this lane's two values of it chosen once per agent (lane_box_uniform); the state
+// machine and the lookahead's candidate points project onto it.  The box form exists together with PA alone: without a
+// parameter table of the caller's the host binds a one-row table of the handle's own values (mpc_launch.hpp).
+template <int MODEL, int NE, int MC, bool LA = false, bool PA = false, class... BT>
 __global__ void __launch_bounds__(64 * SOLO_WAVES, SoloOcc<MODEL>::WPS)
 solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int *__restrict__ ctr,
-            long long max_trips)
+            long long max_trips, BT... bt)
 {
+    constexpr bool BA = sizeof...(BT) != 0;
+    static_assert(!BA || PA, "the box form of the persistent kernel exists in the per-agent-parameter form alone");
+    using BOX = BoxOf<BA, LaneBox>;
     extern __shared__ double s_solo[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const size_t per_wave = solo_lds_doubles<MODEL>(c.nfe, c.N, c.n, c.M, MC < 0);
@@ -420,12 +428,16 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
             i = __builtin_amdgcn_readfirstlane(i);
             if (i >= total) break;
             const int a = list ? list[i] : i;
-            if constexpr (PA) {
+            if constexpr (BA) {
                 DevCfg cm = c;
                 agent_cfg_uniform(cm, w.ptab, w.pidx, a);
-                solo_agent_la<MC>(c, cm, w, a, lane, hist, traj, rec, la_base, max_trips);
+                solo_agent_la<MC>(c, cm, w, a, lane, hist, traj, rec, la_base, max_trips, lane_box_uniform(bt..., a, lane));
+            } else if constexpr (PA) {
+                DevCfg cm = c;
+                agent_cfg_uniform(cm, w.ptab, w.pidx, a);
+                solo_agent_la<MC>(c, cm, w, a, lane, hist, traj, rec, la_base, max_trips, CfgBox());
             } else
-            solo_agent_la<MC>(c, c, w, a, lane, hist, traj, rec, la_base, max_trips);
+            solo_agent_la<MC>(c, c, w, a, lane, hist, traj, rec, la_base, max_trips, CfgBox());
         }
         return;
     }
@@ -438,6 +450,8 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
         DevCfg cm_;
         if constexpr (PA) { cm_ = c; agent_cfg_uniform(cm_, w.ptab, w.pidx, a); }
         const DevCfg &cm = PA ? cm_ : c;
+        BOX bx{};
+        if constexpr (BA) bx = lane_box_uniform(bt..., a, lane);
 #if MPC_DEV_STAMP == 5
         const long long st0 = __builtin_amdgcn_s_memrealtime();
         long long ntrip = 0, t_adv = 0;
@@ -448,7 +462,7 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
             const long long ta = __builtin_amdgcn_s_memrealtime();
 #endif
             const AgentIn<NE> in = load_agent<NE>(c, w, a, lane);
-            const int req = advance_agent<NE, MC>(c, w, a, lane, in, hist, false, /*allow_spec=*/spec);
+            const int req = advance_agent<NE, MC, true, false, BOX>(c, w, a, lane, in, hist, false, /*allow_spec=*/spec, false, 1 << 30, bx);
             if ((req & (REQ_GRAD | REQ_COST)) == 0) break;              // uniform: the agent is done
 #if MPC_DEV_STAMP == 5
             t_adv += __builtin_amdgcn_s_memrealtime() - ta;

@@ -103,6 +103,14 @@ struct WorkspacePA : Workspace {
     const double *ptab;                            // [P][NPARAM] caller's table
     const int *pidx;                               // [B]         caller's row index per agent
 };
+// The input-box table of mpc_set_agent_bounds, as the per-agent-box kernels (step_kernel_box, the box form of solo_kernel,
+// prox_box_kernel) receive it: an argument of its own BEHIND the DevCfg and the Workspace, so that Workspace -- and with
+// it the argument segment and the code of every kernel that has no box form -- is what it was, and KernArgs::W_OFF holds
+// for the new kernels too.
+struct BoxTab {
+    const double *btab;                            // [P][NBOUND] caller's table
+    const int *bidx;                               // [B]         caller's row index per agent
+};
 template <bool PA> struct WsArgT { using type = Workspace; };
 template <> struct WsArgT<true> { using type = WorkspacePA; };
 template <bool PA> using WsArg = typename WsArgT<PA>::type;
@@ -125,6 +133,9 @@ struct KernArgs {
     }
     __device__ __forceinline__ const DevCfg &c() const { return *(const DevCfg *)p; }
     __device__ __forceinline__ const Workspace &w() const { return *(const Workspace *)(p + W_OFF); }
+    // (the per-agent-box kernels alone: their third parameter)
+    static constexpr size_t B_OFF = (W_OFF + sizeof(Workspace) + alignof(BoxTab) - 1) / alignof(BoxTab) * alignof(BoxTab);
+    __device__ __forceinline__ const BoxTab &box() const { return *(const BoxTab *)(p + B_OFF); }
 };
 
 #ifdef MPC_DEV_STAMP
@@ -299,26 +310,70 @@ __device__ __forceinline__ void strow(double *__restrict__ p, int n, int lane, c
     for (int e = 0; e < NE; e++) { const int j = lane + 64 * e; if (j < n) p[j] = r.v[e]; }
 }
 
-__device__ __forceinline__ double prox_p(const DevCfg &c, int par, double x, double g, double gamma)
+// Where the projection takes the input box C = [lo, hi] of element parity `par` (0 drive, 1 steering) from.
+//   CfgBox    the handle's box, read from the DevCfg at the point of use -- what every kernel without a box form does
+//   LaneBox   the agent's own box in the wave-per-agent code: this lane's two values (par = lane & 1 is the lane's)
+//   AgentBox  the agent's own box where a thread owns the agent (chain_block, prox_box_kernel): the whole row
+struct CfgBox {
+    __device__ __forceinline__ double lo(const DevCfg &c, int par) const { return c.u_lb[par]; }
+    __device__ __forceinline__ double hi(const DevCfg &c, int par) const { return c.u_ub[par]; }
+};
+struct LaneBox {
+    double l, h;
+    __device__ __forceinline__ double lo(const DevCfg &, int) const { return l; }
+    __device__ __forceinline__ double hi(const DevCfg &, int) const { return h; }
+};
+struct AgentBox {
+    double lb[2], ub[2];
+    __device__ __forceinline__ double lo(const DevCfg &, int par) const { return par ? lb[1] : lb[0]; }
+    __device__ __forceinline__ double hi(const DevCfg &, int par) const { return par ? ub[1] : ub[0]; }
+};
+template <bool BA, class PER_AGENT> struct BoxOfT { using type = CfgBox; };
+template <class PER_AGENT> struct BoxOfT<true, PER_AGENT> { using type = PER_AGENT; };
+template <bool BA, class PER_AGENT> using BoxOf = typename BoxOfT<BA, PER_AGENT>::type;
+// this lane's two values of row `row` (wave-uniform) of the table: elements par and par + 2
+__device__ __forceinline__ LaneBox load_lane_box(const BoxTab &bt, int row, int lane)
+{
+    const double *__restrict__ r = bt.btab + (size_t)row * NBOUND + (lane & 1);
+    LaneBox b;
+    b.l = r[0]; b.h = r[2];
+    return b;
+}
+
+// ... of row bt.bidx[a] where one wave owns agent a for long (the persistent kernel): the wave-uniform row by scalar
+// loads through the constant address space (the table is read-only while a kernel runs), the lane's two values chosen
+__device__ __forceinline__ LaneBox lane_box_uniform(const BoxTab &bt, int a, int lane)
+{
+    const int row = __builtin_amdgcn_readfirstlane(bt.bidx[a]);
+    const __attribute__((address_space(4))) double *r =
+        (const __attribute__((address_space(4))) double *)(bt.btab + (size_t)row * NBOUND);
+    LaneBox b;
+    b.l = (lane & 1) ? r[1] : r[0]; b.h = (lane & 1) ? r[3] : r[2];
+    return b;
+}
+
+template <class BOX>
+__device__ __forceinline__ double prox_p(const DevCfg &c, const BOX &bx, int par, double x, double g, double gamma)
 {
 #pragma clang fp contract(off)   // fixed roundings: the step kernel and the persistent kernel must agree bit for bit
     // comparison-selects, not fmin/fmax: a NaN gradient must stay a NaN step (Eigen's cwiseMax/cwiseMin
     // in alpaqa's projection keep it too), so that ||p||/gamma is NaN and the stop test says NotFinite
-    const double lo = c.u_lb[par] - x, hi = c.u_ub[par] - x;
+    const double lo = bx.lo(c, par) - x, hi = bx.hi(c, par) - x;
     double p = -gamma * g;
     p = p < lo ? lo : p;
     return hi < p ? hi : p;
 }
-__device__ __forceinline__ bool in_J(const DevCfg &c, int par, double x, double g, double gamma)
+template <class BOX>
+__device__ __forceinline__ bool in_J(const DevCfg &c, const BOX &bx, int par, double x, double g, double gamma)
 {
 #pragma clang fp contract(off)   // fixed roundings: the step kernel and the persistent kernel must agree bit for bit
     const double gd = x - gamma * g;
-    return !(gd < c.u_lb[par] || c.u_ub[par] < gd);
+    return !(gd < bx.lo(c, par) || bx.hi(c, par) < gd);
 }
 
 // K2: forward-backward step of (xb, gb) with step gamma: xhat -> xe row, returns ||p||^2, g'p
-template <int NE>
-__device__ __forceinline__ void prox_to_xe(const DevCfg &c, double *__restrict__ xe, int n, int lane,
+template <int NE, class BOX>
+__device__ __forceinline__ void prox_to_xe(const DevCfg &c, const BOX &bx, double *__restrict__ xe, int n, int lane,
                                            const Row<NE> &xb, const Row<NE> &gb, double gamma,
                                            double &pp, double &gp)
 {
@@ -327,7 +382,7 @@ __device__ __forceinline__ void prox_to_xe(const DevCfg &c, double *__restrict__
     double a = 0.0, b = 0.0;
 #pragma unroll
     for (int e = 0; e < NE; e++) {
-        const double p = prox_p(c, lane & 1, xb.v[e], gb.v[e], gamma);
+        const double p = prox_p(c, bx, lane & 1, xb.v[e], gb.v[e], gamma);
         xh.v[e] = xb.v[e] + p;
         if (lane + 64 * e < n) { a = fma(p, p, a); b = fma(gb.v[e], p, b); }
     }
@@ -468,15 +523,15 @@ __device__ __forceinline__ bool lbfgs_two_loop(const DevCfg &c, const double *__
 // The line-search trial point for step tau (PH_LS_TRIAL) and the point of the speculative Hessian-vector gradient
 // (speculate / PH_AFTER_DL): one function each for the state machine and for the persistent kernel's lookahead
 // (mpc_solo.hpp), which forms the SAME points ahead of the state machine and must get the same bits.
-template <int NE>
-__device__ __forceinline__ Row<NE> trial_point(const DevCfg &c, int par, const Row<NE> &x, const Row<NE> &g,
+template <int NE, class BOX>
+__device__ __forceinline__ Row<NE> trial_point(const DevCfg &c, const BOX &bx, int par, const Row<NE> &x, const Row<NE> &g,
                                                const Row<NE> &qv, double gamma, double tau, bool fallback)
 {
 #pragma clang fp contract(off)
     Row<NE> r;
 #pragma unroll
     for (int e = 0; e < NE; e++) {
-        const double p = prox_p(c, par, x.v[e], g.v[e], gamma);
+        const double p = prox_p(c, bx, par, x.v[e], g.v[e], gamma);
         if (fallback) r.v[e] = x.v[e] + p;
         else if (tau == 1.0) r.v[e] = x.v[e] + qv.v[e];
         else r.v[e] = x.v[e] + (1.0 - tau) * p + tau * qv.v[e];
@@ -484,8 +539,8 @@ __device__ __forceinline__ Row<NE> trial_point(const DevCfg &c, int par, const R
     return r;
 }
 // returns |J| (the point exists when 0 < |J| < n); all 64 lanes must call it
-template <int NE>
-__device__ __forceinline__ int spec_point(const DevCfg &c, int par, int n, int lane, const Row<NE> &xn, const Row<NE> &ge,
+template <int NE, class BOX>
+__device__ __forceinline__ int spec_point(const DevCfg &c, const BOX &bx, int par, int n, int lane, const Row<NE> &xn, const Row<NE> &ge,
                                           double gm, Row<NE> &out)
 {
 #pragma clang fp contract(off)
@@ -494,8 +549,8 @@ __device__ __forceinline__ int spec_point(const DevCfg &c, int par, int n, int l
 #pragma unroll
     for (int e = 0; e < NE; e++) {
         const bool valid = lane + 64 * e < n;
-        const bool in = in_J(c, par, xn.v[e], ge.v[e], gm);
-        qv.v[e] = in ? 0.0 : prox_p(c, par, xn.v[e], ge.v[e], gm);
+        const bool in = in_J(c, bx, par, xn.v[e], ge.v[e], gm);
+        qv.v[e] = in ? 0.0 : prox_p(c, bx, par, xn.v[e], ge.v[e], gm);
         if (valid) { cntJ += in ? 1.0 : 0.0; xx += xn.v[e] * xn.v[e]; }
     }
     wave_sum2_n(cntJ, xx, n);
@@ -571,10 +626,12 @@ __device__ __forceinline__ AgentIn<NE> load_agent(const DevCfg &c, const Workspa
 // (KernArgs), and each turn forms the lane masks of the record's slots (lane == slot, one v_cmp) where it writes them:
 // hoisted out of the loop, 50 such masks and the configuration were live across all of it, far more than a wave's
 // 106 scalar registers, and came back from spill lanes with two v_readlane each.
-template <int NE, int MC, bool HASM = true, bool LEAN = false>
+// BOX: where the projection takes the input box from (CfgBox: the DevCfg's; LaneBox: `bx`, the agent's own row of a bound
+// bounds table, fetched with the agent's rows)
+template <int NE, int MC, bool HASM = true, bool LEAN = false, class BOX = CfgBox>
 __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int lane, const AgentIn<NE> &in,
                              double *hist, bool hist_ready, bool allow_spec = true, bool allow_chain = false,
-                             int P = 1 << 30)
+                             int P = 1 << 30, const BOX &bx = BOX())
 {
 #pragma clang fp contract(off)   // fixed roundings: the step kernel and the persistent kernel must agree bit for bit
     const int n = cfg.n, m = HASM ? cfg.m : 0;
@@ -671,7 +728,7 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
         auto speculate = [&](double gm) {
             if (c.no_spec || !allow_spec) { spec = 0; return; }
             Row<NE> xh;
-            const int nj = spec_point<NE>(c, par, n, lane, XN, GE, gm, xh);
+            const int nj = spec_point<NE>(c, bx, par, n, lane, XN, GE, gm, xh);
             spec = 0;
             if (nj > 0 && nj < n) {
                 strow<NE>(w.xe2 + an, n, lane, xh);
@@ -753,7 +810,7 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
             }
             gamma = c.Lgamma / Lk;
             tau = NAN;
-            prox_to_xe<NE>(c, w.xe + an, n, lane, X, g, gamma, t_pp, t_gp); pp = t_pp; gp = t_gp;
+            prox_to_xe<NE>(c, bx, w.xe + an, n, lane, X, g, gamma, t_pp, t_gp); pp = t_pp; gp = t_gp;
             gamma_top = gamma;
             req = REQ_COST; phase = PH_W_DL;
         } break;
@@ -764,7 +821,7 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
             const double margin = (1.0 + fabs(psik)) * c.qub_tol;
             if (psixh - psik > gp + 0.5 * Lk * pp + margin && Lk * 2.0 <= c.L_max) {
                 Lk *= 2.0; gamma /= 2.0;
-                prox_to_xe<NE>(c, w.xe + an, n, lane, X, G, gamma, t_pp, t_gp); pp = t_pp; gp = t_gp;
+                prox_to_xe<NE>(c, bx, w.xe + an, n, lane, X, G, gamma, t_pp, t_gp); pp = t_pp; gp = t_gp;
                 req = REQ_COST; // stay in PH_W_DL
                 break;
             }
@@ -805,7 +862,7 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
             if (eta > 0.0 && isfinite(eta) && eta * c.Lgamma > gamma) {
                 Lk = 1.0 / eta;
                 gamma = c.Lgamma / Lk;
-                prox_to_xe<NE>(c, w.xe + an, n, lane, X, g, gamma, t_pp, t_gp); pp = t_pp; gp = t_gp;
+                prox_to_xe<NE>(c, bx, w.xe + an, n, lane, X, g, gamma, t_pp, t_gp); pp = t_pp; gp = t_gp;
                 req = REQ_COST; phase = PH_W_DL;
                 break;
             }
@@ -828,7 +885,7 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
                     Row<NE> x = X;
                     const Row<NE> g = G;
 #pragma unroll
-                    for (int e = 0; e < NE; e++) x.v[e] = x.v[e] + prox_p(c, par, x.v[e], g.v[e], gamma);
+                    for (int e = 0; e < NE; e++) x.v[e] = x.v[e] + prox_p(c, bx, par, x.v[e], g.v[e], gamma);
                     strow<NE>(w.xo + an, n, lane, x);
                     for (int kk = lane; kk < m; kk += 64) {
                         const double yh = w.yhx[am + kk];
@@ -852,8 +909,8 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
 #pragma unroll
                 for (int e = 0; e < NE; e++) {
                     const bool valid = lane + 64 * e < n;
-                    const bool in = in_J(c, par, x.v[e], g.v[e], gamma);
-                    qv.v[e] = in ? 0.0 : prox_p(c, par, x.v[e], g.v[e], gamma);
+                    const bool in = in_J(c, bx, par, x.v[e], g.v[e], gamma);
+                    qv.v[e] = in ? 0.0 : prox_p(c, bx, par, x.v[e], g.v[e], gamma);
                     if (valid) { cntJ += in ? 1.0 : 0.0; xx += x.v[e] * x.v[e]; }
                 }
                 wave_sum2_n(cntJ, xx, n);
@@ -891,7 +948,7 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
             Row<NE> qv = Q;
 #pragma unroll
             for (int e = 0; e < NE; e++)
-                if (in_J(c, par, x.v[e], g.v[e], gamma)) qv.v[e] = -g.v[e] - (gh.v[e] - g.v[e]) / hfd;
+                if (in_J(c, bx, par, x.v[e], g.v[e], gamma)) qv.v[e] = -g.v[e] - (gh.v[e] - g.v[e]) / hfd;
             Q = qv;
             phase = PH_LS_INIT;
         } break;
@@ -902,7 +959,7 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
                 const Row<NE> x = X, g = G;
                 bool inj[NE];
 #pragma unroll
-                for (int e = 0; e < NE; e++) inj[e] = lane + 64 * e < n && in_J(c, par, x.v[e], g.v[e], gamma);
+                for (int e = 0; e < NE; e++) inj[e] = lane + 64 * e < n && in_J(c, bx, par, x.v[e], g.v[e], gamma);
                 const double *Sa = w.S + (size_t)a * c.M * n, *Ya = w.Y + (size_t)a * c.M * n;
                 const double *const Sg = Sa, *const Yg = Ya;
                 if (MC < 0) {
@@ -934,7 +991,7 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
         case PH_LS_TRIAL: {
             Ln = Lk; gamman = gamma;
             fallback = tau / 2.0 < c.tau_min; // safe prox step: x+ = xhat, psi+ = psi(xhat)
-            const Row<NE> x = trial_point<NE>(c, par, X, G, Q, gamma, tau, fallback != 0);
+            const Row<NE> x = trial_point<NE>(c, bx, par, X, G, Q, gamma, tau, fallback != 0);
             XN = x;
             strow<NE>(w.xn + an, n, lane, x); strow<NE>(w.xe + an, n, lane, x);
             // (round path: the entry is marked as "gradient at a trial point" whether or not the NEXT launch will
@@ -944,7 +1001,7 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
         case PH_W_LS_G: {
             psin = fallback ? (double)psixh : (double)psie;
             // the gradient at x+ stays in the ge row until the next gradient evaluation
-            prox_to_xe<NE>(c, w.xe + an, n, lane, XN, GE, gamman, t_pp, t_gp); ppn = t_pp; gpn = t_gp;
+            prox_to_xe<NE>(c, bx, w.xe + an, n, lane, XN, GE, gamman, t_pp, t_gp); ppn = t_pp; gpn = t_gp;
             req = REQ_COST; phase = PH_W_LS_C;
             speculate(gamman);
         } break;
@@ -954,7 +1011,7 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
             const double margin_dl = (1.0 + fabs(psin)) * c.qub_tol;
             if (psixhn - psin > gpn + 0.5 * Ln * ppn + margin_dl && Ln * 2.0 <= c.L_max) {
                 Ln *= 2.0; gamman /= 2.0;
-                prox_to_xe<NE>(c, w.xe + an, n, lane, XN, GE, gamman, t_pp, t_gp); ppn = t_pp; gpn = t_gp;
+                prox_to_xe<NE>(c, bx, w.xe + an, n, lane, XN, GE, gamman, t_pp, t_gp); ppn = t_pp; gpn = t_gp;
                 req = REQ_COST; // stay
                 speculate(gamman);
                 break;
@@ -1159,7 +1216,10 @@ __device__ __forceinline__ int wave_append(int *counter, bool on)
 constexpr int CHAIN_SLOTS = 64;   // slots per workgroup: one tile of 64 x (n + 1) doubles, 21 KB at n = 40 -- under the 31 KB of
                                   // history the wave-per-agent blocks of the launch hold (12 pairs), so that five workgroups of
                                   // either kind share a CU (both kinds get the launch's one dynamic-LDS size)
-__device__ __forceinline__ void chain_block(const DevCfg &c, const Workspace &w, int cb, int gpad, int par,
+// BA: every agent projects onto its own box, row bt.bidx[a] of the bounds table.  The thread that will own the agent of
+// slot t is the one that reads the slot's entry, so the row is asked for there, ahead of the gradient tile.
+template <bool BA>
+__device__ __forceinline__ void chain_block(const DevCfg &c, const Workspace &w, const BoxTab &bt, int cb, int gpad, int par,
                                             int *__restrict__ lists_out, int *__restrict__ counts_out, double *lds)
 {
 #pragma clang fp contract(off)   // fixed roundings: the same bits as the wave-per-agent PH_W_LS_G
@@ -1177,12 +1237,19 @@ __device__ __forceinline__ void chain_block(const DevCfg &c, const Workspace &w,
     if (slot0 < 0 || slot0 >= gpad) return;              // uniform: no gradient slots here
     double *tA = lds;
     int *s_agent = (int *)(tA + CHAIN_SLOTS * ld);       // agent of the slot or -1
+    BoxOf<BA, AgentBox> bx{};
     const int total = CHAIN_SLOTS * n;
     {
         const int uslot = slot0 + t;
         const int raw = uslot < gpad ? w.agent_of[uslot] : -1;
         const bool on = raw >= 0 && (raw & CHAIN_BIT) != 0 && (raw & CH2_BIT) == 0 && (raw & AGENT_MASK) < w.B;
         s_agent[t] = on ? (raw & AGENT_MASK) : -1;
+        if constexpr (BA) {
+            if (on) {
+                const double *__restrict__ row = bt.btab + (size_t)bt.bidx[raw & AGENT_MASK] * NBOUND;
+                bx.lb[0] = row[0]; bx.lb[1] = row[1]; bx.ub[0] = row[2]; bx.ub[1] = row[3];
+            }
+        }
     }
     __builtin_amdgcn_wave_barrier();                     // one wave: LDS is in order
     for (int base = 0; base < total; base += 64 * 8) {   // gradient rows -> the tile (coalesced), eight loads in flight per lane
@@ -1219,12 +1286,12 @@ __device__ __forceinline__ void chain_block(const DevCfg &c, const Workspace &w,
         for (int k = N - 1; k >= 0; k--) {
             const double x0 = useq[(size_t)(2 * k) * St], x1 = useq[(size_t)(2 * k + 1) * St];
             const double g0 = ga[2 * k], g1 = ga[2 * k + 1];
-            const double p0 = prox_p(c, 0, x0, g0, gm), p1 = prox_p(c, 1, x1, g1, gm);   // prox_to_xe
+            const double p0 = prox_p(c, bx, 0, x0, g0, gm), p1 = prox_p(c, bx, 1, x1, g1, gm);   // prox_to_xe
             ga[2 * k] = x0 + p0; ga[2 * k + 1] = x1 + p1;
             spp.add(k, fma(p0, p0, 0.0), fma(p1, p1, 0.0));
             sgp.add(k, fma(g0, p0, 0.0), fma(g1, p1, 0.0));
             if (!c.no_spec) {                                                          // speculate()
-                const bool in0 = in_J(c, 0, x0, g0, gm), in1 = in_J(c, 1, x1, g1, gm);
+                const bool in0 = in_J(c, bx, 0, x0, g0, gm), in1 = in_J(c, bx, 1, x1, g1, gm);
                 cnt += (in0 ? 1 : 0) + (in1 ? 1 : 0);
                 const double q0 = in0 ? 0.0 : p0, q1 = in1 ? 0.0 : p1;
                 x2[2 * k] = x0 + h * q0; x2[2 * k + 1] = x1 + h * q1;
@@ -1277,114 +1344,23 @@ __global__ void __launch_bounds__(64 * STEP_WAVES, step_waves_per_simd(NE, MC, H
 step_kernel(const DevCfg c, const Workspace w, int *__restrict__ lists_out,
             int *__restrict__ counts_out, int *__restrict__ counts_next, int apb, int nstep, int par, int P)
 {
-    // blocks [0, nstep): the wave-per-agent state machine; blocks beyond (c.chain): PH_W_LS_G by one thread per
-    // agent for the gradient slots of the round just finished, whose count K1c left in counts_next[2] (the buffer
-    // of that round: this kernel zeroes its two list counters for the round after this one, not that word)
-    if ((int)blockIdx.x >= nstep) {
-        extern __shared__ double s_chain[];
-        if (NE == 1) chain_block(c, w, (int)blockIdx.x - nstep, counts_next[2], par, lists_out, counts_out, s_chain);
-        return;
-    }
-    // apb = agents per workgroup (64, 16 or 4): a wave walks its agents one after the other, so a small
-    // batch is spread over more workgroups (one agent per wave at apb = 4) -- latency, not throughput
-    __shared__ int s_req[64];
-    __shared__ int s_next;
-    extern __shared__ double s_hist[];                   // MC < 0: 2 M n doubles per wave
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#if MPC_DEV_STAMP == 3
-    DevStamp stamp(blockIdx.x * STEP_WAVES + wv);
-#endif
-    double *hist = s_hist + (MC < 0 ? (size_t)wv * 2 * P * c.n : 0);
-    if (blockIdx.x == 0 && threadIdx.x == 0) { counts_next[0] = 0; counts_next[1] = 0; } // next round's buffer
-    // Which of the workgroup's agents are still running: one coalesced look at their phase words.
-    // Only the running ones are handed to the waves, so a wave never pays a memory round trip to
-    // find out that an agent is finished.
-    const int base = blockIdx.x * apb;
-    const int phw = lane < apb && base + lane < w.B ? rec_int_of(w.rec[(size_t)(base + lane) * REC + R_PHASE]) : 0;
-    // (PH_DONE == 0; with c.chain an agent that waits in PH_W_LS_G is served by a chain_block of this launch)
-    const bool runnable = phw != 0 && !(c.chain && (phw == PH_W_LS_G || phw == PH_W_LS_C + chain_tag(par)));
-    const unsigned long long act = __ballot(runnable);
-    const int rank = __popcll(act & ((1ull << lane) - 1ull));
-    const int nact = __popcll(act);
-    if (threadIdx.x == 0) s_next = 0;
-    if (wv == 0) s_req[lane] = REQ_NONE;
-    __syncthreads();
-    // the waves take the running agents from a shared counter, one ahead of the one they work on (its
-    // rows are in flight meanwhile): an agent-step costs between ~0.3 and ~3 us depending on its phase,
-    // and a static deal leaves three waves waiting for the unlucky one
-    auto claim = [&]() -> int {
-        int i = 0;
-        if (lane == 0) i = atomicAdd(&s_next, 1);
-        i = __builtin_amdgcn_readfirstlane(i);
-        if (i >= nact) return -1;
-        return (int)__builtin_ctzll(__ballot(runnable && rank == i));
-    };
-    AgentIn<NE> nxt;
-    int loc = claim();
-    // (MPC_ALL_ROWS: the six-row fetch of rounds 1 - 2, for the A/B measurement and the bit-identity test)
-    const auto phase_of = [&](const DevCfg &cc, int l) { return cc.all_rows ? -1 : (__builtin_amdgcn_readlane(phw, l) & PH_MASK); };
-    if (loc >= 0) nxt = load_agent<NE>(c, w, base + loc, lane, phase_of(c, loc));
-    while (loc >= 0) {
-        // (the kernel's parameters c and w are not used inside this loop: see KernArgs)
-        const KernArgs ka;
-        const DevCfg &c = ka.c();
-        const Workspace &w = ka.w();
-        const int a = base + loc;
-        const AgentIn<NE> cur = nxt;
-        const int loc_next = claim();
-        if (loc_next >= 0) nxt = load_agent<NE>(c, w, base + loc_next, lane, phase_of(c, loc_next)); // in flight during agent a
-        bool hist_ready = false;
-        if (MC < 0) {
-            // An agent that comes back from its Hessian-vector evaluation (or from the cost of a trial
-            // whose speculative gradient is there) runs the two-loop almost first thing: start the
-            // LDS-DMA of its history now.  Issued BEHIND the next agent's row loads: the wait for the
-            // history drains the wave's vector-memory queue in order, so nothing younger than what it
-            // needs should be in it.
-            const int rlo = __double2loint(cur.rv);      // (the integers of the record: rec_int)
-            const int ph = __builtin_amdgcn_readlane(rlo, R_PHASE) & PH_MASK;
-            const int hi = __builtin_amdgcn_readlane(rlo, R_LIDX), hf = __builtin_amdgcn_readlane(rlo, R_LFULL);
-            const int hl = hi | hf;
-            const int sp = __builtin_amdgcn_readlane(rlo, R_SPEC);
-            if ((ph == PH_W_HESS || (ph == PH_W_LS_C && sp != 0)) && hl != 0) {
-                hist_dma(w.S + (size_t)a * c.M * c.n, w.Y + (size_t)a * c.M * c.n, hist, P * c.n,
-                         (hf ? c.M : hi) * c.n, lane);
-                hist_ready = true;
-            }
-        }
-#if MPC_DEV_STAMP == 3
-        stamp.nfall++;                                   // agent-steps of this wave
-        const long long tv0 = __builtin_amdgcn_s_memrealtime();
-        const int ph_in = __builtin_amdgcn_readlane(__double2loint(cur.rv), R_PHASE) & PH_MASK;
-#endif
-        const int req = advance_agent<NE, MC, HASM, true>(c, w, a, lane, cur, hist, hist_ready, true, /*allow_chain=*/true, P);
-#if MPC_DEV_STAMP == 3
-        {   // the longest agent-step of this wave: its length in 10 ns ticks (nmid, capped at 255) and the phase it came in with (nslow)
-            const int dt = (int)(__builtin_amdgcn_s_memrealtime() - tv0);
-            if (dt > stamp.nmid) { stamp.nmid = dt > 255 ? 255 : dt; stamp.nslow = ph_in; }
-        }
-#endif
-        if (lane == 0) s_req[loc] = req;
-        loc = loc_next;
-    }
-    __syncthreads();
-    if (wv == 0) {
-        const int r = s_req[lane];
-#pragma unroll
-        for (int kind = 0; kind < 2; kind++) { // 0: gradient list (normal or channel 2), 1: cost list
-            const bool on = kind == 0 ? (r & (REQ_GRAD | REQ_SPEC)) != 0 : (r & REQ_COST) != 0;
-            const unsigned long long bal = __ballot(on);
-            const int cnt = __popcll(bal);
-            if (cnt == 0) continue;                      // uniform
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&counts_out[kind], cnt);
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (on) {
-                const int off = __popcll(bal & ((1ull << lane) - 1ull));
-                const int flag = kind == 0 ? ((r & REQ_SPEC) ? CH2_BIT : 0) | ((r & REQ_CHAIN) ? CHAIN_BIT : 0) : 0;
-                lists_out[(size_t)kind * w.Ls + base + off] = (blockIdx.x * apb + lane) | flag;
-            }
-        }
-    }
+#define MPC_STEP_BA false
+#define MPC_STEP_BT BoxTab{nullptr, nullptr}
+#include "mpc_step_body.hpp"
+#undef MPC_STEP_BA
+#undef MPC_STEP_BT
+}
+// ... with every agent's own input box (mpc_set_agent_bounds): same body, same occupancy targets, same LDS plan
+template <int NE, int MC, bool HASM>
+__global__ void __launch_bounds__(64 * STEP_WAVES, step_waves_per_simd(NE, MC, HASM))
+step_kernel_box(const DevCfg c, const Workspace w, const BoxTab bt, int *__restrict__ lists_out,
+                int *__restrict__ counts_out, int *__restrict__ counts_next, int apb, int nstep, int par, int P)
+{
+#define MPC_STEP_BA true
+#define MPC_STEP_BT bt
+#include "mpc_step_body.hpp"
+#undef MPC_STEP_BA
+#undef MPC_STEP_BT
 }
 
 // solver state initialisation for a fresh solve (ALMSolver::operator() prologue)

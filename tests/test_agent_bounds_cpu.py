@@ -1,0 +1,174 @@
+"""CPU tests of the per-agent bounds table (mpc_set_agent_bounds): the header declares it, the library exports it, the
+default row is the configuration's box, the host-side table builder puts overrides in the documented columns, the
+front ends carry the new entry points, and the code object holds the per-agent-box form of every step kernel with the
+resources and the argument layout the shared form has.  No compute call is made here."""
+import ctypes as C
+import inspect
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+import model_predictive_control_amd as mp
+from model_predictive_control_amd import _lib
+
+STEP_BOX = "_ZN3mpc15step_kernel_boxI"            # every per-agent-box step kernel
+STEP_BOX_LEAN = STEP_BOX + "Li1ELin1ELb0EEE"      # step_kernel_box<1, -1, false>: the benchmark problem's
+STEP_LDS_BYTES = 264                              # s_req[64] + s_next (+ padding), as the shared kernel
+LEAN_WAVES_PER_SIMD = 5                           # the shared lean kernel's target, and this one's
+
+
+@pytest.fixture(scope="module")
+def L():
+    _lib.build()
+    return _lib.load()
+
+
+def test_header_declares_and_library_exports_the_bounds_api(L):
+    hdr = open(os.path.join(ROOT, "include", "mpc_hip.h")).read()
+    assert re.search(r"#define\s+MPC_NBOUND\s+4\b", hdr)
+    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    assert re.search(r"\bint\s+mpc_default_bounds\s*\(\s*const\s+mpc_config\s*\*\s*\w+\s*,\s*double\s*\*\s*\w+\s*\)", code)
+    assert re.search(r"\bint\s+mpc_set_agent_bounds\s*\(\s*mpc_handle\s*\*\s*\w+\s*,\s*const\s+double\s*\*\s*\w+\s*,\s*int\s+\w+\s*,"
+                     r"\s*const\s+int32_t\s*\*\s*\w+\s*,\s*int\s+\w+\s*\)", code)
+    for name in ("mpc_default_bounds", "mpc_set_agent_bounds"):
+        assert hasattr(L, name) and name in _lib.EXPORTS
+    assert _lib.NBOUND == 4 and mp.NBOUND == 4
+    assert len(L.mpc_default_bounds.argtypes) == 2 and len(L.mpc_set_agent_bounds.argtypes) == 5
+    assert L.mpc_set_agent_bounds.argtypes[2] is C.c_int and L.mpc_set_agent_bounds.argtypes[4] is C.c_int
+
+
+@pytest.mark.parametrize("model", [0, 1])
+def test_default_row_is_the_configurations_box(L, O, model):
+    N = 12 if model else 20
+    row = _lib.default_bounds(mp.default_config(model, N))
+    ocfg = O.default_config(model, N)
+    assert row.shape == (4,) and row.dtype == np.float64
+    assert list(row) == [ocfg.u_lb[0], ocfg.u_lb[1], ocfg.u_ub[0], ocfg.u_ub[1]] == [-1.0, -0.32, 1.0, 0.32]
+    cfg = mp.default_config(model, N, u_lb=[-0.6, -0.11], u_ub=[0.7, float("inf")])
+    assert list(_lib.default_bounds(cfg)) == [-0.6, -0.11, 0.7, float("inf")]
+
+
+def test_null_arguments_return_codes_not_exceptions(L):
+    E_ARG = -1
+    row = (C.c_double * 4)()
+    cfg = mp.default_config(0, 20)
+    assert L.mpc_default_bounds(None, row) == E_ARG and b"mpc_default_bounds" in L.mpc_last_error()
+    assert L.mpc_default_bounds(C.byref(cfg), None) == E_ARG
+    assert L.mpc_default_bounds(C.byref(cfg), row) == 0
+    assert L.mpc_set_agent_bounds(None, None, 0, None, 0) == E_ARG
+    assert b"mpc_set_agent_bounds" in L.mpc_last_error()
+    assert L.mpc_set_agent_bounds(None, C.c_void_p(8), 1, C.c_void_p(8), 1) == E_ARG   # (nothing is dereferenced)
+    assert L.mpc_set_agent_bounds(None, C.c_void_p(8), 1, None, 1) == E_ARG
+
+
+def test_bound_rows(L):
+    cfg = mp.default_config(1, 12, u_lb=[-0.9, -0.3], u_ub=[0.8, 0.25])
+    base = _lib.default_bounds(cfg)
+    assert list(base) == [-0.9, -0.3, 0.8, 0.25]
+    P = 5
+    tab = _lib.bound_rows(cfg, P)
+    assert tab.shape == (P, 4) and tab.dtype == np.float64 and tab.flags["C_CONTIGUOUS"]
+    assert all(np.array_equal(tab[p], base) for p in range(P))
+    rng = np.random.default_rng(0)
+    lb = -rng.uniform(.1, 1, (P, 2)); ub = rng.uniform(.1, 1, (P, 2))
+    tab = _lib.bound_rows(cfg, P, u_lb=lb, u_ub=ub)
+    assert np.array_equal(tab[:, 0:2], lb) and np.array_equal(tab[:, 2:4], ub)
+    tab = _lib.bound_rows(cfg, 3, u_ub=[0.5, 0.2])
+    assert np.array_equal(tab, np.tile([-0.9, -0.3, 0.5, 0.2], (3, 1)))
+    assert mp.bound_rows is _lib.bound_rows and mp.default_bounds is _lib.default_bounds
+    for bad in (dict(u_lb=np.zeros((P, 3))), dict(u_ub=np.zeros((P + 1, 2))), dict(u_lb=np.zeros(3))):
+        with pytest.raises(ValueError):
+            _lib.bound_rows(cfg, P, **bad)
+    with pytest.raises(ValueError):
+        _lib.bound_rows(cfg, 0)
+
+
+def test_front_ends_carry_the_new_entry_points():
+    from model_predictive_control_amd.controller import MPCController
+    for name in ("set_agent_bounds", "clear_agent_bounds"):
+        assert callable(getattr(mp.BatchedMPC, name))
+    assert isinstance(inspect.getattr_static(mp.BatchedMPC, "agent_bounds_bound"), property)
+    assert list(inspect.signature(mp.BatchedMPC.set_agent_bounds).parameters) == ["self", "table", "index"]
+    for fn in (MPCController.solve, MPCController.step):
+        par = inspect.signature(fn).parameters
+        assert "bounds" in par and "bound_index" in par
+        assert par["bounds"].default is None and par["bound_index"].default is None
+        assert "params" in par and "param_index" in par
+    code = ("import sys; sys.path.insert(0, %r); import model_predictive_control_amd as mp; "
+            "from model_predictive_control_amd import controller; "
+            "assert not any('oracle' in m for m in sys.modules), 'oracle imported'; "
+            "assert mp.bound_rows(mp.default_config(0, 20), 2).shape == (2, 4)" % ROOT)
+    subprocess.check_call([sys.executable, "-c", code])
+
+
+# ------------------------------------------------------------------ the code object (read as test_step_kernel_occupancy.py reads it)
+def _tool(name):
+    p = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", name)
+    return p if os.access(p, os.X_OK) else shutil.which(name)
+
+
+@pytest.fixture(scope="module")
+def kernels(tmp_path_factory):
+    yaml = pytest.importorskip("yaml")
+    tools = {n: _tool(n) for n in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")}
+    missing = [n for n, p in tools.items() if p is None]
+    if missing:
+        pytest.skip("needs " + ", ".join(missing))
+    _lib.build()
+    d = tmp_path_factory.mktemp("codeobj")
+    fatbin, co = str(d / "fatbin.bin"), str(d / "gfx950.o")
+    subprocess.check_call([tools["llvm-objcopy"], "--dump-section=.hip_fatbin=" + fatbin, _lib.LIB_PATH, str(d / "x")])
+    subprocess.check_call([tools["clang-offload-bundler"], "--unbundle", "--type=o", "--input=" + fatbin,
+                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
+    notes = subprocess.check_output([tools["llvm-readelf"], "--notes", co], text=True)
+    doc = notes[notes.index("---"):notes.index("\n...", notes.index("---"))]
+    meta = yaml.safe_load(doc)
+    return {k[".name"]: k for k in meta["amdhsa.kernels"]}
+
+
+def _waves_by_vgprs(vgprs):
+    return 512 // (-(-vgprs // 8) * 8)
+
+
+def test_lean_box_step_kernel_fits_the_shared_kernels_target(L, kernels):
+    lean = [k for n, k in kernels.items() if n.startswith(STEP_BOX_LEAN)]
+    assert len(lean) == 1
+    k = lean[0]
+    assert k[".sgpr_spill_count"] == 0
+    assert k[".vgpr_spill_count"] == 0
+    assert k[".private_segment_fixed_size"] == 0
+    assert k[".group_segment_fixed_size"] == STEP_LDS_BYTES
+    assert k[".vgpr_count"] <= 512 // LEAN_WAVES_PER_SIMD // 8 * 8          # 96
+    assert _waves_by_vgprs(k[".vgpr_count"] + k.get(".agpr_count", 0)) >= LEAN_WAVES_PER_SIMD
+    assert k[".max_flat_workgroup_size"] == 256
+    # ... which is what the host sizes the LDS copy of the history for (the plan has no box form of its own)
+    for n, M in ((24, 12), (40, 20)):
+        P, lds, wps = C.c_int(), C.c_int(), C.c_int()
+        assert L.mpc_step_lds_plan(n, M, 0, 1, 0, C.byref(P), C.byref(lds), C.byref(wps)) == 0
+        assert wps.value == LEAN_WAVES_PER_SIMD
+
+
+def test_every_step_kernel_has_a_box_form_with_the_shared_argument_layout(kernels):
+    shared = sorted(n for n in kernels if n.startswith("_ZN3mpc11step_kernelI"))
+    box = sorted(n for n in kernels if n.startswith(STEP_BOX))
+    assert len(shared) == 8 and len(box) == 8
+    # the same eight <NE, MC, HASM>
+    targs = lambda n, pre: n[len(pre):n.index("EEE") + 3]
+    assert [targs(n, "_ZN3mpc11step_kernelI") for n in shared] == [targs(n, STEP_BOX) for n in box]
+    for sn, bn in zip(shared, box):
+        s, k = kernels[sn], kernels[bn]
+        cfg, ws, bt = k[".args"][0], k[".args"][1], k[".args"][2]
+        assert cfg[".value_kind"] == ws[".value_kind"] == bt[".value_kind"] == "by_value"
+        assert cfg[".offset"] == 0 and cfg[".size"] % 8 == 0
+        assert ws[".offset"] == cfg[".size"]                                  # KernArgs::W_OFF
+        assert (cfg[".size"], ws[".size"]) == (s[".args"][0][".size"], s[".args"][1][".size"])
+        assert bt[".offset"] == ws[".offset"] + ws[".size"] and bt[".size"] == 16   # KernArgs::B_OFF: two pointers
+        assert k[".group_segment_fixed_size"] == s[".group_segment_fixed_size"]
+        assert k[".private_segment_fixed_size"] == 0 and k[".vgpr_spill_count"] == 0
