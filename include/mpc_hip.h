@@ -139,6 +139,28 @@ int mpc_set_agent_params(mpc_handle *h, const double *table, int P, const int32_
 int mpc_default_bounds(const mpc_config *cfg, double *row);
 int mpc_set_agent_bounds(mpc_handle *h, const double *table, int P, const int32_t *index, int B);
 
+/* Per-agent constraint data: a table of P rows in device memory and one row index per agent, beside the two tables above.
+ * One row, all doubles: [0..5] g_off, [6..11] D_lb, [12..17] D_ub, [18] lane_halfwidth -- the data of the general
+ * constraints (main.py:43-52 `g_i = x_i^2 - g_off[i]` within `[D_lb[i], D_ub[i]]`; the lane band `|signed distance| <=
+ * lane_halfwidth`).  Only the fields of the handle's constr_mode are read: MPC_CONSTR_STATE_SQ reads the first nx entries
+ * of the three vectors, MPC_CONSTR_LANE reads [18].
+ * mpc_default_constraints (host only): the row `cfg` describes.
+ * mpc_set_agent_constraints: table == NULL unbinds (the handle is then what it was before).  Bound, the calls that read
+ * constraint data -- mpc_eval_cost_grad, mpc_eval_cost_grad_wave, mpc_solve_batch(_async), mpc_solve_active,
+ * mpc_closed_loop(_event) -- use row index[b] for agent b and return MPC_E_ARG for a batch size other than B; no other
+ * entry point reads constraint data.  constr_mode, m, N, Ts, the input box and every ALM and PANOC parameter (Sigma0,
+ * alm_delta, M, ...) stay the handle's.  The table is independent of the other two: any subset of the three may be
+ * bound; bound together they are for the same B (MPC_E_ARG otherwise), each with its own index.  table [P][MPC_NCONSTR]
+ * and index [B] are DEVICE memory of the caller, read at every call: rows may be rewritten in place between calls
+ * without binding again.  The P rows are checked once, at bind time, through a synchronous copy: D_lb[i] <= D_ub[i] for
+ * i < nx (a NaN fails it, infinities pass) and g_off finite (MPC_CONSTR_STATE_SQ); lane_halfwidth finite and > 0
+ * (MPC_CONSTR_LANE); mpc_create itself checks neither.  Index ranges are the caller's to check (the Python front end
+ * does).  Refused (MPC_E_ARG) while an asynchronous solve is in flight, and on a handle with MPC_CONSTR_NONE: there is
+ * nothing to bind to.  A table whose rows equal the handle's values gives the bits of the call without a table. */
+#define MPC_NCONSTR 19
+int mpc_default_constraints(const mpc_config *cfg, double *row);
+int mpc_set_agent_constraints(mpc_handle *h, const double *table, int P, const int32_t *index, int B);
+
 /* a-1 (car_dynamics.py:93-132 / dynamics.py:67-119,:144-173): dx[B][nx] = f(x[B][nx], u[B][2]) */
 int mpc_rhs(mpc_handle *h, int B, const double *x, const double *u, double *dx, void *stream);
 

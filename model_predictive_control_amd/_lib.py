@@ -52,11 +52,15 @@ EXPORTS = [
     "mpc_last_lookahead", "mpc_step_lds_plan", "mpc_default_params", "mpc_set_agent_params",
     "mpc_solve_active", "mpc_trigger_eval", "mpc_closed_loop_event",
     "mpc_default_bounds", "mpc_set_agent_bounds",
+    "mpc_default_constraints", "mpc_set_agent_constraints",
 ]
 NREC = 64
 NPARAM = 31     # MPC_NPARAM: doubles per row of the per-agent parameter table
 # columns of a row, by field name (include/mpc_hip.h: mpc_set_agent_params)
 NBOUND = 4      # MPC_NBOUND: doubles per row of the per-agent bounds table, [u_lb[0], u_lb[1], u_ub[0], u_ub[1]]
+NCONSTR = 19    # MPC_NCONSTR: doubles per row of the per-agent constraint table
+# columns of a constraint row, by field name (include/mpc_hip.h: mpc_set_agent_constraints)
+CONSTR_FIELDS = {"g_off": (0, 6), "D_lb": (6, 6), "D_ub": (12, 6), "lane_halfwidth": (18, 1)}
 PARAM_FIELDS = {"veh": (0, 22), "accel": (22, 1), "friction": (23, 1), "v_ref": (24, 1), "cost_w": (25, 6)}
 
 
@@ -155,6 +159,8 @@ def load():
     L.mpc_set_agent_params.argtypes = [vp, vp, ci, vp, vp, ci]
     L.mpc_default_bounds.argtypes = [cp, C.POINTER(C.c_double)]
     L.mpc_set_agent_bounds.argtypes = [vp, vp, ci, vp, ci]
+    L.mpc_default_constraints.argtypes = [cp, C.POINTER(C.c_double)]
+    L.mpc_set_agent_constraints.argtypes = [vp, vp, ci, vp, ci]
     L.mpc_step_lds_plan.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     L.mpc_math_probe.argtypes = [vp, ci, ci, vp, vp, vp, vp]
     L.mpc_lane_payoff.argtypes = [vp, ci, ci, C.POINTER(C.c_double), vp, vp, vp, vp, vp]
@@ -264,6 +270,46 @@ def bound_rows(cfg, P, u_lb=None, u_ub=None):
         if v.shape != (P, 2):
             raise ValueError(f"bound_rows: {name} must have shape (2,) or ({P}, 2), got {v.shape}")
         tab[:, off:off + 2] = v
+    return tab
+
+
+def default_constraints(cfg):
+    """mpc_default_constraints: the row of the per-agent constraint table that `cfg` describes, float64 [NCONSTR]."""
+    import numpy as np
+    row = (C.c_double * NCONSTR)()
+    rc = load().mpc_default_constraints(C.byref(cfg), row)
+    if rc != 0:
+        raise ValueError(load().mpc_last_error().decode())
+    return np.array(row[:], dtype=np.float64)
+
+
+def constraint_rows(cfg, P, g_off=None, D_lb=None, D_ub=None, lane_halfwidth=None):
+    """A constraint table for BatchedMPC.set_agent_constraints, on the host: float64 [P, NCONSTR] whose rows are
+    default_constraints(cfg) with `g_off` / `D_lb` / `D_ub` [P, k] (or [k]: every row; k = nx or 6 leading entries) and
+    `lane_halfwidth` [P] (or a scalar) in their place.  Pure host code: usable without a GPU."""
+    import numpy as np
+    P = int(P)
+    if P < 1:
+        raise ValueError("constraint_rows: P must be >= 1")
+    tab = np.tile(default_constraints(cfg), (P, 1))
+    nx = 6 if cfg.model == MODEL_PACEJKA else 4
+    for name, val in (("g_off", g_off), ("D_lb", D_lb), ("D_ub", D_ub)):
+        if val is None:
+            continue
+        off = CONSTR_FIELDS[name][0]
+        v = np.asarray(val, dtype=np.float64)
+        if v.ndim == 1:
+            v = np.tile(v, (P, 1))
+        if v.ndim != 2 or v.shape[0] != P or v.shape[1] not in (nx, 6):
+            raise ValueError(f"constraint_rows: {name} must have shape ({nx},), (6,), ({P}, {nx}) or ({P}, 6), got {np.shape(val)}")
+        tab[:, off:off + v.shape[1]] = v
+    if lane_halfwidth is not None:
+        v = np.asarray(lane_halfwidth, dtype=np.float64)
+        if v.ndim == 0:
+            v = np.full(P, float(v))
+        if v.shape != (P,):
+            raise ValueError(f"constraint_rows: lane_halfwidth must be a scalar or have shape ({P},), got {v.shape}")
+        tab[:, CONSTR_FIELDS["lane_halfwidth"][0]] = v
     return tab
 
 

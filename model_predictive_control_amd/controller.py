@@ -103,12 +103,14 @@ class MPCController:
 
     # ------------------------------------------------------------------ batched entry points
     def solve(self, Y0, centerline, U0=None, lam0=None, cl_index=None, params=None, param_index=None,
-              bounds=None, bound_index=None):
+              bounds=None, bound_index=None, constraints=None, constraint_index=None):
         """Batched solve: Y0 [B, nx], centerline [2S] or [C, 2S] (+ cl_index[B]) -> (U [B, 2N], stats).
         params [P, 31] (rows as _lib.param_rows makes them) + param_index [B] (None: agent b uses row b % P): this
         solve runs agent b on its own vehicle and cost parameters (BatchedMPC.set_agent_params).
         bounds [P', 4] (rows as _lib.bound_rows makes them) + bound_index [B] (None: agent b uses row b % P'): this solve
-        projects agent b's inputs onto its own box (BatchedMPC.set_agent_bounds)."""
+        projects agent b's inputs onto its own box (BatchedMPC.set_agent_bounds).
+        constraints [P", 19] (rows as _lib.constraint_rows makes them) + constraint_index [B] (None: agent b uses row
+        b % P"): this solve holds agent b to its own constraint data (BatchedMPC.set_agent_constraints)."""
         dev = self.device
         Y0 = torch.as_tensor(Y0, dtype=torch.float64, device=dev).contiguous()
         B = Y0.shape[0]
@@ -135,26 +137,38 @@ class MPCController:
             if bound_index is None:
                 bound_index = torch.arange(B, device=dev) % bounds.shape[0]
             bound_index = torch.as_tensor(bound_index, device=dev).to(torch.int32).contiguous()
+        if constraints is None and constraint_index is not None:
+            raise ValueError("constraint_index needs constraints")
+        if constraints is not None:
+            constraints = torch.as_tensor(constraints, dtype=torch.float64, device=dev).contiguous()
+            if constraint_index is None:
+                constraint_index = torch.arange(B, device=dev) % constraints.shape[0]
+            constraint_index = torch.as_tensor(constraint_index, device=dev).to(torch.int32).contiguous()
         try:
             if params is not None:
                 self.solver.set_agent_params(params, param_index)
             if bounds is not None:
                 self.solver.set_agent_bounds(bounds, bound_index)
+            if constraints is not None:
+                self.solver.set_agent_constraints(constraints, constraint_index)
             U, lam, stats = self.solver.solve(Y0, cl, U0, lam0 if self._constrained else None, cl_index)
         finally:
             if params is not None:
                 self.solver.clear_agent_params()
             if bounds is not None:
                 self.solver.clear_agent_bounds()
+            if constraints is not None:
+                self.solver.clear_agent_constraints()
         self.last_stats = stats
         self.tot_it += int(stats[:, 2].sum().item())
         self.failures += int((stats[:, 0] != _lib.ST_CONVERGED).sum().item())
         return U, stats
 
     def step(self, Y0, centerline, U0=None, lam0=None, cl_index=None, params=None, param_index=None,
-             bounds=None, bound_index=None):
+             bounds=None, bound_index=None, constraints=None, constraint_index=None):
         """First control of every agent, u0 [B, 2] (main.py:141 input_to_matrix(U)[:, 0])."""
-        U, _ = self.solve(Y0, centerline, U0, lam0, cl_index, params, param_index, bounds, bound_index)
+        U, _ = self.solve(Y0, centerline, U0, lam0, cl_index, params, param_index, bounds, bound_index,
+                          constraints, constraint_index)
         return U[:, :2].contiguous()
 
 

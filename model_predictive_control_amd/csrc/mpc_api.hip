@@ -70,6 +70,15 @@ extern "C" int mpc_default_bounds(const mpc_config *c, double *row)
     return MPC_OK;
 }
 
+static_assert(MPC_NCONSTR == mpc::NCONSTR, "row layout: include/mpc_hip.h and mpc_device.hpp");
+extern "C" int mpc_default_constraints(const mpc_config *c, double *row)
+{
+    if (!c || !row) return fail(MPC_E_ARG, "mpc_default_constraints: null argument");
+    for (int i = 0; i < 6; i++) { row[i] = c->g_off[i]; row[6 + i] = c->D_lb[i]; row[12 + i] = c->D_ub[i]; }
+    row[18] = c->lane_halfwidth;
+    return MPC_OK;
+}
+
 extern "C" int mpc_create(const mpc_config *cfg, int device, mpc_handle **out)
 {
     if (!cfg || !out) return fail(MPC_E_ARG, "mpc_create: null argument");
@@ -170,8 +179,7 @@ extern "C" int mpc_set_agent_params(mpc_handle *h, const double *table, int P, c
     { const int rb = refuse_if_busy(h, "mpc_set_agent_params"); if (rb) return rb; }
     if (!table) { h->ptab = nullptr; h->pidx = h->pidx_plant = nullptr; h->ptab_rows = h->ptab_B = 0; return MPC_OK; }
     if (P < 1 || B < 1 || !index) return fail(MPC_E_ARG, "mpc_set_agent_params: need P >= 1 rows, B >= 1 agents and an index");
-    if (h->btab && B != h->btab_B)
-        return fail(MPC_E_ARG, "mpc_set_agent_params: the bound bounds table is for a batch of " + std::to_string(h->btab_B) + " agents");
+    { const int ra = check_tables_agree(h, B, "mpc_set_agent_params", 0); if (ra) return ra; }
     HIPCHK(hipSetDevice(h->device));
     std::vector<double> rows((size_t)P * MPC_NPARAM);
     HIPCHK(hipMemcpy(rows.data(), table, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -189,6 +197,26 @@ extern "C" int mpc_set_agent_params(mpc_handle *h, const double *table, int P, c
     return MPC_OK;
 }
 
+// the handle's own one-row parameter and box tables and an index of B zeros (see mpc_handle::own_ptab)
+static int reserve_own_tables(mpc_handle *h, int B, const char *who)
+{
+    if (B <= h->own_cap) return MPC_OK;
+    if (h->own_ptab) { HIPCHK(hipFree(h->own_ptab)); h->own_ptab = h->own_btab = nullptr; h->own_pidx = nullptr; h->own_cap = 0; }
+    const size_t cap = ((size_t)B + 63) & ~(size_t)63;
+    constexpr int ND = MPC_NPARAM + 1 + MPC_NBOUND;
+    char *base = nullptr;
+    if (hipMalloc((void **)&base, sizeof(double) * ND + sizeof(int32_t) * cap) != hipSuccess)
+        return fail(MPC_E_ALLOC, std::string(who) + ": hipMalloc failed");
+    double own[ND] = {0};
+    (void)mpc_default_params(&h->cfg, own);
+    (void)mpc_default_bounds(&h->cfg, own + MPC_NPARAM + 1);
+    h->own_ptab = (double *)base; h->own_btab = h->own_ptab + MPC_NPARAM + 1;
+    h->own_pidx = (int32_t *)(base + sizeof(double) * ND); h->own_cap = (int)cap;
+    HIPCHK(hipMemcpy(base, own, sizeof own, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(h->own_pidx, 0, sizeof(int32_t) * cap));
+    return MPC_OK;
+}
+
 // Binds (table != NULL) or unbinds the per-agent table of input boxes, as mpc_set_agent_params binds the parameter
 // table: the rows are checked once, here, through a synchronous copy, by the rule mpc_create applies to the handle's
 // box; the kernels read the caller's memory at every call.
@@ -197,28 +225,46 @@ extern "C" int mpc_set_agent_bounds(mpc_handle *h, const double *table, int P, c
     { const int rb = refuse_if_busy(h, "mpc_set_agent_bounds"); if (rb) return rb; }
     if (!table) { h->btab = nullptr; h->bidx = nullptr; h->btab_rows = h->btab_B = 0; return MPC_OK; }
     if (P < 1 || B < 1 || !index) return fail(MPC_E_ARG, "mpc_set_agent_bounds: need P >= 1 rows, B >= 1 agents and an index");
-    if (h->ptab && B != h->ptab_B)
-        return fail(MPC_E_ARG, "mpc_set_agent_bounds: the bound parameter table is for a batch of " + std::to_string(h->ptab_B) + " agents");
+    { const int ra = check_tables_agree(h, B, "mpc_set_agent_bounds", 1); if (ra) return ra; }
     HIPCHK(hipSetDevice(h->device));
     std::vector<double> rows((size_t)P * MPC_NBOUND);
     HIPCHK(hipMemcpy(rows.data(), table, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (int p = 0; p < P; p++)
         if (!box_ok(rows.data() + (size_t)p * MPC_NBOUND, rows.data() + (size_t)p * MPC_NBOUND + 2))
             return fail(MPC_E_ARG, "mpc_set_agent_bounds: row " + std::to_string(p) + ": u_lb must not exceed u_ub");
-    // the handle's own one-row parameter table and an index of B zeros (see mpc_handle::own_ptab)
-    if (B > h->own_cap) {
-        if (h->own_ptab) { HIPCHK(hipFree(h->own_ptab)); h->own_ptab = nullptr; h->own_pidx = nullptr; h->own_cap = 0; }
-        const size_t cap = ((size_t)B + 63) & ~(size_t)63;
-        char *base = nullptr;
-        if (hipMalloc((void **)&base, sizeof(double) * MPC_NPARAM + 8 + sizeof(int32_t) * cap) != hipSuccess)
-            return fail(MPC_E_ALLOC, "mpc_set_agent_bounds: hipMalloc failed");
-        double own[MPC_NPARAM + 1] = {0};
-        (void)mpc_default_params(&h->cfg, own);
-        h->own_ptab = (double *)base; h->own_pidx = (int32_t *)(base + sizeof(double) * (MPC_NPARAM + 1)); h->own_cap = (int)cap;
-        HIPCHK(hipMemcpy(base, own, sizeof own, hipMemcpyHostToDevice));
-        HIPCHK(hipMemset(h->own_pidx, 0, sizeof(int32_t) * cap));
-    }
+    { const int ro = reserve_own_tables(h, B, "mpc_set_agent_bounds"); if (ro) return ro; }
     h->btab = table; h->btab_rows = P; h->bidx = index; h->btab_B = B;
+    return MPC_OK;
+}
+
+// Binds (table != NULL) or unbinds the per-agent table of constraint data, as mpc_set_agent_bounds binds the boxes: the
+// rows are checked once, here, through a synchronous copy; the kernels read the caller's memory at every call.
+extern "C" int mpc_set_agent_constraints(mpc_handle *h, const double *table, int P, const int32_t *index, int B)
+{
+    { const int rb = refuse_if_busy(h, "mpc_set_agent_constraints"); if (rb) return rb; }
+    if (!table) { h->ctab = nullptr; h->cidx = nullptr; h->ctab_rows = h->ctab_B = 0; return MPC_OK; }
+    if (h->cfg.constr_mode == MPC_CONSTR_NONE)
+        return fail(MPC_E_ARG, "mpc_set_agent_constraints: the handle has no general constraints (constr_mode MPC_CONSTR_NONE)");
+    if (P < 1 || B < 1 || !index) return fail(MPC_E_ARG, "mpc_set_agent_constraints: need P >= 1 rows, B >= 1 agents and an index");
+    { const int ra = check_tables_agree(h, B, "mpc_set_agent_constraints", 2); if (ra) return ra; }
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<double> rows((size_t)P * MPC_NCONSTR);
+    HIPCHK(hipMemcpy(rows.data(), table, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const int nx = mpc_nx(&h->cfg);
+    for (int p = 0; p < P; p++) {
+        const double *r = rows.data() + (size_t)p * MPC_NCONSTR;
+        const std::string where = "mpc_set_agent_constraints: row " + std::to_string(p);
+        if (h->cfg.constr_mode == MPC_CONSTR_LANE) {
+            if (!std::isfinite(r[18]) || !(r[18] > 0.0)) return fail(MPC_E_ARG, where + ": lane_halfwidth must be finite and positive");
+            continue;
+        }
+        for (int i = 0; i < nx; i++) {
+            if (!std::isfinite(r[i])) return fail(MPC_E_ARG, where + ": g_off[" + std::to_string(i) + "] is not finite");
+            if (!(r[6 + i] <= r[12 + i])) return fail(MPC_E_ARG, where + ": D_lb must not exceed D_ub");
+        }
+    }
+    { const int ro = reserve_own_tables(h, B, "mpc_set_agent_constraints"); if (ro) return ro; }
+    h->ctab = table; h->ctab_rows = P; h->cidx = index; h->ctab_B = B;
     return MPC_OK;
 }
 
@@ -315,6 +361,7 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     const DevCfg &c = h->dc;
     if (c.m && (!y || !Sigma)) return fail(MPC_E_ARG, "mpc_eval_cost_grad: y and Sigma are required when m > 0");
     rc = check_bound(h, B, "mpc_eval_cost_grad"); if (rc) return rc;
+    rc = check_con_bound(h, B, "mpc_eval_cost_grad"); if (rc) return rc;
     rc = reserve(h, B); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     // direct mode: the kernel reads and writes the caller's agent-major buffers in place
@@ -325,6 +372,7 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     w.yhe = (yhat && c.m) ? yhat : h->ws.ws_yhe;
     w.psi_direct = psi;
     w.ptab = h->ptab; w.pidx = h->pidx;
+    w.ctab = h->ctab; w.cidx = h->cidx;
     if (wave_path) launch_solo_eval(h, w, s, grad ? 1 : 0);
     else launch_eval(h, w, s, nullptr, nullptr, grad ? B : 0, grad ? 0 : B);
     HIPCHK(hipGetLastError());
@@ -386,10 +434,10 @@ extern "C" int mpc_step_lds_plan(int n, int M, int m, int chain, int lds_pairs, 
 }
 
 // the solve proper on B agents whose parameter rows (table bound) are pidx[b] and whose boxes (bounds table bound) are
-// rows bidx[b]: the caller's batch and the handle's bound indices (mpc_solve_batch), or the gathered rows of a masked
-// solve and their gathered indices
+// rows bidx[b] and whose constraint data (constraint table bound) are rows cidx[b]: the caller's batch and the handle's
+// bound indices (mpc_solve_batch), or the gathered rows of a masked solve and their gathered indices
 static int solve_core(mpc_handle *h, int B, const double *x0, const double *cl, const int32_t *cl_index, const int32_t *pidx,
-                      const int32_t *bidx, double *U, double *lambda, double *stats, hipStream_t s)
+                      const int32_t *bidx, const int32_t *cidx, double *U, double *lambda, double *stats, hipStream_t s)
 {
     int rc = reserve(h, B); if (rc) return rc;
     WorkspaceHost &w = h->ws;
@@ -397,6 +445,7 @@ static int solve_core(mpc_handle *h, int B, const double *x0, const double *cl, 
     w.near = near_for(h, cl);
     w.ptab = h->ptab; w.pidx = pidx;
     w.btab = h->btab; w.bidx = h->btab ? bidx : nullptr;
+    w.ctab = h->ctab; w.cidx = h->ctab ? cidx : nullptr;
     w.xe = w.ws_xe; w.ge = w.ws_ge; w.yhe = w.ws_yhe; w.Sig = w.ws_Sig;
     rc = run_solver(h, s); if (rc) return rc;
     if (stats) hipLaunchKernelGGL(stats_kernel, grid_for(B, 256), dim3(256), 0, s, w, stats);
@@ -412,7 +461,8 @@ static int solve_batch_impl(mpc_handle *h, int B, const double *x0, const double
     if (h->dc.m && !lambda) return fail(MPC_E_ARG, "mpc_solve_batch: lambda is required when m > 0");
     rc = check_bound(h, B, "mpc_solve_batch"); if (rc) return rc;
     rc = check_box_bound(h, B, "mpc_solve_batch"); if (rc) return rc;
-    return solve_core(h, B, x0, cl, cl_index, h->pidx, h->bidx, U, lambda, stats, (hipStream_t)stream);
+    rc = check_con_bound(h, B, "mpc_solve_batch"); if (rc) return rc;
+    return solve_core(h, B, x0, cl, cl_index, h->pidx, h->bidx, h->cidx, U, lambda, stats, (hipStream_t)stream);
 }
 extern "C" int mpc_solve_batch(mpc_handle *h, int B, const double *x0, const double *cl, const int32_t *cl_index, double *U,
                                double *lambda, double *stats, void *stream)
@@ -480,6 +530,7 @@ extern "C" int mpc_closed_loop(mpc_handle *h, int B, int T, int shift, double *x
     if (c.m && !lambda) return fail(MPC_E_ARG, "mpc_closed_loop: lambda is required when m > 0");
     rc = check_bound(h, B, "mpc_closed_loop"); if (rc) return rc;
     rc = check_box_bound(h, B, "mpc_closed_loop"); if (rc) return rc;
+    rc = check_con_bound(h, B, "mpc_closed_loop"); if (rc) return rc;
     // bound table: the controller solves with row pidx[b], the plant advances with row pidx_plant[b] (null: the same)
     hipStream_t s = (hipStream_t)stream;
     double *st = stats;
@@ -520,6 +571,7 @@ static int solve_active_impl(mpc_handle *h, int B, const int32_t *active, const 
     r.xs = e.xs; r.Us = e.Us; r.lams = e.lams; r.stats_s = e.stats_s; r.cis = e.cis; r.pis = e.pis;
     hipLaunchKernelGGL(active_gather_kernel, grows, dim3(EV_BLK), 0, s, r);
     if (h->btab) hipLaunchKernelGGL(active_index_kernel, gblk, dim3(EV_BLK), 0, s, e.list, e.count, h->bidx, e.bis);
+    if (h->ctab) hipLaunchKernelGGL(active_index_kernel, gblk, dim3(EV_BLK), 0, s, e.list, e.count, h->cidx, e.kis);
     int *cnt = (int *)((char *)h->host_counts + 384);   // pinned (see host_counts)
     HIPCHK(hipMemcpyAsync(cnt, e.count, sizeof(int), hipMemcpyDeviceToHost, s));
     rc = bounded_sync(h, s, "mpc_solve_active"); if (rc) return rc;
@@ -527,7 +579,8 @@ static int solve_active_impl(mpc_handle *h, int B, const int32_t *active, const 
     if (nA < 0 || nA > B) return fail(MPC_E_HIP, "mpc_solve_active: the compaction counted " + std::to_string(nA) + " of " + std::to_string(B) + " agents");
     if (n_active) *n_active = nA;
     if (nA == 0) return MPC_OK;
-    rc = solve_core(h, nA, e.xs, cl, cl_index ? e.cis : nullptr, r.pidx ? e.pis : nullptr, h->btab ? e.bis : nullptr, e.Us, c.m ? e.lams : nullptr,
+    rc = solve_core(h, nA, e.xs, cl, cl_index ? e.cis : nullptr, r.pidx ? e.pis : nullptr, h->btab ? e.bis : nullptr,
+                    h->ctab ? e.kis : nullptr, e.Us, c.m ? e.lams : nullptr,
                     stats ? e.stats_s : nullptr, s);
     if (rc) return rc;
     hipLaunchKernelGGL(active_scatter_kernel, grid_for(nA, EV_BLK / 64), dim3(EV_BLK), 0, s, r);
@@ -546,6 +599,7 @@ extern "C" int mpc_solve_active(mpc_handle *h, int B, const int32_t *active, con
     if (h->dc.m && !lambda) return fail(MPC_E_ARG, "mpc_solve_active: lambda is required when m > 0");
     rc = check_bound(h, B, "mpc_solve_active"); if (rc) return rc;   // the caller's B; the compact batch is the library's
     rc = check_box_bound(h, B, "mpc_solve_active"); if (rc) return rc;
+    rc = check_con_bound(h, B, "mpc_solve_active"); if (rc) return rc;
     return solve_active_impl(h, B, active, x0, cl, cl_index, U, lambda, stats, n_active, (hipStream_t)stream, true);
 }
 
@@ -612,6 +666,7 @@ extern "C" int mpc_closed_loop_event(mpc_handle *h, int B, int T, int shift, con
     if (c.m && !lambda) return fail(MPC_E_ARG, "mpc_closed_loop_event: lambda is required when m > 0");
     rc = check_bound(h, B, "mpc_closed_loop_event"); if (rc) return rc;
     rc = check_box_bound(h, B, "mpc_closed_loop_event"); if (rc) return rc;
+    rc = check_con_bound(h, B, "mpc_closed_loop_event"); if (rc) return rc;
     rc = reserve_event(h, B); if (rc) return rc;
     bool fresh = false;
     rc = reserve_xhat(h, B, &fresh); if (rc) return rc;

@@ -92,6 +92,36 @@ MPC_DEV void agent_cfg_uniform(DevCfg &c, const double *__restrict__ tab, const 
 // arithmetic on the way -- so a row equal to the handle's box gives the shared path's bits.
 constexpr int NBOUND = 4;
 
+// mpc_set_agent_constraints: a table [P][NCONSTR] of constraint data in device memory and one row index per agent.  A
+// row is [0..5] g_off, [6..11] D_lb, [12..17] D_ub, [18] lane_halfwidth and replaces exactly the DevCfg fields of those
+// names, of which only the ones of the handle's constr_mode are read: the first nx entries of the three vectors
+// (STATE_SQ) or the halfwidth (LANE).  K1b evaluates g, the clip to [lb, ub], yhat and the adjoint on the private
+// DevCfg that already carries the agent's parameter row (the constraint forms exist together with PA alone); the
+// state machine reads the two bounds where it projects the multipliers (RowCon: mpc_solver.hpp).  The values are used
+// as they are -- no arithmetic on the way -- so a row equal to the handle's values gives the shared path's bits.
+constexpr int NCONSTR = 19;
+
+template <class Ld> MPC_DEV void agent_con_from(DevCfg &c, Ld ld)
+{
+    if (c.constr_mode == 2) { c.lane_hw = ld(18); return; }
+#pragma unroll
+    for (int i = 0; i < 6; i++) { c.g_off[i] = ld(i); c.D_lb[i] = ld(6 + i); c.D_ub[i] = ld(12 + i); }
+}
+// a different agent in every lane: vector values (only the entries a kernel's model reads survive: 3 nx of them)
+MPC_DEV void agent_con(DevCfg &c, const double *__restrict__ tab, const int *__restrict__ idx, int a)
+{
+    const double *__restrict__ r = tab + (size_t)idx[a] * NCONSTR;
+    agent_con_from(c, [=](int f) { return r[f]; });
+}
+// one agent per wave: scalar loads through the constant address space, as agent_cfg_uniform reads the parameter row
+MPC_DEV void agent_con_uniform(DevCfg &c, const double *__restrict__ tab, const int *__restrict__ idx, int a)
+{
+    const int row = __builtin_amdgcn_readfirstlane(idx[a]);
+    const __attribute__((address_space(4))) double *r =
+        (const __attribute__((address_space(4))) double *)(tab + (size_t)row * NCONSTR);
+    agent_con_from(c, [=](int f) { return r[f]; });
+}
+
 // ---------------------------------------------------------------------------------- math
 // The OCML double-precision transcendentals are full-range (Payne-Hanek reduction, dozens of
 // 64-bit literals each) and dominate this kernel's instruction count.  The angles of this problem

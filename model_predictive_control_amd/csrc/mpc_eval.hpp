@@ -673,11 +673,16 @@ __device__ __forceinline__ void adjoint_rec_quad_kin(const DevCfg &c, bool is_g,
 // (tried: the gradient blocks and the cost blocks by kernels of their own -- the cost-only variant needs 55
 // registers and runs eight waves per SIMD, 13 us per launch against 75 us for the gradient blocks -- but
 // the pair of launches is slower than the one: 180.2 vs 175.6 ms per solve)
-template <int MODEL, bool SHARED_CL, bool PA = false>
+// CT (here, in the fused kernel and in the wave evaluation): empty, or the constraint table (one trailing ConTab
+// argument: mpc_set_agent_constraints) -- the agent's private DevCfg takes g_off, D_lb, D_ub and the lane halfwidth of
+// the agent's own row next to its parameter row.  The constraint form exists together with PA alone: without a
+// parameter table of the caller's the host binds a one-row table of the handle's own values (mpc_launch.hpp).
+template <int MODEL, bool SHARED_CL, bool PA = false, class... CT>
 __global__ void __launch_bounds__(64, (MODEL == KIN ? MPC_K1B_WAVES : MPC_K1B_WAVES_PAC))
 stage_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, int nG_imm, int nC_imm,
-             int nblk_max)
+             int nblk_max, CT... ct)
 {
+    static_assert(sizeof...(CT) == 0 || PA, "the constraint form exists in the per-agent-parameter form alone");
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE;
 #if MPC_DEV_STAMP == 6
     DevStamp stamp(blockIdx.x);
@@ -714,6 +719,7 @@ stage_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, 
     const auto put = [=](int f, double v) { *(f == JS ? sl : jr + (size_t)f * St) = v; };
     DevCfg cm_;
     if constexpr (PA) { cm_ = c; agent_cfg(cm_, w.ptab, w.pidx, a); }
+    if constexpr (sizeof...(CT) != 0) agent_con(cm_, ct..., a);
     const DevCfg &cm = PA ? cm_ : c;
     if (is_g) stage_sens_record<MODEL>(cm, xs, xe, d, dl, put);
     Geom g;
@@ -764,11 +770,12 @@ constexpr int FUSED_BLK = 256;
 #ifndef MPC_FUSED_WAVES
 #define MPC_FUSED_WAVES 3
 #endif
-template <int MODEL, bool SHARED_CL, bool PA = false>
+template <int MODEL, bool SHARED_CL, bool PA = false, class... CT>
 __global__ void __launch_bounds__(FUSED_BLK, MPC_FUSED_WAVES)
 stage_adjoint_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, int nG_imm, int nC_imm,
-                     int *__restrict__ desc)
+                     int *__restrict__ desc, CT... ct)
 {
+    static_assert(sizeof...(CT) == 0 || PA, "the constraint form exists in the per-agent-parameter form alone");
     static_assert(MODEL == KIN, "the fused K1b + K1c kernel is the kinematic model's");
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE, BLK = FUSED_BLK;
     extern __shared__ double s_rec[];                    // [JS + 1][N][SPB]; row JS = stage cost
@@ -802,6 +809,7 @@ stage_adjoint_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ 
             const auto put = [=](int f, double v) { r[(size_t)f * NS] = v; };
             DevCfg cm_;
             if constexpr (PA) { cm_ = c; agent_cfg(cm_, w.ptab, w.pidx, a); }
+            if constexpr (sizeof...(CT) != 0) agent_con(cm_, ct..., a);
             const DevCfg &cm = PA ? cm_ : c;
             if (is_g) stage_sens_record<MODEL>(cm, xs, xe, d, dl, put);
             Geom g;

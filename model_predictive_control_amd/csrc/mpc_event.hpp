@@ -77,8 +77,8 @@ __global__ void __launch_bounds__(EV_BLK) active_gather_kernel(const ActiveRows 
     }
 }
 
-// the bounds-table row index of every listed agent into its staging row (one thread per listed agent; a launch of its
-// own, made only while a bounds table is bound: the gather above is what it was)
+// the bounds-table (or constraint-table) row index of every listed agent into its staging row (one thread per listed
+// agent; a launch of its own, made only while that table is bound: the gather above is what it was)
 __global__ void __launch_bounds__(EV_BLK) active_index_kernel(const int *__restrict__ list, const int *__restrict__ count,
                                                               const int *__restrict__ src, int *__restrict__ dst)
 {

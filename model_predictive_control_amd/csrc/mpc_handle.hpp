@@ -37,11 +37,15 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
 // The workspace as the host keeps it: the kernels' Workspace, the parameter table the per-agent kernels get with it
 // (WorkspacePA), and the bounds table of mpc_set_agent_bounds (both null: none bound), which reaches the per-agent-box
-// kernels as an argument of its own (BoxTab) and no other kernel at all.
+// kernels as an argument of its own (BoxTab) and no other kernel at all; the constraint table of
+// mpc_set_agent_constraints likewise (ConTab, the constraint forms alone).
 struct WorkspaceHost : WorkspacePA {
     const double *btab;                            // [P][MPC_NBOUND] caller's table
     const int *bidx;                               // [B]             caller's row index per agent
+    const double *ctab;                            // [P][MPC_NCONSTR] caller's table
+    const int *cidx;                               // [B]              caller's row index per agent
     BoxTab box() const { return BoxTab{btab, bidx}; }
+    ConTab con() const { return ConTab{ctab, cidx}; }
 };
 
 struct mpc_handle {
@@ -136,10 +140,17 @@ struct mpc_handle {
     const double *btab = nullptr;          // [btab_rows][MPC_NBOUND]
     const int32_t *bidx = nullptr;         // [btab_B]
     int btab_rows = 0, btab_B = 0;
-    // The persistent kernel has its box form together with the parameter form alone.  With a bounds table but no
-    // parameter table it runs on this one-row parameter table of the handle's own values (bit for bit the shared
-    // path: tests/test_gpu_agent_params.py) and an index of zeros; made at the first such bind, one allocation.
-    double *own_ptab = nullptr;            // [MPC_NPARAM], then the zeros
+    // mpc_set_agent_constraints: the caller's table of constraint data and row indices (device memory, read at every
+    // call; both null: none bound, every agent is held to the handle's constraint data by the kernels that have always run)
+    const double *ctab = nullptr;          // [ctab_rows][MPC_NCONSTR]
+    const int32_t *cidx = nullptr;         // [ctab_B]
+    int ctab_rows = 0, ctab_B = 0;
+    // The persistent kernel has its box form together with the parameter form alone, and its constraint form -- as the
+    // K1 kernels have theirs -- together with both.  With a table bound but not the ones its kernels come with, they run
+    // on these one-row tables of the handle's own values (bit for bit the shared path: tests/test_gpu_agent_params.py,
+    // tests/test_gpu_agent_bounds.py) and an index of zeros; made at the first such bind, one allocation.
+    double *own_ptab = nullptr;            // [MPC_NPARAM], a pad, then own_btab and the zeros
+    double *own_btab = nullptr;            // [MPC_NBOUND]
     int32_t *own_pidx = nullptr;           // [own_cap] zeros
     int own_cap = 0;
     // staging buffers for the standalone entry points
@@ -151,7 +162,7 @@ struct mpc_handle {
     struct EventBufs {
         char *base = nullptr;
         int cap = 0;                                   // agents the arena holds
-        int *list = nullptr, *blk = nullptr, *count = nullptr, *fire = nullptr, *cis = nullptr, *pis = nullptr, *bis = nullptr;
+        int *list = nullptr, *blk = nullptr, *count = nullptr, *fire = nullptr, *cis = nullptr, *pis = nullptr, *bis = nullptr, *kis = nullptr;
         double *xs = nullptr, *Us = nullptr, *lams = nullptr, *stats_s = nullptr, *stats_own = nullptr;
         double *xhat = nullptr;                        // [xhat_B][nx]
         int xhat_B = 0;
@@ -380,7 +391,7 @@ static int reserve_event(mpc_handle *h, int B)
     const DevCfg &c = h->dc;
     const size_t Bp = ((size_t)B + 63) & ~(size_t)63, m = c.m ? c.m : 1, nblk = (Bp + EV_BLK - 1) / EV_BLK;
     const size_t nd = (size_t)c.nx + c.n + m + 8 + 8;            // doubles per agent: xs, Us, lams, stats_s, stats_own
-    const size_t bytes = nd * 8 * Bp + 4 * (5 * Bp + nblk + 64);  // ints: list, fire, cis, pis, bis [Bp], blk [nblk], count
+    const size_t bytes = nd * 8 * Bp + 4 * (6 * Bp + nblk + 64);  // ints: list, fire, cis, pis, bis, kis [Bp], blk [nblk], count
     char *base = nullptr;
     if (hipMalloc((void **)&base, bytes) != hipSuccess) return fail(MPC_E_ALLOC, "masked-solve staging hipMalloc failed");
     e.base = base; e.cap = (int)Bp;
@@ -389,7 +400,7 @@ static int reserve_event(mpc_handle *h, int B)
     e.xs = takeD(c.nx); e.Us = takeD(c.n); e.lams = takeD(m); e.stats_s = takeD(8); e.stats_own = takeD(8);
     int *ip = (int *)dp;
     auto takeI = [&](size_t cnt) { int *r = ip; ip += cnt; return r; };
-    e.list = takeI(Bp); e.fire = takeI(Bp); e.cis = takeI(Bp); e.pis = takeI(Bp); e.bis = takeI(Bp); e.blk = takeI(nblk); e.count = takeI(64);
+    e.list = takeI(Bp); e.fire = takeI(Bp); e.cis = takeI(Bp); e.pis = takeI(Bp); e.bis = takeI(Bp); e.kis = takeI(Bp); e.blk = takeI(nblk); e.count = takeI(64);
     HIPCHK(hipMemset(base, 0, bytes));
     return MPC_OK;
 }
@@ -423,6 +434,25 @@ static int check_box_bound(const mpc_handle *h, int B, const char *who)
     if (h->btab && B != h->btab_B)
         return fail(MPC_E_ARG, std::string(who) + ": the bound bounds table is for a batch of " + std::to_string(h->btab_B) +
                                " agents, this call has " + std::to_string(B) + " (mpc_set_agent_bounds)");
+    return MPC_OK;
+}
+// ... and one with a constraint table, in the calls that read constraint data (`who`)
+static int check_con_bound(const mpc_handle *h, int B, const char *who)
+{
+    if (h->ctab && B != h->ctab_B)
+        return fail(MPC_E_ARG, std::string(who) + ": the bound constraint table is for a batch of " + std::to_string(h->ctab_B) +
+                               " agents, this call has " + std::to_string(B) + " (mpc_set_agent_constraints)");
+    return MPC_OK;
+}
+// a table can be bound for B agents beside the ones that are: bound together they are for the same batch
+// (self: the table being bound -- 0 parameters, 1 bounds, 2 constraints -- whose earlier binding does not count)
+static int check_tables_agree(const mpc_handle *h, int B, const char *who, int self)
+{
+    const int others[3] = {h->ptab ? h->ptab_B : B, h->btab ? h->btab_B : B, h->ctab ? h->ctab_B : B};
+    const char *names[3] = {"parameter", "bounds", "constraint"};
+    for (int i = 0; i < 3; i++)
+        if (i != self && others[i] != B)
+            return fail(MPC_E_ARG, std::string(who) + ": the bound " + names[i] + " table is for a batch of " + std::to_string(others[i]) + " agents");
     return MPC_OK;
 }
 static inline dim3 grid_for(int B, int block) { return dim3((unsigned)((B + block - 1) / block)); }

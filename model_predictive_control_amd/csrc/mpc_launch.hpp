@@ -2,7 +2,9 @@
 // kernel template.  Every run-time flag becomes a template argument in one place (with_flag / with_model /
 // with_model_table / with_hist_variant), so every kernel template is named at exactly one launch site and a new flag is
 // added once.  What is instantiated is what the `if constexpr`s below let through -- never the cross product: the
-// Pacejka model has no fused K1b + K1c, lookahead exists for <PAC, NE = 1> alone, adjoint_kernel has no per-agent form.
+// Pacejka model has no fused K1b + K1c, lookahead exists for <PAC, NE = 1> alone, adjoint_kernel has no per-agent form,
+// the constraint forms exist beside the parameter form alone (K1b, the wave evaluation), beside the parameter and box
+// forms alone (the persistent kernel) and for constrained problems alone (the step kernel).
 #pragma once
 #include "mpc_handle.hpp"
 
@@ -23,6 +25,16 @@ template <class F> static void with_model_table(const mpc_handle *h, const int32
         if (h->ptab) f(MODEL, std::true_type{}, h->ptab, index);
         else f(MODEL, std::false_type{});
     });
+}
+
+// The workspace as the constraint forms of the K1 kernels and of the persistent kernel take it: they exist together with
+// the parameter form alone, so without a parameter table of the caller's they run on the handle's own one-row table
+// (mpc_handle::own_ptab; its index of zeros needs no slicing per group)
+static WorkspacePA with_own_params(const mpc_handle *h, const WorkspaceHost &w)
+{
+    WorkspacePA wp = w;
+    if (!wp.ptab) { wp.ptab = h->own_ptab; wp.pidx = h->own_pidx; }
+    return wp;
 }
 
 // How the step kernel and the persistent kernel read an agent's L-BFGS history -- f(int_c<NE>, int_c<MC>), the two
@@ -85,6 +97,12 @@ static bool launch_eval_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
             const int spb = FUSED_BLK / c.N;
             const int gb = (nblk * 64 + spb - 1) / spb;
             const size_t flds = sizeof(double) * (size_t)(JS + 1) * c.N * spb;
+            if (w.ctab)     // a constraint table is bound: the constraint form of K1b (here and below)
+                with_flag(shared, [&](auto SH) {
+                    hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, ConTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
+                                       with_own_params(h, w), counts, nG, nC, desc, w.con());
+                });
+            else
             with_flags(shared, pa, [&](auto SH, auto PA) {
                 hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), PA()>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c, w, counts, nG, nC, desc);
             });
@@ -96,6 +114,12 @@ static bool launch_eval_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
     // block on XCD sb % 8 so that K1c could read records from the L2 they were written to -- no change: the 13 MB
     // of records per XCD and launch pass through a 4 MB L2 long before K1c starts)
     const size_t xy_lds = (shared && w.near.gmeta && c.S <= GRID_LDS_MAX_S) ? sizeof(double) * 2 * (size_t)c.S : 0;
+    if (w.ctab)
+        with_flag(shared, [&](auto SH) {
+            hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, ConTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
+                               with_own_params(h, w), counts, nG, nC, nblk, w.con());
+        });
+    else
     with_flags(shared, pa, [&](auto SH, auto PA) {
         hipLaunchKernelGGL((stage_kernel<MODEL, SH(), PA()>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c, w, counts, nG, nC, nblk);
     });
@@ -113,6 +137,14 @@ static bool launch_eval(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, co
 static void launch_solo_eval(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, int want_grad)
 {
     const DevCfg &c = h->dc;
+    if (w.ctab) {
+        with_model(c.model, [&](auto MODEL) {
+            const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
+            hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, ConTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
+                               want_grad, w.con());
+        });
+        return;
+    }
     with_model_table(h, h->pidx, [&](auto MODEL, auto PA, auto...) {
         const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
         hipLaunchKernelGGL((solo_eval_kernel<MODEL(), PA()>), dim3((unsigned)w.B), dim3(64), lds, s, c, w, want_grad);
@@ -178,6 +210,19 @@ static void launch_step_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
     const int apb = apb_env == 64 || apb_env == 32 || apb_env == 16 || apb_env == 8 || apb_env == 4 ? apb_env
                   : w.B >= 32768 ? 64 : w.B >= 16384 ? (lean ? 32 : 64) : w.B >= 6144 ? 16 : 4;
     const int nstep = (w.B + apb - 1) / apb;
+    // (w.ctab: a constraint table is bound -- on a constrained problem, or it would not be -- the constraint form,
+    // without or with the box form)
+    if (w.ctab) {
+        with_flag(w.btab != nullptr, [&](auto BA) {
+            if constexpr (BA())
+                hipLaunchKernelGGL((step_kernel_box_con<NE, MC>), dim3((unsigned)(nstep + nchain)), dim3(64 * STEP_WAVES), lds,
+                                   s, dcl, w, w.box(), w.con(), lists, counts, counts_next, apb, nstep, par, P);
+            else
+                hipLaunchKernelGGL((step_kernel_con<NE, MC>), dim3((unsigned)(nstep + nchain)), dim3(64 * STEP_WAVES), lds,
+                                   s, dcl, w, w.con(), lists, counts, counts_next, apb, nstep, par, P);
+        });
+        return;
+    }
     // (w.btab: a bounds table is bound, the per-agent-box form -- the one kernel of the round path that reads the box)
     with_flags(h->dc.m != 0, w.btab != nullptr, [&](auto HASM, auto BA) {
         if constexpr (BA())
@@ -215,6 +260,14 @@ static void launch_solo_t(mpc_handle *h, const WorkspaceHost &v, hipStream_t s, 
     // say yes: Pacejka model, one element per lane)
     // v.btab: a bounds table is bound, the box form, which exists together with the parameter form alone -- without a
     // parameter table of the caller's it runs on the handle's own one-row table (mpc_set_agent_bounds made it)
+    // v.ctab: a constraint table is bound, the constraint form, which exists together with the box form alone -- without
+    // a bounds table of the caller's it runs on the handle's own one-row box table (never with the lookahead: m > 0)
+    if (v.ctab) {
+        const BoxTab bt = v.btab ? v.box() : BoxTab{h->own_btab, h->own_pidx};
+        hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, ConTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
+                           with_own_params(h, v), list, ctr, max_trips, bt, v.con());
+        return;
+    }
     if (v.btab) {
         WorkspacePA vp = v;
         if (!vp.ptab) { vp.ptab = h->own_ptab; vp.pidx = h->own_pidx; }

@@ -231,13 +231,16 @@ __global__ void __launch_bounds__(256) solo_list_kernel(const Workspace w, int *
 }
 
 // K1 alone through the wave-per-agent evaluation (standalone entry point, parity tests): agent = block
-template <int MODEL, bool PA = false>
-__global__ void __launch_bounds__(64, 1) solo_eval_kernel(const DevCfg c_, const WsArg<PA> w, int want_grad)
+template <int MODEL, bool PA = false, class... CT>
+__global__ void __launch_bounds__(64, 1) solo_eval_kernel(const DevCfg c_, const WsArg<PA> w, int want_grad, CT... ct)
 {
+    static_assert(sizeof...(CT) == 0 || PA, "the constraint form exists in the per-agent-parameter form alone");
     extern __shared__ double s_solo[];
-    // (PA: the agent's row is wave-uniform -- scalar loads into the private DevCfg: agent_cfg_uniform)
+    // (PA: the agent's row is wave-uniform -- scalar loads into the private DevCfg: agent_cfg_uniform; CT: and its
+    // constraint row, the same way)
     DevCfg cm_;
     if constexpr (PA) { cm_ = c_; agent_cfg_uniform(cm_, w.ptab, w.pidx, blockIdx.x); }
+    if constexpr (sizeof...(CT) != 0) agent_con_uniform(cm_, ct..., blockIdx.x);
     const DevCfg &c = PA ? cm_ : c_;
     double *traj = s_solo;
     double *rec = traj + (size_t)(c.N + 1) * ModelDim<MODEL>::NX;
@@ -400,14 +403,20 @@ template <int MODEL> struct SoloOcc { static constexpr int WPS = MODEL == KIN ? 
 // same place, its row by scalar loads and this lane's two values of it chosen once per agent (lane_box_uniform); the state
 // machine and the lookahead's candidate points project onto it.  The box form exists together with PA alone: without a
 // parameter table of the caller's the host binds a one-row table of the handle's own values (mpc_launch.hpp).
+// BT = (BoxTab, ConTab): the constraint form (mpc_set_agent_constraints) -- the evaluations' DevCfg takes the agent's
+// constraint row with its parameter row, and the state machine projects the multipliers with the row's bounds (RowCon).
+// It exists together with the box form alone (the host supplies a one-row box table of the handle's own values when the
+// caller bound none), and never with the lookahead, which is an unconstrained problem's.
 template <int MODEL, int NE, int MC, bool LA = false, bool PA = false, class... BT>
 __global__ void __launch_bounds__(64 * SOLO_WAVES, SoloOcc<MODEL>::WPS)
 solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int *__restrict__ ctr,
             long long max_trips, BT... bt)
 {
-    constexpr bool BA = sizeof...(BT) != 0;
+    constexpr bool BA = sizeof...(BT) != 0, CA = sizeof...(BT) == 2;
     static_assert(!BA || PA, "the box form of the persistent kernel exists in the per-agent-parameter form alone");
+    static_assert(!CA || !LA, "the lookahead is an unconstrained problem's: it has no constraint form");
     using BOX = BoxOf<BA, LaneBox>;
+    using CON = ConOf<CA, RowCon>;
     extern __shared__ double s_solo[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const size_t per_wave = solo_lds_doubles<MODEL>(c.nfe, c.N, c.n, c.M, MC < 0);
@@ -431,7 +440,7 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
             if constexpr (BA) {
                 DevCfg cm = c;
                 agent_cfg_uniform(cm, w.ptab, w.pidx, a);
-                solo_agent_la<MC>(c, cm, w, a, lane, hist, traj, rec, la_base, max_trips, lane_box_uniform(bt..., a, lane));
+                solo_agent_la<MC>(c, cm, w, a, lane, hist, traj, rec, la_base, max_trips, lane_box_uniform(pack_box(bt...), a, lane));
             } else if constexpr (PA) {
                 DevCfg cm = c;
                 agent_cfg_uniform(cm, w.ptab, w.pidx, a);
@@ -451,7 +460,13 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
         if constexpr (PA) { cm_ = c; agent_cfg_uniform(cm_, w.ptab, w.pidx, a); }
         const DevCfg &cm = PA ? cm_ : c;
         BOX bx{};
-        if constexpr (BA) bx = lane_box_uniform(bt..., a, lane);
+        if constexpr (BA) bx = lane_box_uniform(pack_box(bt...), a, lane);
+        CON cn{};
+        if constexpr (CA) {
+            const ConTab &ct = pack_con(bt...);
+            agent_con_uniform(cm_, ct.ctab, ct.cidx, a);
+            cn = row_con_uniform(ct, a);
+        }
 #if MPC_DEV_STAMP == 5
         const long long st0 = __builtin_amdgcn_s_memrealtime();
         long long ntrip = 0, t_adv = 0;
@@ -462,7 +477,7 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
             const long long ta = __builtin_amdgcn_s_memrealtime();
 #endif
             const AgentIn<NE> in = load_agent<NE>(c, w, a, lane);
-            const int req = advance_agent<NE, MC, true, false, BOX>(c, w, a, lane, in, hist, false, /*allow_spec=*/spec, false, 1 << 30, bx);
+            const int req = advance_agent<NE, MC, true, false, BOX, CON>(c, w, a, lane, in, hist, false, /*allow_spec=*/spec, false, 1 << 30, bx, cn);
             if ((req & (REQ_GRAD | REQ_COST)) == 0) break;              // uniform: the agent is done
 #if MPC_DEV_STAMP == 5
             t_adv += __builtin_amdgcn_s_memrealtime() - ta;

@@ -111,6 +111,14 @@ struct BoxTab {
     const double *btab;                            // [P][NBOUND] caller's table
     const int *bidx;                               // [B]         caller's row index per agent
 };
+// The constraint table of mpc_set_agent_constraints, as the constraint forms of the kernels receive it: an argument of
+// its own behind everything the form without it takes (behind the BoxTab where a kernel has both).
+struct ConTab {
+    const double *ctab;                            // [P][NCONSTR] caller's table
+    const int *cidx;                               // [B]          caller's row index per agent
+};
+__device__ __forceinline__ void agent_con(DevCfg &c, const ConTab &t, int a) { agent_con(c, t.ctab, t.cidx, a); }
+__device__ __forceinline__ void agent_con_uniform(DevCfg &c, const ConTab &t, int a) { agent_con_uniform(c, t.ctab, t.cidx, a); }
 template <bool PA> struct WsArgT { using type = Workspace; };
 template <> struct WsArgT<true> { using type = WorkspacePA; };
 template <bool PA> using WsArg = typename WsArgT<PA>::type;
@@ -136,6 +144,15 @@ struct KernArgs {
     // (the per-agent-box kernels alone: their third parameter)
     static constexpr size_t B_OFF = (W_OFF + sizeof(Workspace) + alignof(BoxTab) - 1) / alignof(BoxTab) * alignof(BoxTab);
     __device__ __forceinline__ const BoxTab &box() const { return *(const BoxTab *)(p + B_OFF); }
+    // (the constraint forms alone: their third parameter, or their fourth behind the BoxTab)
+    static_assert(sizeof(ConTab) == sizeof(BoxTab) && alignof(ConTab) == alignof(BoxTab), "one layout for the two table arguments");
+    __device__ __forceinline__ const ConTab &con(bool behind_box) const { return *(const ConTab *)(p + B_OFF + (behind_box ? sizeof(BoxTab) : 0)); }
+    // ... and pointer i of the three every step kernel's parameter list goes on with (lists_out, counts_out, counts_next),
+    // which in those forms lie behind the ConTab
+    __device__ __forceinline__ int *con_tail(bool behind_box, int i) const
+    {
+        return *(int *const *)(p + B_OFF + (behind_box ? sizeof(BoxTab) : 0) + sizeof(ConTab) + i * sizeof(int *));
+    }
 };
 
 #ifdef MPC_DEV_STAMP
@@ -351,6 +368,53 @@ __device__ __forceinline__ LaneBox lane_box_uniform(const BoxTab &bt, int a, int
     b.l = (lane & 1) ? r[1] : r[0]; b.h = (lane & 1) ? r[3] : r[2];
     return b;
 }
+
+// Where the state machine takes the bounds [lb, ub] of general constraint kk of agent a's horizon from
+// (detail::project_y, once per outer iteration).
+//   CfgCon   the handle's, read from the DevCfg at the point of use -- what every kernel without a constraint form does
+//   RowCon   the agent's own row of a bound constraint table, at a wave-uniform address the persistent kernel forms when
+//            it claims the agent: lane kk's two values by vector loads
+//   KernCon  the same row in the step kernels, found where it is needed: the table out of the kernel's argument segment
+//            (KernArgs::con), the agent's row index, then the two values -- dependent loads in a phase an agent passes
+//            a few times per solve, and nothing held in registers across the state machine meanwhile (the constrained
+//            step kernels use all 106 scalar registers as they are)
+MPC_DEV void row_bounds(const DevCfg &c, const double *__restrict__ row, int kk, double &lb, double &ub)
+{
+    if (c.constr_mode == 2) { const double hw = row[18]; lb = -hw; ub = hw; }
+    else { const int i = kk % c.sm; lb = row[6 + i]; ub = row[12 + i]; }
+}
+struct CfgCon {
+    __device__ __forceinline__ void bounds(const DevCfg &c, const KernArgs &, int, int kk, double &lb, double &ub) const
+    {
+        constraint_bounds(c, kk % c.sm, lb, ub);
+    }
+};
+struct RowCon {
+    const double *row;
+    __device__ __forceinline__ void bounds(const DevCfg &c, const KernArgs &, int, int kk, double &lb, double &ub) const
+    {
+        row_bounds(c, row, kk, lb, ub);
+    }
+};
+template <bool BEHIND_BOX> struct KernCon {
+    __device__ __forceinline__ void bounds(const DevCfg &c, const KernArgs &ka, int a, int kk, double &lb, double &ub) const
+    {
+        const ConTab &t = ka.con(BEHIND_BOX);
+        row_bounds(c, t.ctab + (size_t)__builtin_amdgcn_readfirstlane(t.cidx[a]) * NCONSTR, kk, lb, ub);
+    }
+};
+template <bool CA, class PER_AGENT> struct ConOfT { using type = CfgCon; };
+template <class PER_AGENT> struct ConOfT<true, PER_AGENT> { using type = PER_AGENT; };
+template <bool CA, class PER_AGENT> using ConOf = typename ConOfT<CA, PER_AGENT>::type;
+// the row of agent a where one wave owns it for long (the persistent kernel): a wave-uniform address
+__device__ __forceinline__ RowCon row_con_uniform(const ConTab &ct, int a)
+{
+    return RowCon{ct.ctab + (size_t)__builtin_amdgcn_readfirstlane(ct.cidx[a]) * NCONSTR};
+}
+// the tables out of a kernel's trailing pack (BoxTab) or (BoxTab, ConTab)
+__device__ __forceinline__ const BoxTab &pack_box(const BoxTab &b) { return b; }
+__device__ __forceinline__ const BoxTab &pack_box(const BoxTab &b, const ConTab &) { return b; }
+__device__ __forceinline__ const ConTab &pack_con(const BoxTab &, const ConTab &c) { return c; }
 
 template <class BOX>
 __device__ __forceinline__ double prox_p(const DevCfg &c, const BOX &bx, int par, double x, double g, double gamma)
@@ -628,10 +692,12 @@ __device__ __forceinline__ AgentIn<NE> load_agent(const DevCfg &c, const Workspa
 // 106 scalar registers, and came back from spill lanes with two v_readlane each.
 // BOX: where the projection takes the input box from (CfgBox: the DevCfg's; LaneBox: `bx`, the agent's own row of a bound
 // bounds table, fetched with the agent's rows)
-template <int NE, int MC, bool HASM = true, bool LEAN = false, class BOX = CfgBox>
+// CON: where the projection of the multipliers takes the constraint bounds from (CfgCon: the DevCfg's; RowCon: `cn`, the
+// agent's own row of a bound constraint table)
+template <int NE, int MC, bool HASM = true, bool LEAN = false, class BOX = CfgBox, class CON = CfgCon>
 __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int lane, const AgentIn<NE> &in,
                              double *hist, bool hist_ready, bool allow_spec = true, bool allow_chain = false,
-                             int P = 1 << 30, const BOX &bx = BOX())
+                             int P = 1 << 30, const BOX &bx = BOX(), const CON &cn = CON())
 {
 #pragma clang fp contract(off)   // fixed roundings: the step kernel and the persistent kernel must agree bit for bit
     const int n = cfg.n, m = HASM ? cfg.m : 0;
@@ -741,7 +807,7 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
         case PH_OUTER_BEGIN: {
             for (int kk = lane; kk < m; kk += 64) { // detail::project_y
                 double lbd, ubd;
-                constraint_bounds(c, kk % c.sm, lbd, ubd);
+                cn.bounds(c, ka, a, kk, lbd, ubd);
                 const double ylo = isinf(lbd) ? 0.0 : -c.Mcap, yhi = isinf(ubd) ? 0.0 : c.Mcap;
                 w.y[am + kk] = fmin(fmax(w.y[am + kk], ylo), yhi);
             }
@@ -1346,9 +1412,11 @@ step_kernel(const DevCfg c, const Workspace w, int *__restrict__ lists_out,
 {
 #define MPC_STEP_BA false
 #define MPC_STEP_BT BoxTab{nullptr, nullptr}
+#define MPC_STEP_CA false
 #include "mpc_step_body.hpp"
 #undef MPC_STEP_BA
 #undef MPC_STEP_BT
+#undef MPC_STEP_CA
 }
 // ... with every agent's own input box (mpc_set_agent_bounds): same body, same occupancy targets, same LDS plan
 template <int NE, int MC, bool HASM>
@@ -1358,9 +1426,42 @@ step_kernel_box(const DevCfg c, const Workspace w, const BoxTab bt, int *__restr
 {
 #define MPC_STEP_BA true
 #define MPC_STEP_BT bt
+#define MPC_STEP_CA false
 #include "mpc_step_body.hpp"
 #undef MPC_STEP_BA
 #undef MPC_STEP_BT
+#undef MPC_STEP_CA
+}
+// ... with every agent's own constraint data (mpc_set_agent_constraints), without and with its own box.  Only a
+// constrained problem has constraint data: these exist for HASM alone.  (The body reads the table out of the argument
+// segment where it needs it -- KernCon -- so `ct` is named by nothing but the launch.)
+template <int NE, int MC>
+__global__ void __launch_bounds__(64 * STEP_WAVES, step_waves_per_simd(NE, MC, true))
+step_kernel_con(const DevCfg c, const Workspace w, const ConTab ct, int *__restrict__ lists_out,
+                int *__restrict__ counts_out, int *__restrict__ counts_next, int apb, int nstep, int par, int P)
+{
+    constexpr bool HASM = true;
+#define MPC_STEP_BA false
+#define MPC_STEP_BT BoxTab{nullptr, nullptr}
+#define MPC_STEP_CA true
+#include "mpc_step_body.hpp"
+#undef MPC_STEP_BA
+#undef MPC_STEP_BT
+#undef MPC_STEP_CA
+}
+template <int NE, int MC>
+__global__ void __launch_bounds__(64 * STEP_WAVES, step_waves_per_simd(NE, MC, true))
+step_kernel_box_con(const DevCfg c, const Workspace w, const BoxTab bt, const ConTab ct, int *__restrict__ lists_out,
+                    int *__restrict__ counts_out, int *__restrict__ counts_next, int apb, int nstep, int par, int P)
+{
+    constexpr bool HASM = true;
+#define MPC_STEP_BA true
+#define MPC_STEP_BT bt
+#define MPC_STEP_CA true
+#include "mpc_step_body.hpp"
+#undef MPC_STEP_BA
+#undef MPC_STEP_BT
+#undef MPC_STEP_CA
 }
 
 // solver state initialisation for a fresh solve (ALMSolver::operator() prologue)

@@ -1,8 +1,10 @@
-// mpc_step_body.hpp -- the body of the step kernels (mpc_solver.hpp), included once into each of the two: step_kernel
-// (MPC_STEP_BA false: the handle's box) and step_kernel_box (MPC_STEP_BA true: every agent's own box from the bounds table
-// MPC_STEP_BT, that kernel's third parameter).  Text, not a function: the kernels re-read their DevCfg and Workspace from
+// mpc_step_body.hpp -- the body of the step kernels (mpc_solver.hpp), included once into each of them: step_kernel
+// (MPC_STEP_BA false: the handle's box), step_kernel_box (MPC_STEP_BA true: every agent's own box from the bounds table
+// MPC_STEP_BT, that kernel's third parameter) and the constraint forms of the two (MPC_STEP_CA, below).  Text, not a function: the kernels re-read their DevCfg and Workspace from
 // the argument segment (KernArgs) and step_kernel's instruction stream is pinned -- a body reached through a call, even an
 // inlined one, is scheduled differently.  No include guard.
+// MPC_STEP_CA true (step_kernel_con, step_kernel_box_con): every agent's own constraint bounds from the constraint table,
+// the parameter behind the ones above (KernCon).
 //
 // The box form: the workgroup's row indices arrive with its phase words (one coalesced read, lane l: agent base + l), so
 // an agent's row is addressed from a register, and its two values per lane are asked for with the record and the rows
@@ -34,6 +36,7 @@
     const int phw = lane < apb && base + lane < w.B ? rec_int_of(w.rec[(size_t)(base + lane) * REC + R_PHASE]) : 0;
     int brow = 0;                                        // (BA) row of the bounds table of agent base + lane
     if constexpr (MPC_STEP_BA) brow = lane < apb && base + lane < w.B ? (MPC_STEP_BT).bidx[base + lane] : 0;
+    using CON = ConOf<MPC_STEP_CA, KernCon<MPC_STEP_BA>>;
     using BOX = BoxOf<MPC_STEP_BA, LaneBox>;
     const auto box_of = [&](const BoxTab &b, int l) {
         if constexpr (MPC_STEP_BA) return load_lane_box(b, __builtin_amdgcn_readlane(brow, l), lane);
@@ -99,7 +102,7 @@
         const long long tv0 = __builtin_amdgcn_s_memrealtime();
         const int ph_in = __builtin_amdgcn_readlane(__double2loint(cur.rv), R_PHASE) & PH_MASK;
 #endif
-        const int req = advance_agent<NE, MC, HASM, true, BOX>(c, w, a, lane, cur, hist, hist_ready, true, /*allow_chain=*/true, P, cbx);
+        const int req = advance_agent<NE, MC, HASM, true, BOX, CON>(c, w, a, lane, cur, hist, hist_ready, true, /*allow_chain=*/true, P, cbx, CON());
 #if MPC_DEV_STAMP == 3
         {   // the longest agent-step of this wave: its length in 10 ns ticks (nmid, capped at 255) and the phase it came in with (nslow)
             const int dt = (int)(__builtin_amdgcn_s_memrealtime() - tv0);
@@ -110,6 +113,13 @@
         loc = loc_next;
     }
     __syncthreads();
+    // (CA: the two list pointers are read again from the argument segment here, where they are used, and so are not held
+    // across the loop above -- four scalar registers that the constrained kernels, at 106 of 106, do not have)
+    int *lists_o = lists_out, *counts_o = counts_out;
+    if constexpr (MPC_STEP_CA) {
+        const KernArgs kt;
+        lists_o = kt.con_tail(MPC_STEP_BA, 0); counts_o = kt.con_tail(MPC_STEP_BA, 1);
+    }
     if (wv == 0) {
         const int r = s_req[lane];
 #pragma unroll
@@ -119,12 +129,12 @@
             const int cnt = __popcll(bal);
             if (cnt == 0) continue;                      // uniform
             int base = 0;
-            if (lane == 0) base = atomicAdd(&counts_out[kind], cnt);
+            if (lane == 0) base = atomicAdd(&counts_o[kind], cnt);
             base = __builtin_amdgcn_readfirstlane(base);
             if (on) {
                 const int off = __popcll(bal & ((1ull << lane) - 1ull));
                 const int flag = kind == 0 ? ((r & REQ_SPEC) ? CH2_BIT : 0) | ((r & REQ_CHAIN) ? CHAIN_BIT : 0) : 0;
-                lists_out[(size_t)kind * w.Ls + base + off] = (blockIdx.x * apb + lane) | flag;
+                lists_o[(size_t)kind * w.Ls + base + off] = (blockIdx.x * apb + lane) | flag;
             }
         }
     }

@@ -50,6 +50,7 @@ class BatchedMPC:
         self._cl_key, self._cl_keep = None, None   # the centerline table the search tables were last built for
         self._params_keep = None    # (table, index, plant_index) of set_agent_params, alive while bound
         self._bounds_keep = None    # (table, index) of set_agent_bounds, alive while bound
+        self._constraints_keep = None   # (table, index) of set_agent_constraints, alive while bound
         import os
         # nearest-point search of K1b as the library chose it at mpc_create: 2 grid of index ranges (default), 0 the
         # full scan (MPC_NEAREST_SCAN) -- which needs no tables
@@ -192,6 +193,38 @@ class BatchedMPC:
     @property
     def agent_bounds_bound(self):
         return self._bounds_keep is not None
+
+    # ------------------------------------------------------------------ per-agent constraint data
+    def set_agent_constraints(self, table, index):
+        """Binds a per-agent table of constraint data (mpc_set_agent_constraints): table [P, 19] float64 (rows
+        [g_off[6], D_lb[6], D_ub[6], lane_halfwidth], as _lib.constraint_rows makes them; only the fields of the engine's
+        constr_mode are read), index [B] int32 = the row of agent b.  Bound, every call that reads constraint data
+        (eval_cost_grad, solve, solve_async, solve_active, closed_loop, closed_loop_event) uses agent b's row and serves
+        batches of exactly B agents.  Independent of the parameter and bounds tables (any subset; together they are for
+        the same B).  The tensors stay the caller's: the library reads them at every call, so rows may be rewritten in
+        place between calls; the engine keeps them alive until clear_agent_constraints()."""
+        self._free()
+        if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] != _lib.NCONSTR or table.shape[0] < 1:
+            raise ValueError(f"table: expected a tensor [P >= 1, {_lib.NCONSTR}]")
+        self._chk(table, table.shape, "table")
+        if not isinstance(index, torch.Tensor) or index.dim() != 1 or index.shape[0] < 1:
+            raise ValueError("index: expected a tensor [B >= 1]")
+        B, P = int(index.shape[0]), int(table.shape[0])
+        self._chk(index, (B,), "index", torch.int32)
+        if int(index.min()) < 0 or int(index.max()) >= P:
+            raise ValueError("index out of range")
+        _lib.check(self.lib.mpc_set_agent_constraints(self._h, _ptr(table), P, _ptr(index), B))
+        self._constraints_keep = (table, index)
+
+    def clear_agent_constraints(self):
+        """Unbinds the constraint table: the engine is what it was before set_agent_constraints."""
+        self._free()
+        _lib.check(self.lib.mpc_set_agent_constraints(self._h, None, 0, None, 0))
+        self._constraints_keep = None
+
+    @property
+    def agent_constraints_bound(self):
+        return self._constraints_keep is not None
 
     def invalidate_centerline_tables(self):
         """Forget the nearest-point search tables: the next call rebuilds them for the table it is given."""
