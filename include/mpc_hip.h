@@ -18,8 +18,8 @@
  *  - centerlines: table cl [C][2S], each row flat [x_0..x_{S-1}, y_0..y_{S-1}]
  *    (main.py:113 ravel(order='F')); cl_index [B] int32 selects a row per agent, NULL = row 0.
  *  - every call is asynchronous on `stream` (a hipStream_t passed as void*) except
- *    mpc_solve_batch / mpc_solve_active / mpc_closed_loop / mpc_closed_loop_event, which poll device counters and return
- *    when the batch is solved.
+ *    mpc_solve_batch / mpc_solve_active / mpc_closed_loop / mpc_closed_loop_event / mpc_closed_loop_track, which poll
+ *    device counters and return when the batch is solved.
  *  - between mpc_solve_batch_async and mpc_solve_wait the handle belongs to its worker thread: every
  *    other call on it returns MPC_E_ARG without touching it.
  *  - return value: 0 on success, negative MPC_E_* otherwise; mpc_last_error() explains.
@@ -279,6 +279,61 @@ int mpc_closed_loop_event(mpc_handle *h, int B, int T, int shift, const double *
                           double *x, const double *cl, const int32_t *cl_index, double *U, double *lambda,
                           int32_t *held, const double *disturbance, double *traj_x, double *traj_u,
                           uint8_t *solved, int32_t *solve_count, int32_t *fail_count, double *stats, void *stream);
+
+/* Lap driving: per-agent centerline windows on long and closed tracks.  A centerline row is S points and the nearest
+ * point is searched among candidates 0 .. S-2 of ONE row: an agent that reaches the end of its row sticks there.  A track
+ * is therefore cut into overlapping windows, each an ordinary centerline row, and an agent's row is re-selected on the
+ * device whenever it re-plans; K1b, the grid of index ranges and every solver kernel see what they always saw.
+ *
+ * Track table: track [K][2L], each row flat [x_0..x_{L-1}, y_0..y_{L-1}] like a centerline row; a CLOSED track does not
+ * repeat its first point at the end.  With stride w, window r of track k is row k*R + r of win [K*R][2S] and holds track
+ * points r*w + i, i < S -- on a closed track the point index is taken mod L and R = ceil(L / w); on an open track
+ * R = (L - S) / w + 1 (integer division).  L >= S in both cases.
+ *
+ * The rule, for an agent on row k*R + r whose nearest index on that row is i (integers only; the one floating-point
+ * decision is the nearest index):
+ *     open:    p = r*w + i - lead,            r' = min(max(floor(p / w), 0), R - 1)   (floor towards minus infinity)
+ *     closed:  p = (r*w + i - lead) mod L,    r' = p / w                             (0 <= p < L)
+ *     new row = k*R + r',   pos = r*w + i  (mod L on a closed track): the track point the agent stands at.
+ * Where nothing is clamped the agent's nearest index on its new row lies in [lead, lead + w): `lead` points of the track
+ * behind it, S - lead - w or more ahead.
+ *
+ * mpc_track_init (host only): checks K >= 1, L >= S, stride >= 1, 0 <= lead <= S - 2 and that K * R fits an int32
+ *   (MPC_E_ARG otherwise) and fills *t, R included.  The other calls refuse a track that is not what it gives for the
+ *   handle's S.
+ * mpc_track_windows: win from track, a pure gather, asynchronous on `stream`: every word of win is a copy of a word of
+ *   track.  The caller then prepares the search tables for win once (mpc_centerline_blocks(h, win, K*R, stream)).
+ *   GRID LIMIT: the grid of index ranges is built for at most 1 024 rows (256 KB each); a window table with K*R above that
+ *   takes the full scan in every call -- the same results, slower.  The caller chooses the stride accordingly.
+ * mpc_track_select: x [B][nx] (only x[b][0], x[b][1] are read), cl_index [B] inout, pos [B] out (NULL ok).  The nearest
+ *   index is the one K1b will find for that row: the search mpc_set_nearest_blocks selects with the tables
+ *   mpc_centerline_blocks built for `win`, the full scan if there are none -- the same index, bit for bit.  An agent with
+ *   active[b] == 0 (active NULL: all are active), one whose x or y is not finite and one whose cl_index is not a row of
+ *   the table is not written (neither cl_index nor pos).  Asynchronous on `stream`.
+ * mpc_track_locate: the first placement.  a = nearest index by the same rule on the agent's WHOLE track row
+ *   track_index[b] (NULL: track 0): candidates 0 .. L-2, first minimum, the same squared-distance expression; then the
+ *   rule above with r*w + i replaced by a.  An agent whose track_index is not a track of the table is not written.
+ *   Asynchronous on `stream`.
+ * mpc_closed_loop_track: mpc_closed_loop_event (every argument of it, cl = win, cl_index NOT const and not NULL) with one
+ *   step between 1 and 2: the FIRING agents re-select their row (mpc_track_select with active = fire, on the plant state
+ *   x); an agent that holds its plan keeps the row the plan was solved on.  traj_row [B][T] (NULL ok) is the row in force
+ *   at step t.  thr = 0 re-selects and solves everybody at every step.  A later call continues from cl_index, held and the
+ *   nominal states, as the event loop does.  The caller builds win and its search tables once, before the loop: the loop
+ *   builds nothing.  On a one-window track it is mpc_closed_loop_event on that row, bit for bit.  Blocking.
+ * All of them are refused (MPC_E_ARG) while an asynchronous solve is in flight; with a parameter, bounds or constraint
+ * table bound, the calls that take B return MPC_E_ARG for a batch size other than the bound one. */
+typedef struct mpc_track { int32_t K, L, stride, lead, closed, R; } mpc_track;
+int mpc_track_init(mpc_track *t, const mpc_config *cfg, int K, int L, int stride, int lead, int closed);
+int mpc_track_windows(mpc_handle *h, const mpc_track *t, const double *track, double *win, void *stream);
+int mpc_track_locate(mpc_handle *h, const mpc_track *t, int B, const double *x, const double *track,
+                     const int32_t *track_index, int32_t *cl_index, void *stream);
+int mpc_track_select(mpc_handle *h, const mpc_track *t, int B, const double *x, const double *win,
+                     const int32_t *active, int32_t *cl_index, int32_t *pos, void *stream);
+int mpc_closed_loop_track(mpc_handle *h, int B, int T, int shift, const double *w, double thr, int max_hold,
+                          double *x, const double *win, int32_t *cl_index, double *U, double *lambda,
+                          int32_t *held, const double *disturbance, double *traj_x, double *traj_u,
+                          uint8_t *solved, int32_t *solve_count, int32_t *fail_count, double *stats, void *stream,
+                          const mpc_track *trk, int32_t *traj_row);
 
 /* profiling aid: rounds (eval launches) and kernel time of the last mpc_solve_batch */
 int mpc_last_solve_info(mpc_handle *h, int64_t *rounds, int64_t *evals_grad, int64_t *evals_cost,

@@ -5,9 +5,11 @@ from . import _lib
 from ._lib import (MODEL_KINEMATIC, MODEL_PACEJKA, WRAP_FLOOR, WRAP_FMOD, WRAP_IEEE, CONSTR_NONE,
                    CONSTR_STATE_SQ, CONSTR_LANE, NSTATS, NPARAM, MpcConfig, default_config, default_params, param_rows,
                    NBOUND, default_bounds, bound_rows, NCONSTR, default_constraints, constraint_rows, MpcError)
-from .solver import BatchedMPC
+from .solver import BatchedMPC, Track
+from .tracks import stadium_track, circle_track
 
 __all__ = ["BatchedMPC", "MpcConfig", "default_config", "MpcError", "MODEL_KINEMATIC",
            "MODEL_PACEJKA", "WRAP_FLOOR", "WRAP_FMOD", "WRAP_IEEE", "CONSTR_NONE", "CONSTR_STATE_SQ",
            "CONSTR_LANE", "NSTATS", "NPARAM", "default_params", "param_rows",
-           "NBOUND", "default_bounds", "bound_rows", "NCONSTR", "default_constraints", "constraint_rows"]
+           "NBOUND", "default_bounds", "bound_rows", "NCONSTR", "default_constraints", "constraint_rows",
+           "Track", "stadium_track", "circle_track"]

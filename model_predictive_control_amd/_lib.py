@@ -31,7 +31,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPC_LIB_PATH", os.path.join(_HERE, "libmpc_hip.so"))  # override: dev experiments
 _SRC = [os.path.join(_HERE, "csrc", f) for f in ("mpc_api.hip", "mpc_handle.hpp", "mpc_launch.hpp", "mpc_rounds.hpp",
                                                   "mpc_aux.hpp", "mpc_eval.hpp", "mpc_solver.hpp", "mpc_device.hpp",
-                                                  "mpc_game.hpp", "mpc_solo.hpp", "mpc_event.hpp", "mpc_step_body.hpp")]
+                                                  "mpc_game.hpp", "mpc_solo.hpp", "mpc_event.hpp", "mpc_step_body.hpp",
+                                                  "mpc_track.hpp")]
 _HDR = os.path.join(os.path.dirname(_HERE), "include", "mpc_hip.h")
 
 MODEL_KINEMATIC, MODEL_PACEJKA = 0, 1
@@ -53,6 +54,7 @@ EXPORTS = [
     "mpc_solve_active", "mpc_trigger_eval", "mpc_closed_loop_event",
     "mpc_default_bounds", "mpc_set_agent_bounds",
     "mpc_default_constraints", "mpc_set_agent_constraints",
+    "mpc_track_init", "mpc_track_windows", "mpc_track_locate", "mpc_track_select", "mpc_closed_loop_track",
 ]
 NREC = 64
 NPARAM = 31     # MPC_NPARAM: doubles per row of the per-agent parameter table
@@ -86,6 +88,12 @@ class MpcConfig(C.Structure):
         ("L_min", C.c_double), ("L_max", C.c_double), ("tau_min", C.c_double),
         ("qub_tol", C.c_double),
     ]
+
+
+class MpcTrack(C.Structure):
+    """Mirror of `mpc_track` (include/mpc_hip.h): the geometry of a table of track windows, filled by mpc_track_init."""
+    _fields_ = [("K", C.c_int32), ("L", C.c_int32), ("stride", C.c_int32), ("lead", C.c_int32),
+                ("closed", C.c_int32), ("R", C.c_int32)]
 
 
 def source_hash():
@@ -149,6 +157,12 @@ def load():
     L.mpc_trigger_eval.argtypes = [vp, ci, vp, vp, vp, C.POINTER(C.c_double), C.c_double, ci, vp, vp, vp]
     L.mpc_closed_loop_event.argtypes = [vp, ci, ci, ci, C.POINTER(C.c_double), C.c_double, ci, vp, vp, vp, vp, vp, vp,
                                         vp, vp, vp, vp, vp, vp, vp, vp]
+    tp = C.POINTER(MpcTrack)
+    L.mpc_track_init.argtypes = [tp, cp, ci, ci, ci, ci, ci]
+    L.mpc_track_windows.argtypes = [vp, tp, vp, vp, vp]
+    L.mpc_track_locate.argtypes = [vp, tp, ci, vp, vp, vp, vp, vp]
+    L.mpc_track_select.argtypes = [vp, tp, ci, vp, vp, vp, vp, vp, vp]
+    L.mpc_closed_loop_track.argtypes = L.mpc_closed_loop_event.argtypes + [tp, vp]
     L.mpc_last_solve_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                       C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double)]
@@ -311,6 +325,16 @@ def constraint_rows(cfg, P, g_off=None, D_lb=None, D_ub=None, lane_halfwidth=Non
             raise ValueError(f"constraint_rows: lane_halfwidth must be a scalar or have shape ({P},), got {v.shape}")
         tab[:, CONSTR_FIELDS["lane_halfwidth"][0]] = v
     return tab
+
+
+def track_init(cfg, K, L, stride, lead, closed):
+    """mpc_track_init: the geometry (an MpcTrack, R filled in) of the window table of K tracks of L points each for
+    `cfg`'s S, or ValueError with the library's reason.  Pure host code: usable without a GPU."""
+    t = MpcTrack()
+    rc = load().mpc_track_init(C.byref(t), C.byref(cfg), int(K), int(L), int(stride), int(lead), int(bool(closed)))
+    if rc != 0:
+        raise ValueError(load().mpc_last_error().decode())
+    return t
 
 
 def library_hash():

@@ -1,8 +1,9 @@
 // mpc_api.hip -- the C-ABI of libmpc_hip.so (see include/mpc_hip.h): the extern "C" entry points of the batched MPC
 // solve on one MI355X, one process / one handle per GPU.  The one translation unit of the library: the host side is in
 // mpc_handle.hpp (the handle), mpc_launch.hpp (which kernel instantiation a launch takes) and mpc_rounds.hpp (the
-// round loop of a solve), the kernels in the headers those include.
+// round loop of a solve), the kernels in the headers those include (and mpc_track.hpp: the kernels of lap driving).
 #include "mpc_rounds.hpp"
+#include "mpc_track.hpp"
 
 extern "C" const char *mpc_last_error(void) { return g_err.c_str(); }
 #ifndef MPC_SOURCE_SHA256
@@ -646,27 +647,114 @@ extern "C" int mpc_trigger_eval(mpc_handle *h, int B, const double *x, const dou
     return MPC_OK;
 }
 
+// ---------------------------------------------------------------------------------- lap driving (mpc_track.hpp)
+// windows of a track of L points with stride w: closed ceil(L / w), open (L - S) / w + 1; -1 when L < S
+static long long track_window_count(long long L, long long S, long long w, int closed)
+{
+    if (L < S || w < 1) return -1;
+    return closed ? (L + w - 1) / w : (L - S) / w + 1;
+}
+extern "C" int mpc_track_init(mpc_track *t, const mpc_config *cfg, int K, int L, int stride, int lead, int closed)
+{
+    if (!t || !cfg) return fail(MPC_E_ARG, "mpc_track_init: null argument");
+    const int S = cfg->S;
+    if (S < 3) return fail(MPC_E_ARG, "mpc_track_init: the configuration needs S >= 3 centerline points");
+    if (K < 1) return fail(MPC_E_ARG, "mpc_track_init: K must be >= 1");
+    if (L < S) return fail(MPC_E_ARG, "mpc_track_init: a track needs L >= S = " + std::to_string(S) + " points");
+    if (stride < 1) return fail(MPC_E_ARG, "mpc_track_init: stride must be >= 1");
+    if (lead < 0 || lead > S - 2) return fail(MPC_E_ARG, "mpc_track_init: lead must be in [0, S - 2]");
+    const long long R = track_window_count(L, S, stride, closed);
+    if (R < 1 || (long long)K * R > 2147483647ll) return fail(MPC_E_ARG, "mpc_track_init: K * R does not fit an int32");
+    t->K = K; t->L = L; t->stride = stride; t->lead = lead; t->closed = closed ? 1 : 0; t->R = (int32_t)R;
+    return MPC_OK;
+}
+// a track as mpc_track_init fills it for this handle's S (anything else is refused before a kernel sees it)
+static int check_track(const mpc_handle *h, const mpc_track *t, const char *who)
+{
+    if (!t) return fail(MPC_E_ARG, std::string(who) + ": null track");
+    const int S = h->cfg.S;
+    const long long R = track_window_count(t->L, S, t->stride, t->closed);
+    if (t->K < 1 || R < 1 || t->lead < 0 || t->lead > S - 2 || (t->closed != 0 && t->closed != 1) || R != t->R ||
+        (long long)t->K * R > 2147483647ll)
+        return fail(MPC_E_ARG, std::string(who) + ": the track's geometry is not what mpc_track_init gives for this handle");
+    return MPC_OK;
+}
+static TrackGeom track_geom(const mpc_track *t) { return TrackGeom{t->K, t->L, t->stride, t->lead, t->closed, t->R}; }
+
+extern "C" int mpc_track_windows(mpc_handle *h, const mpc_track *t, const double *track, double *win, void *stream)
+{
+    int rc = check_common(h, 0, "mpc_track_windows"); if (rc) return rc;
+    rc = check_track(h, t, "mpc_track_windows"); if (rc) return rc;
+    if (!track || !win) return fail(MPC_E_ARG, "mpc_track_windows: null buffer");
+    const size_t words = (size_t)t->K * (size_t)t->R * 2 * (size_t)h->cfg.S;
+    const unsigned blocks = (unsigned)std::min<size_t>((words + 255) / 256, (size_t)1 << 20);
+    hipLaunchKernelGGL(track_windows_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, track_geom(t), h->cfg.S, track, win);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
+// what the two per-agent calls share: the handle, the track and, with tables bound, the batch they are bound for
+static int check_track_call(mpc_handle *h, const mpc_track *t, int B, const char *who)
+{
+    int rc = check_common(h, B, who); if (rc) return rc;
+    rc = check_track(h, t, who); if (rc) return rc;
+    rc = check_bound(h, B, who); if (rc) return rc;
+    rc = check_box_bound(h, B, who); if (rc) return rc;
+    return check_con_bound(h, B, who);
+}
+
+extern "C" int mpc_track_locate(mpc_handle *h, const mpc_track *t, int B, const double *x, const double *track,
+                                const int32_t *track_index, int32_t *cl_index, void *stream)
+{
+    int rc = check_track_call(h, t, B, "mpc_track_locate"); if (rc) return rc;
+    if (B == 0) return MPC_OK;
+    if (!x || !track || !cl_index) return fail(MPC_E_ARG, "mpc_track_locate: null buffer");
+    DevCfg cL = h->dc;
+    cL.S = t->L;                           // nearest_index over the whole track row: candidates 0 .. L-2
+    hipLaunchKernelGGL(track_locate_kernel, grid_for(B, 64), dim3(64), 0, (hipStream_t)stream, cL, track_geom(t), B, h->dc.nx, x,
+                       track, track_index, cl_index);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
+extern "C" int mpc_track_select(mpc_handle *h, const mpc_track *t, int B, const double *x, const double *win,
+                                const int32_t *active, int32_t *cl_index, int32_t *pos, void *stream)
+{
+    int rc = check_track_call(h, t, B, "mpc_track_select"); if (rc) return rc;
+    if (B == 0) return MPC_OK;
+    if (!x || !win || !cl_index) return fail(MPC_E_ARG, "mpc_track_select: null buffer");
+    hipLaunchKernelGGL(track_select_kernel, grid_for(B, 64), dim3(64), 0, (hipStream_t)stream, h->dc, track_geom(t), B, h->dc.nx, x,
+                       win, active, near_for(h, win), cl_index, pos, (int *)nullptr, 0, 0);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
 // Event-triggered closed loop: per step the trigger (which also shifts a firing agent's plan by the stages it has
 // applied), the masked solve of the agents that fired, and one kernel that applies stage `held` of every agent's plan
 // to plant and nominal state.  Control returns to the host once per step for the count of firing agents (and, inside
 // the solve, once per round window, as in every solve); data never leaves the device.
-extern "C" int mpc_closed_loop_event(mpc_handle *h, int B, int T, int shift, const double *w, double thr, int max_hold,
-                                     double *x, const double *cl, const int32_t *cl_index, double *U, double *lambda,
-                                     int32_t *held, const double *disturbance, double *traj_x, double *traj_u,
-                                     uint8_t *solved, int32_t *solve_count, int32_t *fail_count, double *stats, void *stream)
+// (trk != null: mpc_closed_loop_track -- between the trigger and the masked solve the firing agents re-select their row
+// of the window table `cl` on the plant state, and traj_row records the row in force; trk == null launches nothing more)
+static int closed_loop_event_impl(const char *who_, mpc_handle *h, int B, int T, int shift, const double *w, double thr, int max_hold,
+                                  double *x, const double *cl, const int32_t *cl_index, double *U, double *lambda,
+                                  int32_t *held, const double *disturbance, double *traj_x, double *traj_u,
+                                  uint8_t *solved, int32_t *solve_count, int32_t *fail_count, double *stats, void *stream,
+                                  const mpc_track *trk, int32_t *cl_index_rw, int32_t *traj_row)
 {
-    int rc = check_trigger_args("mpc_closed_loop_event", w, thr, max_hold, held); if (rc) return rc;
-    if (T < 0) return fail(MPC_E_ARG, "mpc_closed_loop_event: negative T");
-    if (!h) return fail(MPC_E_ARG, "mpc_closed_loop_event: null handle");
-    rc = check_max_hold(h, "mpc_closed_loop_event", max_hold); if (rc) return rc;
-    rc = check_common(h, B, "mpc_closed_loop_event"); if (rc) return rc;
+    const std::string who(who_);
+    int rc = check_trigger_args(who_, w, thr, max_hold, held); if (rc) return rc;
+    if (T < 0) return fail(MPC_E_ARG, who + ": negative T");
+    if (!h) return fail(MPC_E_ARG, who + ": null handle");
+    rc = check_max_hold(h, who_, max_hold); if (rc) return rc;
+    rc = check_common(h, B, who_); if (rc) return rc;
+    if (trk) { rc = check_track(h, trk, who_); if (rc) return rc; }
     if (B == 0 || T == 0) return MPC_OK;
-    if (!x || !cl || !U) return fail(MPC_E_ARG, "mpc_closed_loop_event: null buffer");
+    if (!x || !cl || !U || (trk && !cl_index_rw)) return fail(MPC_E_ARG, who + ": null buffer");
     const DevCfg &c = h->dc;
-    if (c.m && !lambda) return fail(MPC_E_ARG, "mpc_closed_loop_event: lambda is required when m > 0");
-    rc = check_bound(h, B, "mpc_closed_loop_event"); if (rc) return rc;
-    rc = check_box_bound(h, B, "mpc_closed_loop_event"); if (rc) return rc;
-    rc = check_con_bound(h, B, "mpc_closed_loop_event"); if (rc) return rc;
+    if (c.m && !lambda) return fail(MPC_E_ARG, who + ": lambda is required when m > 0");
+    rc = check_bound(h, B, who_); if (rc) return rc;
+    rc = check_box_bound(h, B, who_); if (rc) return rc;
+    rc = check_con_bound(h, B, who_); if (rc) return rc;
     rc = reserve_event(h, B); if (rc) return rc;
     bool fresh = false;
     rc = reserve_xhat(h, B, &fresh); if (rc) return rc;
@@ -677,6 +765,9 @@ extern "C" int mpc_closed_loop_event(mpc_handle *h, int B, int T, int shift, con
     for (int t = 0; t < T; t++) {
         // (nominal states just allocated: every agent re-plans at the first step, whatever `held` says)
         launch_trigger(h, s, B, x, e.xhat, held, tw, thr, max_hold, fresh && t == 0, nullptr, e.fire, shift ? U : nullptr);
+        if (trk)
+            hipLaunchKernelGGL(track_select_kernel, grid_for(B, 64), dim3(64), 0, s, c, track_geom(trk), B, c.nx, x, cl, e.fire,
+                               near_for(h, cl), cl_index_rw, (int *)nullptr, traj_row, t, T);
         rc = solve_active_impl(h, B, e.fire, x, cl, cl_index, U, lambda, st, nullptr, s, false); if (rc) return rc;
         // bound table: the plant advances with row pidx_plant[b] (null: the controller's), the nominal state with pidx[b]
         with_model_table(h, h->pidx_plant ? h->pidx_plant : h->pidx, [&](auto MODEL, auto PA, auto... pt) {
@@ -691,7 +782,27 @@ extern "C" int mpc_closed_loop_event(mpc_handle *h, int B, int T, int shift, con
         });
     }
     HIPCHK(hipGetLastError());
-    return bounded_sync(h, s, "mpc_closed_loop_event");
+    return bounded_sync(h, s, who_);
+}
+extern "C" int mpc_closed_loop_event(mpc_handle *h, int B, int T, int shift, const double *w, double thr, int max_hold,
+                                     double *x, const double *cl, const int32_t *cl_index, double *U, double *lambda,
+                                     int32_t *held, const double *disturbance, double *traj_x, double *traj_u,
+                                     uint8_t *solved, int32_t *solve_count, int32_t *fail_count, double *stats, void *stream)
+{
+    return closed_loop_event_impl("mpc_closed_loop_event", h, B, T, shift, w, thr, max_hold, x, cl, cl_index, U, lambda, held,
+                                  disturbance, traj_x, traj_u, solved, solve_count, fail_count, stats, stream, nullptr, nullptr, nullptr);
+}
+
+// Lap driving: the event-triggered loop on a table of track windows, every firing agent re-selecting its row
+extern "C" int mpc_closed_loop_track(mpc_handle *h, int B, int T, int shift, const double *w, double thr, int max_hold,
+                                     double *x, const double *win, int32_t *cl_index, double *U, double *lambda,
+                                     int32_t *held, const double *disturbance, double *traj_x, double *traj_u,
+                                     uint8_t *solved, int32_t *solve_count, int32_t *fail_count, double *stats, void *stream,
+                                     const mpc_track *trk, int32_t *traj_row)
+{
+    if (!trk) return fail(MPC_E_ARG, "mpc_closed_loop_track: null track");
+    return closed_loop_event_impl("mpc_closed_loop_track", h, B, T, shift, w, thr, max_hold, x, win, cl_index, U, lambda, held,
+                                  disturbance, traj_x, traj_u, solved, solve_count, fail_count, stats, stream, trk, cl_index, traj_row);
 }
 
 extern "C" int mpc_last_speculation(mpc_handle *h, int64_t *issued, int64_t *used)

@@ -22,6 +22,31 @@ def _ptr(t):
 EventLoopResult = collections.namedtuple(
     "EventLoopResult", "x U lam held traj_x traj_u solved solve_count failures stats")
 
+# what BatchedMPC.closed_loop_track returns: the fields of EventLoopResult, then cl_index [B] int32 (each agent's row of
+# the window table on return: pass it to the next call) and traj_row [B, T] int32 (the row in force at every step)
+TrackLoopResult = collections.namedtuple(
+    "TrackLoopResult", EventLoopResult._fields + ("cl_index", "traj_row"))
+
+
+class Track:
+    """A table of track windows (BatchedMPC.track_windows): `win` [K * R, 2S], the window tensor -- an ordinary
+    centerline table, usable wherever one is --, `track` [K, 2L] it was gathered from and the geometry K, L, S, stride,
+    lead, closed, R (include/mpc_hip.h: mpc_track).  Holds both tensors alive."""
+
+    def __init__(self, geom, S, track, win):
+        self._c = geom
+        self.K, self.L, self.stride, self.lead = int(geom.K), int(geom.L), int(geom.stride), int(geom.lead)
+        self.closed, self.R, self.S = bool(geom.closed), int(geom.R), int(S)
+        self.track, self.win = track, win
+
+    @property
+    def rows(self):
+        return self.K * self.R
+
+    def __repr__(self):
+        return (f"Track(K={self.K}, L={self.L}, S={self.S}, stride={self.stride}, lead={self.lead}, "
+                f"closed={self.closed}, R={self.R})")
+
 
 class BatchedMPC:
     """One handle = one GPU.  All tensors are float64, contiguous, on `device`."""
@@ -475,6 +500,109 @@ class BatchedMPC:
             _ptr(lam), _ptr(held), _ptr(disturbance), _ptr(tx), _ptr(tu), _ptr(solved), _ptr(count), _ptr(fails),
             _ptr(stats), self._stream()))
         return EventLoopResult(x, U, lam, held, tx, tu, solved, count, fails, stats)
+
+    # ------------------------------------------------------------------ lap driving: windows of a track
+    def track_windows(self, track, stride, lead, closed):
+        """mpc_track_init + mpc_track_windows: cuts `track` [K, 2L] (or [2L]: one track; rows flat x.. then y.., a closed
+        track without a repeated closing point) into windows of S points every `stride` points and returns the Track
+        that holds them.  The nearest-point tables for the window table are prepared here, once (not for more than
+        1 024 windows: such a table takes the full scan -- the same results, slower)."""
+        self._free()
+        if isinstance(track, torch.Tensor) and track.dim() == 1:
+            track = track.unsqueeze(0)
+        if not isinstance(track, torch.Tensor) or track.dim() != 2 or track.shape[1] % 2:
+            raise ValueError("track: expected a tensor [K, 2L] (flat x.. then y..)")
+        self._chk(track, track.shape, "track")
+        K, L = int(track.shape[0]), int(track.shape[1]) // 2
+        geom = _lib.track_init(self.cfg, K, L, stride, lead, closed)
+        win = self._empty(K * int(geom.R), 2 * self.S)
+        _lib.check(self.lib.mpc_track_windows(self._h, C.byref(geom), _ptr(track), _ptr(win), self._stream()))
+        trk = Track(geom, self.S, track, win)
+        self._centerline(win, None, 0)
+        return trk
+
+    def _track(self, trk):
+        if not isinstance(trk, Track):
+            raise TypeError("expected the Track that track_windows returned")
+        if trk.S != self.S or trk.win.device != self.device:
+            raise ValueError("this Track was made by another engine (other S or device)")
+        return trk
+
+    def _pose(self, x):
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise ValueError(f"x: expected [B, {self.nx}]")
+        B = x.shape[0]
+        self._chk(x, (B, self.nx), "x")
+        return B
+
+    def track_locate(self, x, track_obj, track_index=None):
+        """mpc_track_locate: the first placement -- cl_index [B] int32, each agent's row of track_obj.win, from the
+        nearest point of its whole track (track_index [B] int32, None: track 0) to x[b, :2]."""
+        self._free()
+        trk, B = self._track(track_obj), self._pose(x)
+        if track_index is not None:
+            self._chk(track_index, (B,), "track_index", torch.int32)
+            if B and (int(track_index.min()) < 0 or int(track_index.max()) >= trk.K):
+                raise ValueError("track_index out of range")
+        ci = torch.zeros(B, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.mpc_track_locate(self._h, C.byref(trk._c), B, _ptr(x), _ptr(trk.track), _ptr(track_index),
+                                             _ptr(ci), self._stream()))
+        return ci
+
+    def track_select(self, x, track_obj, cl_index, active=None):
+        """mpc_track_select: (cl_index [B] int32, pos [B] int32) -- the rows after re-selection from x[b, :2] and the
+        track point each agent stands at.  Agents with active[b] == 0 (int32 or bool [B]; None: all active) and agents
+        whose x or y is not finite keep their row; their pos is -1.  Returns copies."""
+        trk, B = self._track(track_obj), self._pose(x)
+        win = self._centerline(trk.win, cl_index, B)
+        if isinstance(active, torch.Tensor) and active.dtype == torch.bool:
+            active = active.to(torch.int32)
+        if active is not None:
+            self._chk(active, (B,), "active", torch.int32)
+        ci = cl_index.clone()
+        pos = torch.full((B,), -1, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.mpc_track_select(self._h, C.byref(trk._c), B, _ptr(x), _ptr(win), _ptr(active), _ptr(ci),
+                                             _ptr(pos), self._stream()))
+        return ci, pos
+
+    def closed_loop_track(self, x, track_obj, U, T, w, thr, max_hold, cl_index, held=None, lam=None, shift=False,
+                          disturbance=None, stats=None):
+        """mpc_closed_loop_track: closed_loop_event on the windows of a track -- at every step the agents that re-plan
+        first re-select their row of track_obj.win from the plant state; an agent that holds its plan keeps the row the
+        plan was solved on.  cl_index [B] int32: the rows to start from (track_locate; or the cl_index of an earlier
+        result, with its U / held / lam / stats, to continue).  Returns a TrackLoopResult (copies; the arguments are
+        not written)."""
+        trk = self._track(track_obj)
+        B, T = x.shape[0], int(T)
+        self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
+        thr, max_hold = self._trigger_args(thr, max_hold)
+        if T < 0:
+            raise ValueError("T must be >= 0")
+        if cl_index is None:
+            raise ValueError("cl_index: the rows to start from are required (track_locate)")
+        win = self._centerline(trk.win, cl_index, B)
+        x, U, ci = x.clone(), U.clone(), cl_index.clone()
+        held = torch.full((B,), -1, dtype=torch.int32, device=self.device) if held is None else held.clone()
+        self._chk(held, (B,), "held", torch.int32)
+        if self.m:
+            lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None else lam.clone()
+            self._chk(lam, (B, self.m), "lam")
+        else:
+            lam = None
+        if disturbance is not None:
+            self._chk(disturbance, (B, T, self.nx), "disturbance")
+        stats = torch.zeros(B, _lib.NSTATS, dtype=torch.float64, device=self.device) if stats is None else stats.clone()
+        self._chk(stats, (B, _lib.NSTATS), "stats")
+        tx, tu = self._empty(B, T, self.nx), self._empty(B, T, 2)
+        solved = torch.zeros(B, T, dtype=torch.uint8, device=self.device)
+        count = torch.zeros(B, dtype=torch.int32, device=self.device)
+        fails = torch.zeros(B, dtype=torch.int32, device=self.device)
+        rows = torch.zeros(B, T, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.mpc_closed_loop_track(
+            self._h, B, T, int(bool(shift)), self._weights(w), thr, max_hold, _ptr(x), _ptr(win), _ptr(ci), _ptr(U),
+            _ptr(lam), _ptr(held), _ptr(disturbance), _ptr(tx), _ptr(tu), _ptr(solved), _ptr(count), _ptr(fails),
+            _ptr(stats), self._stream(), C.byref(trk._c), _ptr(rows)))
+        return TrackLoopResult(x, U, lam, held, tx, tu, solved, count, fails, stats, ci, rows)
 
     def lane_payoff(self, ego, cars, ncars, params):
         """f-3: out[B, 2, 4] = target lane 1, 2 -> [total, safety, velocity, comfort] (game_theory.py:115-244)."""
