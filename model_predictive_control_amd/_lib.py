@@ -217,113 +217,94 @@ def default_config(model=MODEL_PACEJKA, N=12, **overrides):
     return cfg
 
 
-def default_params(cfg):
-    """mpc_default_params: the row of the per-agent parameter table that `cfg` describes, float64 [NPARAM]."""
+def _default_row(fn, width, cfg):
+    """The row of a per-agent table that `cfg` describes (library function `fn`), float64 [width]."""
     import numpy as np
-    row = (C.c_double * NPARAM)()
-    rc = load().mpc_default_params(C.byref(cfg), row)
+    row = (C.c_double * width)()
+    rc = getattr(load(), fn)(C.byref(cfg), row)
     if rc != 0:
         raise ValueError(load().mpc_last_error().decode())
     return np.array(row[:], dtype=np.float64)
+
+
+def _default_table(who, default, cfg, P):
+    """float64 [P, width] whose rows are default(cfg)"""
+    import numpy as np
+    if int(P) < 1:
+        raise ValueError(f"{who}: P must be >= 1")
+    return np.tile(default(cfg), (int(P), 1))
+
+
+def _set_field(who, tab, name, val, off, widths):
+    """Writes field `name` (columns from `off`) of the table from an every-row value -- a scalar where widths is (1,),
+    else [w] -- or a per-row one -- [P], else [P, w] -- with w one of `widths`."""
+    import numpy as np
+    P = tab.shape[0]
+    v = np.asarray(val, dtype=np.float64)
+    if widths == (1,):
+        if v.ndim == 0:
+            v = np.full(P, float(v))
+        if v.shape != (P,):
+            raise ValueError(f"{who}: {name} must be a scalar or have shape ({P},), got {np.shape(val)}")
+        tab[:, off] = v
+        return
+    if v.ndim == 1:
+        v = np.tile(v, (P, 1))
+    if v.ndim != 2 or v.shape[0] != P or v.shape[1] not in widths:
+        shapes = [f"({w},)" for w in widths] + [f"({P}, {w})" for w in widths]
+        raise ValueError(f"{who}: {name} must have shape {', '.join(shapes[:-1])} or {shapes[-1]}, got {np.shape(val)}")
+    tab[:, off:off + v.shape[1]] = v
+
+
+def default_params(cfg):
+    """mpc_default_params: the row of the per-agent parameter table that `cfg` describes, float64 [NPARAM]."""
+    return _default_row("mpc_default_params", NPARAM, cfg)
 
 
 def param_rows(cfg, P, **overrides):
     """A parameter table for BatchedMPC.set_agent_params, on the host: float64 [P, NPARAM] whose rows are
     default_params(cfg) with overrides by field name -- `veh` [P, 22] (or [22]: every row), `cost_w` [P, 6] (or [6]),
     `accel`, `friction`, `v_ref` [P] (or a scalar).  Pure host code: usable without a GPU."""
-    import numpy as np
-    P = int(P)
-    if P < 1:
-        raise ValueError("param_rows: P must be >= 1")
-    tab = np.tile(default_params(cfg), (P, 1))
+    tab = _default_table("param_rows", default_params, cfg, P)
     for name, val in overrides.items():
         if name not in PARAM_FIELDS:
             raise ValueError(f"param_rows: unknown field {name!r} (one of {sorted(PARAM_FIELDS)})")
         off, width = PARAM_FIELDS[name]
-        v = np.asarray(val, dtype=np.float64)
-        if width == 1:
-            if v.ndim == 0:
-                v = np.full(P, float(v))
-            if v.shape != (P,):
-                raise ValueError(f"param_rows: {name} must be a scalar or have shape ({P},), got {v.shape}")
-            tab[:, off] = v
-        else:
-            if v.shape == (width,):
-                v = np.tile(v, (P, 1))
-            if v.shape != (P, width):
-                raise ValueError(f"param_rows: {name} must have shape ({width},) or ({P}, {width}), got {v.shape}")
-            tab[:, off:off + width] = v
+        _set_field("param_rows", tab, name, val, off, (width,))
     return tab
 
 
 def default_bounds(cfg):
     """mpc_default_bounds: the row of the per-agent bounds table that `cfg` describes, float64 [NBOUND]."""
-    import numpy as np
-    row = (C.c_double * NBOUND)()
-    rc = load().mpc_default_bounds(C.byref(cfg), row)
-    if rc != 0:
-        raise ValueError(load().mpc_last_error().decode())
-    return np.array(row[:], dtype=np.float64)
+    return _default_row("mpc_default_bounds", NBOUND, cfg)
 
 
 def bound_rows(cfg, P, u_lb=None, u_ub=None):
     """A bounds table for BatchedMPC.set_agent_bounds, on the host: float64 [P, NBOUND] whose rows are
     default_bounds(cfg) with `u_lb` / `u_ub` [P, 2] (or [2]: every row) in their place.  Pure host code: usable
     without a GPU."""
-    import numpy as np
-    P = int(P)
-    if P < 1:
-        raise ValueError("bound_rows: P must be >= 1")
-    tab = np.tile(default_bounds(cfg), (P, 1))
+    tab = _default_table("bound_rows", default_bounds, cfg, P)
     for name, val, off in (("u_lb", u_lb, 0), ("u_ub", u_ub, 2)):
-        if val is None:
-            continue
-        v = np.asarray(val, dtype=np.float64)
-        if v.shape == (2,):
-            v = np.tile(v, (P, 1))
-        if v.shape != (P, 2):
-            raise ValueError(f"bound_rows: {name} must have shape (2,) or ({P}, 2), got {v.shape}")
-        tab[:, off:off + 2] = v
+        if val is not None:
+            _set_field("bound_rows", tab, name, val, off, (2,))
     return tab
 
 
 def default_constraints(cfg):
     """mpc_default_constraints: the row of the per-agent constraint table that `cfg` describes, float64 [NCONSTR]."""
-    import numpy as np
-    row = (C.c_double * NCONSTR)()
-    rc = load().mpc_default_constraints(C.byref(cfg), row)
-    if rc != 0:
-        raise ValueError(load().mpc_last_error().decode())
-    return np.array(row[:], dtype=np.float64)
+    return _default_row("mpc_default_constraints", NCONSTR, cfg)
 
 
 def constraint_rows(cfg, P, g_off=None, D_lb=None, D_ub=None, lane_halfwidth=None):
     """A constraint table for BatchedMPC.set_agent_constraints, on the host: float64 [P, NCONSTR] whose rows are
     default_constraints(cfg) with `g_off` / `D_lb` / `D_ub` [P, k] (or [k]: every row; k = nx or 6 leading entries) and
     `lane_halfwidth` [P] (or a scalar) in their place.  Pure host code: usable without a GPU."""
-    import numpy as np
-    P = int(P)
-    if P < 1:
-        raise ValueError("constraint_rows: P must be >= 1")
-    tab = np.tile(default_constraints(cfg), (P, 1))
+    tab = _default_table("constraint_rows", default_constraints, cfg, P)
     nx = 6 if cfg.model == MODEL_PACEJKA else 4
-    for name, val in (("g_off", g_off), ("D_lb", D_lb), ("D_ub", D_ub)):
-        if val is None:
-            continue
-        off = CONSTR_FIELDS[name][0]
-        v = np.asarray(val, dtype=np.float64)
-        if v.ndim == 1:
-            v = np.tile(v, (P, 1))
-        if v.ndim != 2 or v.shape[0] != P or v.shape[1] not in (nx, 6):
-            raise ValueError(f"constraint_rows: {name} must have shape ({nx},), (6,), ({P}, {nx}) or ({P}, 6), got {np.shape(val)}")
-        tab[:, off:off + v.shape[1]] = v
-    if lane_halfwidth is not None:
-        v = np.asarray(lane_halfwidth, dtype=np.float64)
-        if v.ndim == 0:
-            v = np.full(P, float(v))
-        if v.shape != (P,):
-            raise ValueError(f"constraint_rows: lane_halfwidth must be a scalar or have shape ({P},), got {v.shape}")
-        tab[:, CONSTR_FIELDS["lane_halfwidth"][0]] = v
+    for name, val, widths in (("g_off", g_off, (nx, 6)), ("D_lb", D_lb, (nx, 6)), ("D_ub", D_ub, (nx, 6)),
+                              ("lane_halfwidth", lane_halfwidth, (1,))):
+        if val is not None:
+            _set_field("constraint_rows", tab, name, val, CONSTR_FIELDS[name][0], widths)
     return tab
 
 

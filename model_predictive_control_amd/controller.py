@@ -123,42 +123,25 @@ class MPCController:
             cl_index = torch.as_tensor(cl_index, dtype=torch.int32, device=dev).contiguous()
         if lam0 is not None:
             lam0 = torch.as_tensor(lam0, dtype=torch.float64, device=dev).contiguous()
-        if params is None and param_index is not None:
-            raise ValueError("param_index needs params")
-        if params is not None:
-            params = torch.as_tensor(params, dtype=torch.float64, device=dev).contiguous()
-            if param_index is None:
-                param_index = torch.arange(B, device=dev) % params.shape[0]
-            param_index = torch.as_tensor(param_index, device=dev).to(torch.int32).contiguous()
-        if bounds is None and bound_index is not None:
-            raise ValueError("bound_index needs bounds")
-        if bounds is not None:
-            bounds = torch.as_tensor(bounds, dtype=torch.float64, device=dev).contiguous()
-            if bound_index is None:
-                bound_index = torch.arange(B, device=dev) % bounds.shape[0]
-            bound_index = torch.as_tensor(bound_index, device=dev).to(torch.int32).contiguous()
-        if constraints is None and constraint_index is not None:
-            raise ValueError("constraint_index needs constraints")
-        if constraints is not None:
-            constraints = torch.as_tensor(constraints, dtype=torch.float64, device=dev).contiguous()
-            if constraint_index is None:
-                constraint_index = torch.arange(B, device=dev) % constraints.shape[0]
-            constraint_index = torch.as_tensor(constraint_index, device=dev).to(torch.int32).contiguous()
+        tables = []                                       # (kind, table, index) of the tables this call binds
+        for kind, table, index, name in (("params", params, param_index, "param_index"),
+                                         ("bounds", bounds, bound_index, "bound_index"),
+                                         ("constraints", constraints, constraint_index, "constraint_index")):
+            if table is None:
+                if index is not None:
+                    raise ValueError(f"{name} needs {kind}")
+                continue
+            table = torch.as_tensor(table, dtype=torch.float64, device=dev).contiguous()
+            if index is None:
+                index = torch.arange(B, device=dev) % table.shape[0]
+            tables.append((kind, table, torch.as_tensor(index, device=dev).to(torch.int32).contiguous()))
         try:
-            if params is not None:
-                self.solver.set_agent_params(params, param_index)
-            if bounds is not None:
-                self.solver.set_agent_bounds(bounds, bound_index)
-            if constraints is not None:
-                self.solver.set_agent_constraints(constraints, constraint_index)
+            for kind, table, index in tables:
+                getattr(self.solver, "set_agent_" + kind)(table, index)
             U, lam, stats = self.solver.solve(Y0, cl, U0, lam0 if self._constrained else None, cl_index)
         finally:
-            if params is not None:
-                self.solver.clear_agent_params()
-            if bounds is not None:
-                self.solver.clear_agent_bounds()
-            if constraints is not None:
-                self.solver.clear_agent_constraints()
+            for kind, _, _ in tables:
+                getattr(self.solver, "clear_agent_" + kind)()
         self.last_stats = stats
         self.tot_it += int(stats[:, 2].sum().item())
         self.failures += int((stats[:, 0] != _lib.ST_CONVERGED).sum().item())

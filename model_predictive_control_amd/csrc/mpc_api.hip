@@ -1,6 +1,6 @@
 // mpc_api.hip -- the C-ABI of libmpc_hip.so (see include/mpc_hip.h): the extern "C" entry points of the batched MPC
 // solve on one MI355X, one process / one handle per GPU.  The one translation unit of the library: the host side is in
-// mpc_handle.hpp (the handle), mpc_launch.hpp (which kernel instantiation a launch takes) and mpc_rounds.hpp (the
+// mpc_handle.hpp (the handle and its per-agent tables), mpc_launch.hpp (which kernel instantiation a launch takes) and mpc_rounds.hpp (the
 // round loop of a solve), the kernels in the headers those include (and mpc_track.hpp: the kernels of lap driving).
 #include "mpc_rounds.hpp"
 #include "mpc_track.hpp"
@@ -170,34 +170,6 @@ extern "C" int mpc_centerline_blocks(mpc_handle *h, const double *cl, int C, voi
     return MPC_OK;
 }
 
-// Binds (table != NULL) or unbinds the per-agent parameter table.  The rows are checked once, here, through a
-// synchronous copy (binding is not on the hot path; rows rewritten in place later are the caller's to keep valid):
-// what the model divides by must be positive and everything finite.  Nothing else is done: the kernels read the
-// caller's memory at every call.
-extern "C" int mpc_set_agent_params(mpc_handle *h, const double *table, int P, const int32_t *index,
-                                    const int32_t *plant_index, int B)
-{
-    { const int rb = refuse_if_busy(h, "mpc_set_agent_params"); if (rb) return rb; }
-    if (!table) { h->ptab = nullptr; h->pidx = h->pidx_plant = nullptr; h->ptab_rows = h->ptab_B = 0; return MPC_OK; }
-    if (P < 1 || B < 1 || !index) return fail(MPC_E_ARG, "mpc_set_agent_params: need P >= 1 rows, B >= 1 agents and an index");
-    { const int ra = check_tables_agree(h, B, "mpc_set_agent_params", 0); if (ra) return ra; }
-    HIPCHK(hipSetDevice(h->device));
-    std::vector<double> rows((size_t)P * MPC_NPARAM);
-    HIPCHK(hipMemcpy(rows.data(), table, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int p = 0; p < P; p++) {
-        const double *r = rows.data() + (size_t)p * MPC_NPARAM;
-        for (int i = 0; i < MPC_NPARAM; i++)
-            if (!std::isfinite(r[i]))
-                return fail(MPC_E_ARG, "mpc_set_agent_params: row " + std::to_string(p) + ", value " + std::to_string(i) + " is not finite");
-        if (!(r[1] + r[2] > 0.0))
-            return fail(MPC_E_ARG, "mpc_set_agent_params: row " + std::to_string(p) + ": lf + lr (veh[1] + veh[2]) must be positive");
-        if (h->cfg.model == MPC_MODEL_PACEJKA && (!(r[7] > 0.0) || !(r[8] > 0.0)))
-            return fail(MPC_E_ARG, "mpc_set_agent_params: row " + std::to_string(p) + ": mass and inertia (veh[7], veh[8]) must be positive");
-    }
-    h->ptab = table; h->ptab_rows = P; h->pidx = index; h->pidx_plant = plant_index; h->ptab_B = B;
-    return MPC_OK;
-}
-
 // the handle's own one-row parameter and box tables and an index of B zeros (see mpc_handle::own_ptab)
 static int reserve_own_tables(mpc_handle *h, int B, const char *who)
 {
@@ -218,55 +190,76 @@ static int reserve_own_tables(mpc_handle *h, int B, const char *who)
     return MPC_OK;
 }
 
-// Binds (table != NULL) or unbinds the per-agent table of input boxes, as mpc_set_agent_params binds the parameter
-// table: the rows are checked once, here, through a synchronous copy, by the rule mpc_create applies to the handle's
-// box; the kernels read the caller's memory at every call.
-extern "C" int mpc_set_agent_bounds(mpc_handle *h, const double *table, int P, const int32_t *index, int B)
+// What a row of each kind must satisfy to be bound (`where`: "<setter>: row <p>", the head of the refusal) -- the one
+// real difference between the three setters.
+// parameters: what the model divides by must be positive and everything finite
+static int param_row_rule(const mpc_handle *h, const double *r, const std::string &where)
 {
-    { const int rb = refuse_if_busy(h, "mpc_set_agent_bounds"); if (rb) return rb; }
-    if (!table) { h->btab = nullptr; h->bidx = nullptr; h->btab_rows = h->btab_B = 0; return MPC_OK; }
-    if (P < 1 || B < 1 || !index) return fail(MPC_E_ARG, "mpc_set_agent_bounds: need P >= 1 rows, B >= 1 agents and an index");
-    { const int ra = check_tables_agree(h, B, "mpc_set_agent_bounds", 1); if (ra) return ra; }
-    HIPCHK(hipSetDevice(h->device));
-    std::vector<double> rows((size_t)P * MPC_NBOUND);
-    HIPCHK(hipMemcpy(rows.data(), table, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int p = 0; p < P; p++)
-        if (!box_ok(rows.data() + (size_t)p * MPC_NBOUND, rows.data() + (size_t)p * MPC_NBOUND + 2))
-            return fail(MPC_E_ARG, "mpc_set_agent_bounds: row " + std::to_string(p) + ": u_lb must not exceed u_ub");
-    { const int ro = reserve_own_tables(h, B, "mpc_set_agent_bounds"); if (ro) return ro; }
-    h->btab = table; h->btab_rows = P; h->bidx = index; h->btab_B = B;
+    for (int i = 0; i < MPC_NPARAM; i++)
+        if (!std::isfinite(r[i])) return fail(MPC_E_ARG, where + ", value " + std::to_string(i) + " is not finite");
+    if (!(r[1] + r[2] > 0.0)) return fail(MPC_E_ARG, where + ": lf + lr (veh[1] + veh[2]) must be positive");
+    if (h->cfg.model == MPC_MODEL_PACEJKA && (!(r[7] > 0.0) || !(r[8] > 0.0)))
+        return fail(MPC_E_ARG, where + ": mass and inertia (veh[7], veh[8]) must be positive");
+    return MPC_OK;
+}
+// input boxes: the rule mpc_create applies to the handle's box
+static int box_row_rule(const mpc_handle *, const double *r, const std::string &where)
+{
+    return box_ok(r, r + 2) ? MPC_OK : fail(MPC_E_ARG, where + ": u_lb must not exceed u_ub");
+}
+// constraint data: the fields the handle's constr_mode reads
+static int constr_row_rule(const mpc_handle *h, const double *r, const std::string &where)
+{
+    if (h->cfg.constr_mode == MPC_CONSTR_LANE)
+        return std::isfinite(r[18]) && r[18] > 0.0 ? MPC_OK : fail(MPC_E_ARG, where + ": lane_halfwidth must be finite and positive");
+    for (int i = 0; i < mpc_nx(&h->cfg); i++) {
+        if (!std::isfinite(r[i])) return fail(MPC_E_ARG, where + ": g_off[" + std::to_string(i) + "] is not finite");
+        if (!(r[6 + i] <= r[12 + i])) return fail(MPC_E_ARG, where + ": D_lb must not exceed D_ub");
+    }
     return MPC_OK;
 }
 
-// Binds (table != NULL) or unbinds the per-agent table of constraint data, as mpc_set_agent_bounds binds the boxes: the
-// rows are checked once, here, through a synchronous copy; the kernels read the caller's memory at every call.
+// Binds (table != NULL) or unbinds the per-agent table of one kind.  The rows are checked once, here, through a
+// synchronous copy (binding is not on the hot path; rows rewritten in place later are the caller's to keep valid).
+// Nothing else is done: the kernels read the caller's memory at every call.  The box and constraint forms of some
+// kernels exist beside the parameter (and box) form alone: binding either makes the handle's own one-row tables.
+static int bind_agent_table(mpc_handle *h, TableKind kind, const double *table, int P, const int32_t *index, int B,
+                            int (*row_rule)(const mpc_handle *, const double *, const std::string &))
+{
+    const char *who = k_tables[kind].setter;
+    const size_t width = (size_t)k_tables[kind].width;
+    { const int rb = refuse_if_busy(h, who); if (rb) return rb; }
+    if (!table) { h->tab[kind] = BoundTable{}; return MPC_OK; }
+    if (kind == TAB_CONSTR && h->cfg.constr_mode == MPC_CONSTR_NONE)
+        return fail(MPC_E_ARG, std::string(who) + ": the handle has no general constraints (constr_mode MPC_CONSTR_NONE)");
+    if (P < 1 || B < 1 || !index) return fail(MPC_E_ARG, std::string(who) + ": need P >= 1 rows, B >= 1 agents and an index");
+    { const int ra = check_tables_agree(h, B, who, kind); if (ra) return ra; }
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<double> rows((size_t)P * width);
+    HIPCHK(hipMemcpy(rows.data(), table, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int p = 0; p < P; p++) {
+        const int rr = row_rule(h, rows.data() + (size_t)p * width, std::string(who) + ": row " + std::to_string(p));
+        if (rr) return rr;
+    }
+    if (kind != TAB_PARAMS) { const int ro = reserve_own_tables(h, B, who); if (ro) return ro; }
+    h->tab[kind] = BoundTable{table, index, P, B};
+    return MPC_OK;
+}
+
+extern "C" int mpc_set_agent_params(mpc_handle *h, const double *table, int P, const int32_t *index,
+                                    const int32_t *plant_index, int B)
+{
+    const int rc = bind_agent_table(h, TAB_PARAMS, table, P, index, B, param_row_rule);
+    if (rc == MPC_OK) h->pidx_plant = table ? plant_index : nullptr;
+    return rc;
+}
+extern "C" int mpc_set_agent_bounds(mpc_handle *h, const double *table, int P, const int32_t *index, int B)
+{
+    return bind_agent_table(h, TAB_BOX, table, P, index, B, box_row_rule);
+}
 extern "C" int mpc_set_agent_constraints(mpc_handle *h, const double *table, int P, const int32_t *index, int B)
 {
-    { const int rb = refuse_if_busy(h, "mpc_set_agent_constraints"); if (rb) return rb; }
-    if (!table) { h->ctab = nullptr; h->cidx = nullptr; h->ctab_rows = h->ctab_B = 0; return MPC_OK; }
-    if (h->cfg.constr_mode == MPC_CONSTR_NONE)
-        return fail(MPC_E_ARG, "mpc_set_agent_constraints: the handle has no general constraints (constr_mode MPC_CONSTR_NONE)");
-    if (P < 1 || B < 1 || !index) return fail(MPC_E_ARG, "mpc_set_agent_constraints: need P >= 1 rows, B >= 1 agents and an index");
-    { const int ra = check_tables_agree(h, B, "mpc_set_agent_constraints", 2); if (ra) return ra; }
-    HIPCHK(hipSetDevice(h->device));
-    std::vector<double> rows((size_t)P * MPC_NCONSTR);
-    HIPCHK(hipMemcpy(rows.data(), table, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
-    const int nx = mpc_nx(&h->cfg);
-    for (int p = 0; p < P; p++) {
-        const double *r = rows.data() + (size_t)p * MPC_NCONSTR;
-        const std::string where = "mpc_set_agent_constraints: row " + std::to_string(p);
-        if (h->cfg.constr_mode == MPC_CONSTR_LANE) {
-            if (!std::isfinite(r[18]) || !(r[18] > 0.0)) return fail(MPC_E_ARG, where + ": lane_halfwidth must be finite and positive");
-            continue;
-        }
-        for (int i = 0; i < nx; i++) {
-            if (!std::isfinite(r[i])) return fail(MPC_E_ARG, where + ": g_off[" + std::to_string(i) + "] is not finite");
-            if (!(r[6 + i] <= r[12 + i])) return fail(MPC_E_ARG, where + ": D_lb must not exceed D_ub");
-        }
-    }
-    { const int ro = reserve_own_tables(h, B, "mpc_set_agent_constraints"); if (ro) return ro; }
-    h->ctab = table; h->ctab_rows = P; h->cidx = index; h->ctab_B = B;
-    return MPC_OK;
+    return bind_agent_table(h, TAB_CONSTR, table, P, index, B, constr_row_rule);
 }
 
 extern "C" int mpc_rhs(mpc_handle *h, int B, const double *x, const double *u, double *dx, void *stream)
@@ -274,9 +267,9 @@ extern "C" int mpc_rhs(mpc_handle *h, int B, const double *x, const double *u, d
     int rc = check_common(h, B, "mpc_rhs"); if (rc) return rc;
     if (B == 0) return MPC_OK;
     if (!x || !u || !dx) return fail(MPC_E_ARG, "mpc_rhs: null buffer");
-    rc = check_bound(h, B, "mpc_rhs"); if (rc) return rc;
+    rc = check_tables(h, B, "mpc_rhs", READS_PARAMS); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    with_model_table(h, h->pidx, [&](auto MODEL, auto PA, auto... pt) {
+    with_model_table(h, h->params().idx, [&](auto MODEL, auto PA, auto... pt) {
         hipLaunchKernelGGL((rhs_kernel<MODEL(), PA(), decltype(pt)...>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, x, u, dx, pt...);
     });
     HIPCHK(hipGetLastError());
@@ -289,9 +282,9 @@ extern "C" int mpc_rollout(mpc_handle *h, int B, int Nsim, const double *x0, con
     int rc = check_common(h, B, "mpc_rollout"); if (rc) return rc;
     if (B == 0 || Nsim == 0) return MPC_OK;
     if (Nsim < 0 || !x0 || !U || !X) return fail(MPC_E_ARG, "mpc_rollout: bad argument");
-    rc = check_bound(h, B, "mpc_rollout"); if (rc) return rc;
+    rc = check_tables(h, B, "mpc_rollout", READS_PARAMS); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    with_model_table(h, h->pidx, [&](auto MODEL, auto PA, auto... pt) {
+    with_model_table(h, h->params().idx, [&](auto MODEL, auto PA, auto... pt) {
         hipLaunchKernelGGL((simulate_kernel<MODEL(), PA(), decltype(pt)...>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, Nsim, x0, U, X, pt...);
     });
     HIPCHK(hipGetLastError());
@@ -342,9 +335,9 @@ extern "C" int mpc_stage_cost(mpc_handle *h, int B, const double *x, const doubl
     int rc = check_common(h, B, "mpc_stage_cost"); if (rc) return rc;
     if (B == 0) return MPC_OK;
     if (!x || !u || !cl || !out) return fail(MPC_E_ARG, "mpc_stage_cost: null buffer");
-    rc = check_bound(h, B, "mpc_stage_cost"); if (rc) return rc;
+    rc = check_tables(h, B, "mpc_stage_cost", READS_PARAMS); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    with_model_table(h, h->pidx, [&](auto MODEL, auto PA, auto... pt) {
+    with_model_table(h, h->params().idx, [&](auto MODEL, auto PA, auto... pt) {
         hipLaunchKernelGGL((stage_cost_kernel<MODEL(), PA(), decltype(pt)...>), grid_for(B, 64), dim3(64), 0, s,
                            h->dc, B, x, u, cl, cl_index, out, pt...);
     });
@@ -361,8 +354,7 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     if (!x0 || !cl || !U || !psi) return fail(MPC_E_ARG, "mpc_eval_cost_grad: null buffer");
     const DevCfg &c = h->dc;
     if (c.m && (!y || !Sigma)) return fail(MPC_E_ARG, "mpc_eval_cost_grad: y and Sigma are required when m > 0");
-    rc = check_bound(h, B, "mpc_eval_cost_grad"); if (rc) return rc;
-    rc = check_con_bound(h, B, "mpc_eval_cost_grad"); if (rc) return rc;
+    rc = check_tables(h, B, "mpc_eval_cost_grad", READS_PARAMS | READS_CONSTR); if (rc) return rc;
     rc = reserve(h, B); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     // direct mode: the kernel reads and writes the caller's agent-major buffers in place
@@ -372,8 +364,8 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     w.y = const_cast<double *>(y); w.Sig = c.m ? const_cast<double *>(Sigma) : h->ws.ws_Sig;
     w.yhe = (yhat && c.m) ? yhat : h->ws.ws_yhe;
     w.psi_direct = psi;
-    w.ptab = h->ptab; w.pidx = h->pidx;
-    w.ctab = h->ctab; w.cidx = h->cidx;
+    w.ptab = h->params().table; w.pidx = h->params().idx;
+    w.ctab = h->tab[TAB_CONSTR].table; w.cidx = h->tab[TAB_CONSTR].idx;
     if (wave_path) launch_solo_eval(h, w, s, grad ? 1 : 0);
     else launch_eval(h, w, s, nullptr, nullptr, grad ? B : 0, grad ? 0 : B);
     HIPCHK(hipGetLastError());
@@ -396,10 +388,10 @@ extern "C" int mpc_prox_step(mpc_handle *h, int B, const double *x, const double
     int rc = check_common(h, B, "mpc_prox_step"); if (rc) return rc;
     if (B == 0) return MPC_OK;
     if (!x || !grad || !gamma || !out) return fail(MPC_E_ARG, "mpc_prox_step: null buffer");
-    rc = check_box_bound(h, B, "mpc_prox_step"); if (rc) return rc;
-    if (h->btab)
+    rc = check_tables(h, B, "mpc_prox_step", READS_BOX); if (rc) return rc;
+    if (const BoundTable &box = h->tab[TAB_BOX]; box.table)
         hipLaunchKernelGGL(prox_box_kernel, grid_for(B, 64), dim3(64), 0, (hipStream_t)stream, h->dc, B, x, grad, gamma, xhat, p, out,
-                           BoxTab{h->btab, h->bidx});
+                           BoxTab{box.table, box.idx});
     else
         hipLaunchKernelGGL(prox_kernel, grid_for(B, 64), dim3(64), 0, (hipStream_t)stream, h->dc, B, x, grad, gamma, xhat, p, out);
     HIPCHK(hipGetLastError());
@@ -434,19 +426,20 @@ extern "C" int mpc_step_lds_plan(int n, int M, int m, int chain, int lds_pairs, 
     return MPC_OK;
 }
 
-// the solve proper on B agents whose parameter rows (table bound) are pidx[b] and whose boxes (bounds table bound) are
-// rows bidx[b] and whose constraint data (constraint table bound) are rows cidx[b]: the caller's batch and the handle's
-// bound indices (mpc_solve_batch), or the gathered rows of a masked solve and their gathered indices
-static int solve_core(mpc_handle *h, int B, const double *x0, const double *cl, const int32_t *cl_index, const int32_t *pidx,
-                      const int32_t *bidx, const int32_t *cidx, double *U, double *lambda, double *stats, hipStream_t s)
+// the solve proper on B agents whose rows of the bound tables are idx.of[kind][b] (a kind with no table bound: not
+// read): the caller's batch and the handle's bound indices (mpc_solve_batch), or the gathered rows of a masked solve and
+// their gathered indices
+static int solve_core(mpc_handle *h, int B, const double *x0, const double *cl, const int32_t *cl_index, const AgentIdx &idx,
+                      double *U, double *lambda, double *stats, hipStream_t s)
 {
     int rc = reserve(h, B); if (rc) return rc;
     WorkspaceHost &w = h->ws;
     w.cl = cl; w.cl_index = cl_index; w.x0 = x0; w.xo = U; w.y = lambda; w.psi_direct = nullptr;
     w.near = near_for(h, cl);
-    w.ptab = h->ptab; w.pidx = pidx;
-    w.btab = h->btab; w.bidx = h->btab ? bidx : nullptr;
-    w.ctab = h->ctab; w.cidx = h->ctab ? cidx : nullptr;
+    const auto rows_of = [&](TableKind k) { return h->tab[k].table ? idx.of[k] : nullptr; };
+    w.ptab = h->tab[TAB_PARAMS].table; w.pidx = rows_of(TAB_PARAMS);
+    w.btab = h->tab[TAB_BOX].table; w.bidx = rows_of(TAB_BOX);
+    w.ctab = h->tab[TAB_CONSTR].table; w.cidx = rows_of(TAB_CONSTR);
     w.xe = w.ws_xe; w.ge = w.ws_ge; w.yhe = w.ws_yhe; w.Sig = w.ws_Sig;
     rc = run_solver(h, s); if (rc) return rc;
     if (stats) hipLaunchKernelGGL(stats_kernel, grid_for(B, 256), dim3(256), 0, s, w, stats);
@@ -460,10 +453,8 @@ static int solve_batch_impl(mpc_handle *h, int B, const double *x0, const double
     if (B == 0) return MPC_OK;
     if (!x0 || !cl || !U) return fail(MPC_E_ARG, "mpc_solve_batch: null buffer");
     if (h->dc.m && !lambda) return fail(MPC_E_ARG, "mpc_solve_batch: lambda is required when m > 0");
-    rc = check_bound(h, B, "mpc_solve_batch"); if (rc) return rc;
-    rc = check_box_bound(h, B, "mpc_solve_batch"); if (rc) return rc;
-    rc = check_con_bound(h, B, "mpc_solve_batch"); if (rc) return rc;
-    return solve_core(h, B, x0, cl, cl_index, h->pidx, h->bidx, h->cidx, U, lambda, stats, (hipStream_t)stream);
+    rc = check_tables(h, B, "mpc_solve_batch", READS_ALL); if (rc) return rc;
+    return solve_core(h, B, x0, cl, cl_index, h->bound_rows(), U, lambda, stats, (hipStream_t)stream);
 }
 extern "C" int mpc_solve_batch(mpc_handle *h, int B, const double *x0, const double *cl, const int32_t *cl_index, double *U,
                                double *lambda, double *stats, void *stream)
@@ -529,9 +520,7 @@ extern "C" int mpc_closed_loop(mpc_handle *h, int B, int T, int shift, double *x
     if (T < 0 || !x || !cl || !U) return fail(MPC_E_ARG, "mpc_closed_loop: bad argument");
     const DevCfg &c = h->dc;
     if (c.m && !lambda) return fail(MPC_E_ARG, "mpc_closed_loop: lambda is required when m > 0");
-    rc = check_bound(h, B, "mpc_closed_loop"); if (rc) return rc;
-    rc = check_box_bound(h, B, "mpc_closed_loop"); if (rc) return rc;
-    rc = check_con_bound(h, B, "mpc_closed_loop"); if (rc) return rc;
+    rc = check_tables(h, B, "mpc_closed_loop", READS_ALL); if (rc) return rc;
     // bound table: the controller solves with row pidx[b], the plant advances with row pidx_plant[b] (null: the same)
     hipStream_t s = (hipStream_t)stream;
     double *st = stats;
@@ -541,7 +530,7 @@ extern "C" int mpc_closed_loop(mpc_handle *h, int B, int T, int shift, double *x
     }
     for (int t = 0; t < T; t++) {
         rc = mpc_solve_batch(h, B, x, cl, cl_index, U, lambda, st, stream); if (rc) return rc;
-        with_model_table(h, h->pidx_plant ? h->pidx_plant : h->pidx, [&](auto MODEL, auto PA, auto... pt) {
+        with_model_table(h, h->plant_rows(), [&](auto MODEL, auto PA, auto... pt) {
             hipLaunchKernelGGL((plant_step_kernel<MODEL(), PA(), decltype(pt)...>), grid_for(B, 64), dim3(64), 0,
                                s, c, B, t, T, shift, x, U, traj_x, traj_u, st, fail_count, pt...);
         });
@@ -568,11 +557,13 @@ static int solve_active_impl(mpc_handle *h, int B, const int32_t *active, const 
     ActiveRows r;
     r.list = e.list; r.count = e.count; r.nx = c.nx; r.n = c.n; r.m = c.m;
     r.x0 = const_cast<double *>(x0); r.U = U; r.lam = lambda; r.stats = stats;
-    r.cl_index = cl_index; r.pidx = h->ptab ? h->pidx : nullptr;
+    r.cl_index = cl_index; r.pidx = h->params().idx;
     r.xs = e.xs; r.Us = e.Us; r.lams = e.lams; r.stats_s = e.stats_s; r.cis = e.cis; r.pis = e.pis;
     hipLaunchKernelGGL(active_gather_kernel, grows, dim3(EV_BLK), 0, s, r);
-    if (h->btab) hipLaunchKernelGGL(active_index_kernel, gblk, dim3(EV_BLK), 0, s, e.list, e.count, h->bidx, e.bis);
-    if (h->ctab) hipLaunchKernelGGL(active_index_kernel, gblk, dim3(EV_BLK), 0, s, e.list, e.count, h->cidx, e.kis);
+    const AgentIdx gathered = {{e.pis, e.bis, e.kis}};   // (the parameter rows ride in the gather above)
+    for (int k = TAB_BOX; k < TAB_KINDS; k++)
+        if (h->tab[k].table)
+            hipLaunchKernelGGL(active_index_kernel, gblk, dim3(EV_BLK), 0, s, e.list, e.count, h->tab[k].idx, const_cast<int32_t *>(gathered.of[k]));
     int *cnt = (int *)((char *)h->host_counts + 384);   // pinned (see host_counts)
     HIPCHK(hipMemcpyAsync(cnt, e.count, sizeof(int), hipMemcpyDeviceToHost, s));
     rc = bounded_sync(h, s, "mpc_solve_active"); if (rc) return rc;
@@ -580,8 +571,7 @@ static int solve_active_impl(mpc_handle *h, int B, const int32_t *active, const 
     if (nA < 0 || nA > B) return fail(MPC_E_HIP, "mpc_solve_active: the compaction counted " + std::to_string(nA) + " of " + std::to_string(B) + " agents");
     if (n_active) *n_active = nA;
     if (nA == 0) return MPC_OK;
-    rc = solve_core(h, nA, e.xs, cl, cl_index ? e.cis : nullptr, r.pidx ? e.pis : nullptr, h->btab ? e.bis : nullptr,
-                    h->ctab ? e.kis : nullptr, e.Us, c.m ? e.lams : nullptr,
+    rc = solve_core(h, nA, e.xs, cl, cl_index ? e.cis : nullptr, gathered, e.Us, c.m ? e.lams : nullptr,
                     stats ? e.stats_s : nullptr, s);
     if (rc) return rc;
     hipLaunchKernelGGL(active_scatter_kernel, grid_for(nA, EV_BLK / 64), dim3(EV_BLK), 0, s, r);
@@ -598,9 +588,7 @@ extern "C" int mpc_solve_active(mpc_handle *h, int B, const int32_t *active, con
     if (B == 0) return MPC_OK;
     if (!active || !x0 || !cl || !U) return fail(MPC_E_ARG, "mpc_solve_active: null buffer");
     if (h->dc.m && !lambda) return fail(MPC_E_ARG, "mpc_solve_active: lambda is required when m > 0");
-    rc = check_bound(h, B, "mpc_solve_active"); if (rc) return rc;   // the caller's B; the compact batch is the library's
-    rc = check_box_bound(h, B, "mpc_solve_active"); if (rc) return rc;
-    rc = check_con_bound(h, B, "mpc_solve_active"); if (rc) return rc;
+    rc = check_tables(h, B, "mpc_solve_active", READS_ALL); if (rc) return rc;   // the caller's B; the compact batch is the library's
     return solve_active_impl(h, B, active, x0, cl, cl_index, U, lambda, stats, n_active, (hipStream_t)stream, true);
 }
 
@@ -698,9 +686,7 @@ static int check_track_call(mpc_handle *h, const mpc_track *t, int B, const char
 {
     int rc = check_common(h, B, who); if (rc) return rc;
     rc = check_track(h, t, who); if (rc) return rc;
-    rc = check_bound(h, B, who); if (rc) return rc;
-    rc = check_box_bound(h, B, who); if (rc) return rc;
-    return check_con_bound(h, B, who);
+    return check_tables(h, B, who, READS_ALL);
 }
 
 extern "C" int mpc_track_locate(mpc_handle *h, const mpc_track *t, int B, const double *x, const double *track,
@@ -752,9 +738,7 @@ static int closed_loop_event_impl(const char *who_, mpc_handle *h, int B, int T,
     if (!x || !cl || !U || (trk && !cl_index_rw)) return fail(MPC_E_ARG, who + ": null buffer");
     const DevCfg &c = h->dc;
     if (c.m && !lambda) return fail(MPC_E_ARG, who + ": lambda is required when m > 0");
-    rc = check_bound(h, B, who_); if (rc) return rc;
-    rc = check_box_bound(h, B, who_); if (rc) return rc;
-    rc = check_con_bound(h, B, who_); if (rc) return rc;
+    rc = check_tables(h, B, who_, READS_ALL); if (rc) return rc;
     rc = reserve_event(h, B); if (rc) return rc;
     bool fresh = false;
     rc = reserve_xhat(h, B, &fresh); if (rc) return rc;
@@ -770,11 +754,11 @@ static int closed_loop_event_impl(const char *who_, mpc_handle *h, int B, int T,
                                near_for(h, cl), cl_index_rw, (int *)nullptr, traj_row, t, T);
         rc = solve_active_impl(h, B, e.fire, x, cl, cl_index, U, lambda, st, nullptr, s, false); if (rc) return rc;
         // bound table: the plant advances with row pidx_plant[b] (null: the controller's), the nominal state with pidx[b]
-        with_model_table(h, h->pidx_plant ? h->pidx_plant : h->pidx, [&](auto MODEL, auto PA, auto... pt) {
+        with_model_table(h, h->plant_rows(), [&](auto MODEL, auto PA, auto... pt) {
             if constexpr (PA())
                 hipLaunchKernelGGL((event_step_kernel<MODEL(), true, decltype(pt)..., const int32_t *>), grid_for(B, 64), dim3(64), 0, s,
                                    c, B, t, T, x, e.xhat, U, held, e.fire, disturbance, traj_x, traj_u, solved, solve_count,
-                                   st, fail_count, pt..., h->pidx);
+                                   st, fail_count, pt..., h->params().idx);
             else
                 hipLaunchKernelGGL((event_step_kernel<MODEL(), false>), grid_for(B, 64), dim3(64), 0, s,
                                    c, B, t, T, x, e.xhat, U, held, e.fire, disturbance, traj_x, traj_u, solved, solve_count,

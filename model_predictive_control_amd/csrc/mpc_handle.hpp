@@ -1,5 +1,6 @@
 // mpc_handle.hpp -- host side of libmpc_hip.so, part 1: the handle behind the C-ABI, its error reporting, configuration
-// check, environment switches, stream-concurrency probe, workspace and bounded waits.  Host code (plus the probe's
+// check, environment switches, stream-concurrency probe, workspace, bounded waits, and the per-agent tables bound to it
+// (one BoundTable per TableKind, one batch-size check for all of them: check_tables).  Host code (plus the probe's
 // idling kernel); included by mpc_api.hip alone.
 #pragma once
 #include "../../include/mpc_hip.h"
@@ -34,6 +35,23 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
         if (e_ != hipSuccess)                                                                 \
             return fail(MPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
     } while (0)
+
+// The per-agent tables a caller can bind beside the handle's shared values: parameters (mpc_set_agent_params), input
+// boxes (mpc_set_agent_bounds) and constraint data (mpc_set_agent_constraints).  The kinds are walked in this order
+// wherever they are checked; an entry point names the kinds it reads as a mask of READS_* (check_tables).
+enum TableKind { TAB_PARAMS, TAB_BOX, TAB_CONSTR, TAB_KINDS };
+enum : unsigned { READS_PARAMS = 1u << TAB_PARAMS, READS_BOX = 1u << TAB_BOX, READS_CONSTR = 1u << TAB_CONSTR, READS_ALL = (1u << TAB_KINDS) - 1 };
+static constexpr struct { const char *noun, *setter; int width; } k_tables[TAB_KINDS] = {   // messages, doubles per row
+    {"parameter", "mpc_set_agent_params", MPC_NPARAM},
+    {"bounds", "mpc_set_agent_bounds", MPC_NBOUND},
+    {"constraint", "mpc_set_agent_constraints", MPC_NCONSTR}};
+struct BoundTable {
+    const double *table = nullptr;         // [rows][k_tables[kind].width], null: none bound
+    const int32_t *idx = nullptr;          // [B] the row per agent
+    int rows = 0, B = 0;
+};
+// the row indices of the agents of one solve, per kind: the handle's bound ones, or a masked solve's gathered ones
+struct AgentIdx { const int32_t *of[TAB_KINDS]; };
 
 // The workspace as the host keeps it: the kernels' Workspace, the parameter table the per-agent kernels get with it
 // (WorkspacePA), and the bounds table of mpc_set_agent_bounds (both null: none bound), which reaches the per-agent-box
@@ -129,22 +147,13 @@ struct mpc_handle {
     bool spin = false;             // the round loop busy-waits instead of napping (MPC_SPIN)
     bool host_timing = false;      // the round loop prints its host-side times to stderr (MPC_HOST_TIMING)
     std::string host_trace;        // file the round loop appends one line per polled window to (MPC_HOST_TRACE; empty: none)
-    // mpc_set_agent_params: the caller's parameter table and row indices (device memory, read at every call; all null:
-    // none bound, every agent runs the handle's values through the kernels that have always run)
-    const double *ptab = nullptr;          // [ptab_rows][MPC_NPARAM]
-    const int32_t *pidx = nullptr;         // [ptab_B] the controller's row per agent
-    const int32_t *pidx_plant = nullptr;   // [ptab_B] the plant's row per agent (mpc_closed_loop), null: pidx
-    int ptab_rows = 0, ptab_B = 0;
-    // mpc_set_agent_bounds: the caller's table of input boxes and row indices (device memory, read at every call; both
-    // null: none bound, every agent projects onto the handle's box through the kernels that have always run)
-    const double *btab = nullptr;          // [btab_rows][MPC_NBOUND]
-    const int32_t *bidx = nullptr;         // [btab_B]
-    int btab_rows = 0, btab_B = 0;
-    // mpc_set_agent_constraints: the caller's table of constraint data and row indices (device memory, read at every
-    // call; both null: none bound, every agent is held to the handle's constraint data by the kernels that have always run)
-    const double *ctab = nullptr;          // [ctab_rows][MPC_NCONSTR]
-    const int32_t *cidx = nullptr;         // [ctab_B]
-    int ctab_rows = 0, ctab_B = 0;
+    // The caller's per-agent tables, one per kind (mpc_set_agent_params / _bounds / _constraints; device memory, read at
+    // every call).  A kind with none bound runs the handle's values through the kernels that have always run.
+    BoundTable tab[TAB_KINDS];
+    const int32_t *pidx_plant = nullptr;   // parameters alone: [B] the plant's row per agent (mpc_closed_loop), null: the controller's
+    const BoundTable &params() const { return tab[TAB_PARAMS]; }
+    const int32_t *plant_rows() const { return pidx_plant ? pidx_plant : params().idx; }
+    AgentIdx bound_rows() const { return AgentIdx{{tab[TAB_PARAMS].idx, tab[TAB_BOX].idx, tab[TAB_CONSTR].idx}}; }
     // The persistent kernel has its box form together with the parameter form alone, and its constraint form -- as the
     // K1 kernels have theirs -- together with both.  With a table bound but not the ones its kernels come with, they run
     // on these one-row tables of the handle's own values (bit for bit the shared path: tests/test_gpu_agent_params.py,
@@ -419,40 +428,27 @@ static int reserve_xhat(mpc_handle *h, int B, bool *fresh)
     return MPC_OK;
 }
 
-// a handle with a parameter table serves the batch size the table's indices were bound for, and no other
-static int check_bound(const mpc_handle *h, int B, const char *who)
+// A handle with a table bound serves the batch size the table's indices were bound for, and no other, in the calls
+// that read that kind of table (`kinds`: a mask of READS_*).  Parameters, box, constraints: the first mismatch wins.
+static int check_tables(const mpc_handle *h, int B, const char *who, unsigned kinds)
 {
-    if (h->ptab && B != h->ptab_B)
-        return fail(MPC_E_ARG, std::string(who) + ": the bound parameter table is for a batch of " + std::to_string(h->ptab_B) +
-                               " agents, this call has " + std::to_string(B) + " (mpc_set_agent_params)");
-    return MPC_OK;
-}
-
-// ... and so does one with a bounds table, in the calls that read the box (`who`)
-static int check_box_bound(const mpc_handle *h, int B, const char *who)
-{
-    if (h->btab && B != h->btab_B)
-        return fail(MPC_E_ARG, std::string(who) + ": the bound bounds table is for a batch of " + std::to_string(h->btab_B) +
-                               " agents, this call has " + std::to_string(B) + " (mpc_set_agent_bounds)");
-    return MPC_OK;
-}
-// ... and one with a constraint table, in the calls that read constraint data (`who`)
-static int check_con_bound(const mpc_handle *h, int B, const char *who)
-{
-    if (h->ctab && B != h->ctab_B)
-        return fail(MPC_E_ARG, std::string(who) + ": the bound constraint table is for a batch of " + std::to_string(h->ctab_B) +
-                               " agents, this call has " + std::to_string(B) + " (mpc_set_agent_constraints)");
+    for (int k = 0; k < TAB_KINDS; k++) {
+        const BoundTable &t = h->tab[k];
+        if ((kinds >> k & 1u) && t.table && B != t.B)
+            return fail(MPC_E_ARG, std::string(who) + ": the bound " + k_tables[k].noun + " table is for a batch of " + std::to_string(t.B) +
+                                   " agents, this call has " + std::to_string(B) + " (" + k_tables[k].setter + ")");
+    }
     return MPC_OK;
 }
 // a table can be bound for B agents beside the ones that are: bound together they are for the same batch
-// (self: the table being bound -- 0 parameters, 1 bounds, 2 constraints -- whose earlier binding does not count)
+// (self: the kind being bound, whose earlier binding does not count)
 static int check_tables_agree(const mpc_handle *h, int B, const char *who, int self)
 {
-    const int others[3] = {h->ptab ? h->ptab_B : B, h->btab ? h->btab_B : B, h->ctab ? h->ctab_B : B};
-    const char *names[3] = {"parameter", "bounds", "constraint"};
-    for (int i = 0; i < 3; i++)
-        if (i != self && others[i] != B)
-            return fail(MPC_E_ARG, std::string(who) + ": the bound " + names[i] + " table is for a batch of " + std::to_string(others[i]) + " agents");
+    for (int k = 0; k < TAB_KINDS; k++) {
+        const BoundTable &t = h->tab[k];
+        if (k != self && t.table && t.B != B)
+            return fail(MPC_E_ARG, std::string(who) + ": the bound " + k_tables[k].noun + " table is for a batch of " + std::to_string(t.B) + " agents");
+    }
     return MPC_OK;
 }
 static inline dim3 grid_for(int B, int block) { return dim3((unsigned)((B + block - 1) / block)); }

@@ -4,7 +4,8 @@
 // added once.  What is instantiated is what the `if constexpr`s below let through -- never the cross product: the
 // Pacejka model has no fused K1b + K1c, lookahead exists for <PAC, NE = 1> alone, adjoint_kernel has no per-agent form,
 // the constraint forms exist beside the parameter form alone (K1b, the wave evaluation), beside the parameter and box
-// forms alone (the persistent kernel) and for constrained problems alone (the step kernel).
+// forms alone (the persistent kernel) and for constrained problems alone (the step kernel).  Where a form needs a table
+// the caller has not bound, with_own_params / with_own_box put the handle's own one-row table in its place.
 #pragma once
 #include "mpc_handle.hpp"
 
@@ -22,20 +23,23 @@ template <class F> static auto with_model(int model, F &&f) { if (model == PAC) 
 template <class F> static void with_model_table(const mpc_handle *h, const int32_t *index, F &&f)
 {
     with_model(h->dc.model, [&](auto MODEL) {
-        if (h->ptab) f(MODEL, std::true_type{}, h->ptab, index);
+        if (h->params().table) f(MODEL, std::true_type{}, h->params().table, index);
         else f(MODEL, std::false_type{});
     });
 }
 
-// The workspace as the constraint forms of the K1 kernels and of the persistent kernel take it: they exist together with
-// the parameter form alone, so without a parameter table of the caller's they run on the handle's own one-row table
-// (mpc_handle::own_ptab; its index of zeros needs no slicing per group)
+// The workspace as the constraint forms of the K1 kernels and the box and constraint forms of the persistent kernel take
+// it: they exist together with the parameter form alone, so without a parameter table of the caller's they run on the
+// handle's own one-row table (mpc_handle::own_ptab; its index of zeros needs no slicing per group)
 static WorkspacePA with_own_params(const mpc_handle *h, const WorkspaceHost &w)
 {
     WorkspacePA wp = w;
     if (!wp.ptab) { wp.ptab = h->own_ptab; wp.pidx = h->own_pidx; }
     return wp;
 }
+// ... and the box as the constraint form of the persistent kernel takes it: it exists together with the box form alone,
+// so without a bounds table of the caller's it runs on the handle's own one-row box table (mpc_handle::own_btab)
+static BoxTab with_own_box(const mpc_handle *h, const WorkspaceHost &w) { return w.btab ? w.box() : BoxTab{h->own_btab, h->own_pidx}; }
 
 // How the step kernel and the persistent kernel read an agent's L-BFGS history -- f(int_c<NE>, int_c<MC>), the two
 // kernels' template arguments (results do not depend on the choice).  NE: elements per lane, 1 up to n = 64 and 2
@@ -145,7 +149,7 @@ static void launch_solo_eval(mpc_handle *h, const WorkspaceHost &w, hipStream_t 
         });
         return;
     }
-    with_model_table(h, h->pidx, [&](auto MODEL, auto PA, auto...) {
+    with_model_table(h, h->params().idx, [&](auto MODEL, auto PA, auto...) {
         const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
         hipLaunchKernelGGL((solo_eval_kernel<MODEL(), PA()>), dim3((unsigned)w.B), dim3(64), lds, s, c, w, want_grad);
     });
@@ -258,22 +262,19 @@ static void launch_solo_t(mpc_handle *h, const WorkspaceHost &v, hipStream_t s, 
     nblk = std::max(1, std::min(nblk, 4 * SoloOcc<MODEL>::WPS * h->num_cus)); // what is resident (registers); the rest queues
     // (v.ptab: a parameter table is bound, the per-agent variant.  The lookahead kernel exists where solo_lookahead can
     // say yes: Pacejka model, one element per lane)
-    // v.btab: a bounds table is bound, the box form, which exists together with the parameter form alone -- without a
-    // parameter table of the caller's it runs on the handle's own one-row table (mpc_set_agent_bounds made it)
-    // v.ctab: a constraint table is bound, the constraint form, which exists together with the box form alone -- without
-    // a bounds table of the caller's it runs on the handle's own one-row box table (never with the lookahead: m > 0)
+    // v.btab: a bounds table is bound, the box form, which exists together with the parameter form alone (with_own_params)
+    // v.ctab: a constraint table is bound, the constraint form, which exists together with the box form alone
+    // (with_own_box; never with the lookahead: m > 0)
     if (v.ctab) {
-        const BoxTab bt = v.btab ? v.box() : BoxTab{h->own_btab, h->own_pidx};
         hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, ConTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
-                           with_own_params(h, v), list, ctr, max_trips, bt, v.con());
+                           with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), v.con());
         return;
     }
     if (v.btab) {
-        WorkspacePA vp = v;
-        if (!vp.ptab) { vp.ptab = h->own_ptab; vp.pidx = h->own_pidx; }
         with_flag(la, [&](auto LA) {
             if constexpr (!LA() || (MODEL == PAC && NE == 1))
-                hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, LA(), true, BoxTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c, vp, list, ctr, max_trips, v.box());
+                hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, LA(), true, BoxTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
+                                   with_own_params(h, v), list, ctr, max_trips, v.box());
         });
         return;
     }

@@ -48,6 +48,13 @@ class Track:
                 f"closed={self.closed}, R={self.R})")
 
 
+# the per-agent tables of an engine, by kind: doubles per row, the library's setter, whether the setter takes a plant index
+_AgentTable = collections.namedtuple("_AgentTable", "width setter plant")
+_AGENT_TABLES = {"params": _AgentTable(_lib.NPARAM, "mpc_set_agent_params", True),
+                 "bounds": _AgentTable(_lib.NBOUND, "mpc_set_agent_bounds", False),
+                 "constraints": _AgentTable(_lib.NCONSTR, "mpc_set_agent_constraints", False)}
+
+
 class BatchedMPC:
     """One handle = one GPU.  All tensors are float64, contiguous, on `device`."""
 
@@ -73,9 +80,7 @@ class BatchedMPC:
         self._h = h
         self._pending = False       # an asynchronous solve is in flight: the worker thread owns the handle
         self._cl_key, self._cl_keep = None, None   # the centerline table the search tables were last built for
-        self._params_keep = None    # (table, index, plant_index) of set_agent_params, alive while bound
-        self._bounds_keep = None    # (table, index) of set_agent_bounds, alive while bound
-        self._constraints_keep = None   # (table, index) of set_agent_constraints, alive while bound
+        self._keep = {}             # kind -> (table, index[, plant_index]) of set_agent_<kind>, alive while bound
         import os
         # nearest-point search of K1b as the library chose it at mpc_create: 2 grid of index ranges (default), 0 the
         # full scan (MPC_NEAREST_SCAN) -- which needs no tables
@@ -153,7 +158,34 @@ class BatchedMPC:
                     self._cl_key, self._cl_keep = key, cl
         return cl
 
-    # ------------------------------------------------------------------ per-agent parameters
+    # ------------------------------------------------------------------ per-agent tables
+    def _bind_agent_table(self, kind, table, *indices):
+        """set_agent_<kind>: the shape, dtype, device and range checks, the library's setter, and the tensors kept alive.
+        indices: `index`, and `plant_index` (or None) for the kind that has one."""
+        d = _AGENT_TABLES[kind]
+        self._free()
+        if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] != d.width or table.shape[0] < 1:
+            raise ValueError(f"table: expected a tensor [P >= 1, {d.width}]")
+        self._chk(table, table.shape, "table")
+        index = indices[0]
+        if not isinstance(index, torch.Tensor) or index.dim() != 1 or index.shape[0] < 1:
+            raise ValueError("index: expected a tensor [B >= 1]")
+        B, P = int(index.shape[0]), int(table.shape[0])
+        for t, name in zip(indices, ("index", "plant_index")):
+            if t is None:
+                continue
+            self._chk(t, (B,), name, torch.int32)
+            if int(t.min()) < 0 or int(t.max()) >= P:
+                raise ValueError(f"{name} out of range")
+        _lib.check(getattr(self.lib, d.setter)(self._h, _ptr(table), P, *map(_ptr, indices), B))
+        self._keep[kind] = (table, *indices)
+
+    def _clear_agent_table(self, kind):
+        d = _AGENT_TABLES[kind]
+        self._free()
+        _lib.check(getattr(self.lib, d.setter)(self._h, None, 0, *([None] * (2 if d.plant else 1)), 0))
+        self._keep.pop(kind, None)
+
     def set_agent_params(self, table, index, plant_index=None):
         """Binds a per-agent parameter table (mpc_set_agent_params): table [P, 31] float64 (rows as
         _lib.param_rows makes them), index [B] int32 = the row of agent b, plant_index [B] int32 = the row the PLANT
@@ -161,33 +193,16 @@ class BatchedMPC:
         eval_cost_grad, solve, solve_async, closed_loop) uses agent b's row and serves batches of exactly B agents.
         The tensors stay the caller's: the library reads them at every call, so rows may be rewritten in place
         between calls; the engine keeps them alive until clear_agent_params()."""
-        self._free()
-        if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] != _lib.NPARAM or table.shape[0] < 1:
-            raise ValueError(f"table: expected a tensor [P >= 1, {_lib.NPARAM}]")
-        self._chk(table, table.shape, "table")
-        if not isinstance(index, torch.Tensor) or index.dim() != 1 or index.shape[0] < 1:
-            raise ValueError("index: expected a tensor [B >= 1]")
-        B, P = int(index.shape[0]), int(table.shape[0])
-        for t, name in ((index, "index"), (plant_index, "plant_index")):
-            if t is None:
-                continue
-            self._chk(t, (B,), name, torch.int32)
-            if int(t.min()) < 0 or int(t.max()) >= P:
-                raise ValueError(f"{name} out of range")
-        _lib.check(self.lib.mpc_set_agent_params(self._h, _ptr(table), P, _ptr(index), _ptr(plant_index), B))
-        self._params_keep = (table, index, plant_index)
+        self._bind_agent_table("params", table, index, plant_index)
 
     def clear_agent_params(self):
         """Unbinds the parameter table: the engine is what it was before set_agent_params."""
-        self._free()
-        _lib.check(self.lib.mpc_set_agent_params(self._h, None, 0, None, None, 0))
-        self._params_keep = None
+        self._clear_agent_table("params")
 
     @property
     def agent_params_bound(self):
-        return self._params_keep is not None
+        return "params" in self._keep
 
-    # ------------------------------------------------------------------ per-agent input bounds
     def set_agent_bounds(self, table, index):
         """Binds a per-agent table of input boxes (mpc_set_agent_bounds): table [P, 4] float64 (rows
         [u_lb[0], u_lb[1], u_ub[0], u_ub[1]], as _lib.bound_rows makes them), index [B] int32 = the row of agent b.
@@ -196,30 +211,16 @@ class BatchedMPC:
         table (either, both or neither; together they are for the same B).  The tensors stay the caller's: the
         library reads them at every call, so rows may be rewritten in place between calls; the engine keeps them
         alive until clear_agent_bounds()."""
-        self._free()
-        if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] != _lib.NBOUND or table.shape[0] < 1:
-            raise ValueError(f"table: expected a tensor [P >= 1, {_lib.NBOUND}]")
-        self._chk(table, table.shape, "table")
-        if not isinstance(index, torch.Tensor) or index.dim() != 1 or index.shape[0] < 1:
-            raise ValueError("index: expected a tensor [B >= 1]")
-        B, P = int(index.shape[0]), int(table.shape[0])
-        self._chk(index, (B,), "index", torch.int32)
-        if int(index.min()) < 0 or int(index.max()) >= P:
-            raise ValueError("index out of range")
-        _lib.check(self.lib.mpc_set_agent_bounds(self._h, _ptr(table), P, _ptr(index), B))
-        self._bounds_keep = (table, index)
+        self._bind_agent_table("bounds", table, index)
 
     def clear_agent_bounds(self):
         """Unbinds the bounds table: the engine is what it was before set_agent_bounds."""
-        self._free()
-        _lib.check(self.lib.mpc_set_agent_bounds(self._h, None, 0, None, 0))
-        self._bounds_keep = None
+        self._clear_agent_table("bounds")
 
     @property
     def agent_bounds_bound(self):
-        return self._bounds_keep is not None
+        return "bounds" in self._keep
 
-    # ------------------------------------------------------------------ per-agent constraint data
     def set_agent_constraints(self, table, index):
         """Binds a per-agent table of constraint data (mpc_set_agent_constraints): table [P, 19] float64 (rows
         [g_off[6], D_lb[6], D_ub[6], lane_halfwidth], as _lib.constraint_rows makes them; only the fields of the engine's
@@ -228,28 +229,15 @@ class BatchedMPC:
         batches of exactly B agents.  Independent of the parameter and bounds tables (any subset; together they are for
         the same B).  The tensors stay the caller's: the library reads them at every call, so rows may be rewritten in
         place between calls; the engine keeps them alive until clear_agent_constraints()."""
-        self._free()
-        if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] != _lib.NCONSTR or table.shape[0] < 1:
-            raise ValueError(f"table: expected a tensor [P >= 1, {_lib.NCONSTR}]")
-        self._chk(table, table.shape, "table")
-        if not isinstance(index, torch.Tensor) or index.dim() != 1 or index.shape[0] < 1:
-            raise ValueError("index: expected a tensor [B >= 1]")
-        B, P = int(index.shape[0]), int(table.shape[0])
-        self._chk(index, (B,), "index", torch.int32)
-        if int(index.min()) < 0 or int(index.max()) >= P:
-            raise ValueError("index out of range")
-        _lib.check(self.lib.mpc_set_agent_constraints(self._h, _ptr(table), P, _ptr(index), B))
-        self._constraints_keep = (table, index)
+        self._bind_agent_table("constraints", table, index)
 
     def clear_agent_constraints(self):
         """Unbinds the constraint table: the engine is what it was before set_agent_constraints."""
-        self._free()
-        _lib.check(self.lib.mpc_set_agent_constraints(self._h, None, 0, None, 0))
-        self._constraints_keep = None
+        self._clear_agent_table("constraints")
 
     @property
     def agent_constraints_bound(self):
-        return self._constraints_keep is not None
+        return "constraints" in self._keep
 
     def invalidate_centerline_tables(self):
         """Forget the nearest-point search tables: the next call rebuilds them for the table it is given."""

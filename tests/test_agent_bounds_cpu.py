@@ -6,7 +6,6 @@ import ctypes as C
 import inspect
 import os
 import re
-import shutil
 import subprocess
 import sys
 
@@ -16,6 +15,7 @@ import pytest
 from conftest import ROOT
 
 import model_predictive_control_amd as mp
+from codeobj_common import _waves_by_vgprs, built_library_kernels
 from model_predictive_control_amd import _lib
 
 STEP_BOX = "_ZN3mpc15step_kernel_boxI"            # every per-agent-box step kernel
@@ -108,33 +108,10 @@ def test_front_ends_carry_the_new_entry_points():
     subprocess.check_call([sys.executable, "-c", code])
 
 
-# ------------------------------------------------------------------ the code object (read as test_step_kernel_occupancy.py reads it)
-def _tool(name):
-    p = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", name)
-    return p if os.access(p, os.X_OK) else shutil.which(name)
-
-
+# ------------------------------------------------------------------ the code object (tests/codeobj_common.py)
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    yaml = pytest.importorskip("yaml")
-    tools = {n: _tool(n) for n in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")}
-    missing = [n for n, p in tools.items() if p is None]
-    if missing:
-        pytest.skip("needs " + ", ".join(missing))
-    _lib.build()
-    d = tmp_path_factory.mktemp("codeobj")
-    fatbin, co = str(d / "fatbin.bin"), str(d / "gfx950.o")
-    subprocess.check_call([tools["llvm-objcopy"], "--dump-section=.hip_fatbin=" + fatbin, _lib.LIB_PATH, str(d / "x")])
-    subprocess.check_call([tools["clang-offload-bundler"], "--unbundle", "--type=o", "--input=" + fatbin,
-                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-    notes = subprocess.check_output([tools["llvm-readelf"], "--notes", co], text=True)
-    doc = notes[notes.index("---"):notes.index("\n...", notes.index("---"))]
-    meta = yaml.safe_load(doc)
-    return {k[".name"]: k for k in meta["amdhsa.kernels"]}
-
-
-def _waves_by_vgprs(vgprs):
-    return 512 // (-(-vgprs // 8) * 8)
+    return built_library_kernels(tmp_path_factory)
 
 
 def test_lean_box_step_kernel_fits_the_shared_kernels_target(L, kernels):

@@ -6,7 +6,6 @@ import ctypes as C
 import inspect
 import os
 import re
-import shutil
 import subprocess
 import sys
 
@@ -16,6 +15,7 @@ import pytest
 from conftest import ROOT
 
 import model_predictive_control_amd as mp
+from codeobj_common import _waves_by_vgprs, built_library_kernels
 from model_predictive_control_amd import _lib
 
 STEP = "_ZN3mpc11step_kernelI"
@@ -122,34 +122,14 @@ def test_front_ends_carry_the_new_entry_points():
     subprocess.check_call([sys.executable, "-c", code])
 
 
-# ------------------------------------------------------------------ the code object (read as test_agent_bounds_cpu.py reads it)
-def _tool(name):
-    p = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", name)
-    return p if os.access(p, os.X_OK) else shutil.which(name)
-
-
+# ------------------------------------------------------------------ the code object (tests/codeobj_common.py)
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    """The gfx950 code object's kernel metadata.  PyYAML and the LLVM tools of the ROCm installation are needed: their
-    absence fails these tests (a skip would drop the register and occupancy checks without notice)."""
-    import yaml
-    tools = {n: _tool(n) for n in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")}
-    missing = [n for n, p in tools.items() if p is None]
-    assert not missing, "needs " + ", ".join(missing)
-    _lib.build()
-    d = tmp_path_factory.mktemp("codeobj")
-    fatbin, co = str(d / "fatbin.bin"), str(d / "gfx950.o")
-    subprocess.check_call([tools["llvm-objcopy"], "--dump-section=.hip_fatbin=" + fatbin, _lib.LIB_PATH, str(d / "x")])
-    subprocess.check_call([tools["clang-offload-bundler"], "--unbundle", "--type=o", "--input=" + fatbin,
-                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-    notes = subprocess.check_output([tools["llvm-readelf"], "--notes", co], text=True)
-    doc = notes[notes.index("---"):notes.index("\n...", notes.index("---"))]
-    meta = yaml.safe_load(doc)
-    return {k[".name"]: k for k in meta["amdhsa.kernels"]}
+    return built_library_kernels(tmp_path_factory, skip=False)    # (these register and occupancy checks never skip)
 
 
-def _waves_by_vgprs(k):
-    return min(8, 512 // (-(-(k[".vgpr_count"] + k.get(".agpr_count", 0)) // 8) * 8))
+def _waves(k):
+    return min(8, _waves_by_vgprs(k[".vgpr_count"] + k.get(".agpr_count", 0)))
 
 
 def test_every_constrained_step_kernel_has_its_constraint_forms(kernels):
@@ -168,7 +148,7 @@ def test_every_constrained_step_kernel_has_its_constraint_forms(kernels):
             assert k[".private_segment_fixed_size"] == 0 and k[".vgpr_spill_count"] == 0
             assert k[".sgpr_spill_count"] <= p[".sgpr_spill_count"], (cn, k[".sgpr_spill_count"], p[".sgpr_spill_count"])
             assert k[".vgpr_count"] <= p[".vgpr_count"], (cn, k[".vgpr_count"], p[".vgpr_count"])
-            assert _waves_by_vgprs(k) == _waves_by_vgprs(p), (cn, k[".vgpr_count"], p[".vgpr_count"])
+            assert _waves(k) == _waves(p), (cn, k[".vgpr_count"], p[".vgpr_count"])
             assert k[".group_segment_fixed_size"] == p[".group_segment_fixed_size"]
             assert k[".max_flat_workgroup_size"] == 256
             # the argument layout KernArgs reads: DevCfg, Workspace, the tables (two pointers each), then the list

@@ -3,7 +3,7 @@ constraint data [g_off[6], D_lb[6], D_ub[6], lane_halfwidth] in device memory an
 parameter and bounds tables.  Every agent of a batch with different speed limits, minimum speeds or lane widths is
 checked against the oracle run with that agent's own values; a table whose rows equal the handle's values must give the
 bits of the call without a table; the host's switch points must change no bit under a table either.  The helpers are
-copies of tests/test_gpu_agent_bounds.py's and tests/test_gpu_agent_params.py's; the tolerances are the ones those
+those of tests/agent_tables_common.py; the tolerances are the ones those
 files and tests/test_gpu_parity.py assert for the same quantities.
 
 The rows and inputs (recipes A, B, C, C') are fixed draws: their order is part of the test.  They were checked with the
@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+from agent_tables_common import T, box_rows_of, by_row, kwl, oracle_solve, param_rows_of, rel, table_of
 from conftest import straight_centerline, synthetic_states
 
 pytestmark = pytest.mark.gpu
@@ -23,6 +24,7 @@ pytestmark = pytest.mark.gpu
 import model_predictive_control_amd as mp  # noqa: E402
 from model_predictive_control_amd import _lib  # noqa: E402
 
+ctable = functools.partial(table_of, make=_lib.constraint_rows, fields=_lib.CONSTR_FIELDS)   # [P, 19] host table of the rows
 BASE_OFF = np.array([20, 1, 1, 0.5, 1, 0.1])
 SQ_COMMON = dict(constr_mode=1, D_lb=[-np.inf] * 6, D_ub=[0.0] * 6, g_off=[20, 1, 1, 0.5, 1, 0.1], Sigma0=10.0, alm_eps=1e-8,
                  max_total_inner=6000)
@@ -34,52 +36,6 @@ LANE_COMMON = dict(constr_mode=2, lane_halfwidth=0.05, Sigma0=10.0, alm_eps=1e-8
 def dev():
     assert torch.cuda.is_available(), "GPU tests need a HIP device"
     return torch.device("cuda:0")
-
-
-def T(a, dev, dtype=torch.float64):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device=dev)
-
-
-def rel(a, b):
-    return np.abs(a - b).max() / max(1e-300, np.abs(b).max())
-
-
-def kwl(kw):
-    """ctypes-friendly copy of a row's overrides."""
-    return {k: (list(v) if hasattr(v, "__len__") else float(v)) for k, v in kw.items()}
-
-
-def by_row(idx, P, fn):
-    """fn(p, sel) -> tuple of arrays for the agents sel (those with row p); the tuples scattered back into batch order."""
-    B = len(idx)
-    outs = None
-    for p in range(P):
-        sel = np.nonzero(idx == p)[0]
-        if sel.size == 0:
-            continue
-        res = fn(p, sel)
-        if outs is None:
-            outs = [None if r is None else np.empty((B,) + np.asarray(r).shape[1:]) for r in res]
-        for o, r in zip(outs, res):
-            if o is not None:
-                o[sel] = r
-    return outs
-
-
-def oracle_solve(O, model, N, overrides, X0, cl, U0, **common):
-    """overrides[b]: the configuration overrides of agent b (dicts; agents that share one are solved in one batch)."""
-    B = len(overrides)
-    keys = [repr(sorted((k, np.asarray(v).tolist()) for k, v in o.items())) for o in overrides]
-    U = np.empty((B, U0.shape[1])); st = np.empty((B, 8)); lam = None
-    for key in sorted(set(keys)):
-        sel = np.array([b for b in range(B) if keys[b] == key])
-        ocfg = O.default_config(model, N, **{**common, **kwl(overrides[sel[0]])})
-        Us, ls, ss = O.solve_batch(ocfg, X0[sel], cl, U0[sel])
-        U[sel], st[sel] = Us, ss
-        if ls.shape[1]:
-            lam = np.empty((B, ls.shape[1])) if lam is None else lam
-            lam[sel] = ls
-    return U, st, lam
 
 
 # ----------------------------------------------------------------------------- the rows of the tests
@@ -115,16 +71,6 @@ def rows_B():
 
 def rows_lane(hws=(0.05, 0.03, 0.04, 0.07)):
     return [dict(lane_halfwidth=float(h)) for h in hws]
-
-
-def ctable(cfg, rws):
-    """[P, 19] host table of the rows (what a row does not name is the configuration's)."""
-    tab = _lib.constraint_rows(cfg, len(rws))
-    for p, kw in enumerate(rws):
-        for k, v in kw.items():
-            off, width = _lib.CONSTR_FIELDS[k]
-            tab[p, off:off + width] = v
-    return tab
 
 
 def states_A(B):
@@ -410,38 +356,6 @@ def test_groups_change_nothing_under_a_constraint_table(dev):
 
 
 # ----------------------------------------------------------------------------- 7
-def param_rows_of(O, model, P, seed):
-    """The parameter rows of tests/test_gpu_agent_params.py (same draws)."""
-    rng = np.random.default_rng(seed)
-    base = O.default_config(model, 12)
-    out = []
-    for p in range(P):
-        veh = np.array(list(base.veh))
-        if model == 0:
-            veh[1] *= rng.uniform(.8, 1.25); veh[2] *= rng.uniform(.8, 1.25)
-            kw = dict(veh=veh, accel=base.accel * rng.uniform(.75, 1.25), friction=base.friction * rng.uniform(.7, 1.3),
-                      v_ref=rng.uniform(.6, 1.4), cost_w=np.array(list(base.cost_w)) * rng.uniform(.7, 1.4, 6))
-        else:
-            veh[1] *= rng.uniform(.9, 1.1); veh[2] *= rng.uniform(.9, 1.1)
-            veh[7] *= rng.uniform(.85, 1.2); veh[8] *= rng.uniform(.85, 1.2)
-            veh[11:17] *= rng.uniform(.9, 1.1, 6)
-            veh[17] *= rng.uniform(.85, 1.15); veh[18:22] *= rng.uniform(.8, 1.2, 4)
-            kw = dict(veh=veh, v_ref=rng.uniform(.7, 1.3), cost_w=np.array(list(base.cost_w)) * rng.uniform(.7, 1.4, 6))
-        out.append({} if p == 0 else kw)
-    return out
-
-
-def box_rows_of(P, seed):
-    """The box rows of tests/test_gpu_agent_bounds.py (same draws)."""
-    rng = np.random.default_rng(seed)
-    out = [dict(u_lb=[-1.0, -0.32], u_ub=[1.0, 0.32])]
-    for _ in range(1, P):
-        lb_d = -rng.uniform(.2, 1.0); ub_d = rng.uniform(.35, 1.0)
-        s_lo = -rng.uniform(.08, .32); s_hi = rng.uniform(.08, .32)
-        out.append(dict(u_lb=[lb_d, s_lo], u_ub=[ub_d, s_hi]))
-    return out
-
-
 def test_three_tables_at_once(dev, O):
     model, N, common, crw, cidx, X0, cl, U0 = recipe("A")
     B = len(cidx)
@@ -451,11 +365,7 @@ def test_three_tables_at_once(dev, O):
     pidx, bidx = (np.arange(B) + 1) % 4, (np.arange(B) + 2) % 4
     assert (pidx != bidx).all() and (pidx != cidx).all() and (bidx != cidx).all()
     cfg = mp.default_config(model, N, **common)
-    ptab = _lib.param_rows(cfg, 4)
-    for p, kw in enumerate(prw):
-        for k, v in kw.items():
-            off, width = _lib.PARAM_FIELDS[k]
-            ptab[p, off:off + width] = v
+    ptab = table_of(cfg, prw)
     btab = np.array([list(r["u_lb"]) + list(r["u_ub"]) for r in brw])
     eng = mp.BatchedMPC(cfg, dev)
     kp = (T(ptab, dev), T(pidx, dev, torch.int32)); eng.set_agent_params(*kp)

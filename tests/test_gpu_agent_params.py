@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from agent_tables_common import (T, assert_reference_tolerance, assert_tight, by_row, kwl, oracle_solve,
+                                 param_rows_of as rows, problem, rel, table_of)
 from conftest import straight_centerline, synthetic_states
 
 pytestmark = pytest.mark.gpu
@@ -21,37 +23,7 @@ def dev():
     return torch.device("cuda:0")
 
 
-def T(a, dev, dtype=torch.float64):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device=dev)
-
-
-def rel(a, b):
-    return np.abs(a - b).max() / max(1e-300, np.abs(b).max())
-
-
 # ----------------------------------------------------------------------------- the rows of the tests
-def rows(O, model, P, seed):
-    """Row p as the override of the oracle's configuration AND the content of table row p (row 0: the defaults).
-    The order of the draws is part of the test: these rows were checked with the oracle alone."""
-    rng = np.random.default_rng(seed)
-    base = O.default_config(model, 12)
-    out = []
-    for p in range(P):
-        veh = np.array(list(base.veh))
-        if model == 0:
-            veh[1] *= rng.uniform(.8, 1.25); veh[2] *= rng.uniform(.8, 1.25)
-            kw = dict(veh=veh, accel=base.accel * rng.uniform(.75, 1.25), friction=base.friction * rng.uniform(.7, 1.3),
-                      v_ref=rng.uniform(.6, 1.4), cost_w=np.array(list(base.cost_w)) * rng.uniform(.7, 1.4, 6))
-        else:
-            veh[1] *= rng.uniform(.9, 1.1); veh[2] *= rng.uniform(.9, 1.1)
-            veh[7] *= rng.uniform(.85, 1.2); veh[8] *= rng.uniform(.85, 1.2)
-            veh[11:17] *= rng.uniform(.9, 1.1, 6)
-            veh[17] *= rng.uniform(.85, 1.15); veh[18:22] *= rng.uniform(.8, 1.2, 4)
-            kw = dict(veh=veh, v_ref=rng.uniform(.7, 1.3), cost_w=np.array(list(base.cost_w)) * rng.uniform(.7, 1.4, 6))
-        out.append({} if p == 0 else kw)
-    return out
-
-
 def narrow_rows(O):
     """The rows of the state-constrained test: row 0 default, rows 1 .. 3 from default_rng(1)."""
     rng = np.random.default_rng(1)
@@ -64,79 +36,10 @@ def narrow_rows(O):
     return out
 
 
-def table_of(cfg, rws):
-    """[P, 31] host table: the handle's row with the overrides of each row."""
-    tab = _lib.param_rows(cfg, len(rws))
-    for p, kw in enumerate(rws):
-        for k, v in kw.items():
-            off, width = _lib.PARAM_FIELDS[k]
-            tab[p, off:off + width] = v
-    return tab
-
-
-def kwl(kw):
-    """ctypes-friendly copy of a row's overrides."""
-    return {k: (list(v) if hasattr(v, "__len__") else float(v)) for k, v in kw.items()}
-
-
-def by_row(idx, P, fn):
-    """fn(p, sel) -> tuple of arrays for the agents sel (those with row p); the tuples scattered back into batch order."""
-    B = len(idx)
-    outs = None
-    for p in range(P):
-        sel = np.nonzero(idx == p)[0]
-        if sel.size == 0:
-            continue
-        res = fn(p, sel)
-        if outs is None:
-            outs = [None if r is None else np.empty((B,) + np.asarray(r).shape[1:]) for r in res]
-        for o, r in zip(outs, res):
-            if o is not None:
-                o[sel] = r
-    return outs
-
-
 def bind(eng, dev, tab, idx, plant=None):
     t, i = T(tab, dev), T(idx, dev, torch.int32)
     eng.set_agent_params(t, i, None if plant is None else T(plant, dev, torch.int32))
     return t, i
-
-
-def problem(model, N, B, seed=21):
-    return synthetic_states(model, B, seed=seed), straight_centerline(), np.tile([1., 0.], (B, N))
-
-
-def oracle_solve(O, model, N, rws, idx, X0, cl, U0, **common):
-    def one(p, sel):
-        ocfg = O.default_config(model, N, **common, **kwl(rws[p]))
-        U, lam, st = O.solve_batch(ocfg, X0[sel], cl, U0[sel])
-        return U, st, (lam if lam.shape[1] else None)
-    return by_row(idx, len(rws), one)
-
-
-def assert_tight(U, st, Uo, sto):
-    """The assertions of test_solve_matches_oracle_tight_tolerance (alm_eps = 1e-10)."""
-    conv = (st[:, 0] == 1) & (sto[:, 0] == 1)
-    assert conv.mean() >= 0.97
-    assert np.mean((st[:, 0] == 1) == (sto[:, 0] == 1)) >= 0.98
-    scale = np.maximum(1.0, np.abs(Uo).max(1))
-    d = np.abs(U - Uo).max(1) / scale                                     # bench.DU_METRIC
-    match = conv & (d <= 1e-5)
-    assert match.sum() >= 0.97 * conv.sum()
-    other = conv & ~match
-    assert np.all(np.abs(st[other, 6] - sto[other, 6]) > 1e-9)            # the others sit at distinct minima
-    assert np.median(np.abs(U - Uo).max(1)[match]) <= 1e-7
-    assert np.allclose(st[match, 6], sto[match, 6], rtol=1e-10, atol=1e-12)
-
-
-def assert_reference_tolerance(U, st, Uo, sto):
-    """The assertions of test_solve_reference_tolerance_statistics (alm_eps = 1e-6)."""
-    assert np.all(st[:, 0] == 1) and np.all(sto[:, 0] == 1)
-    assert np.allclose(st[:, 6], sto[:, 6], rtol=0, atol=1e-9)
-    assert np.abs(U - Uo).max() <= 2e-4
-    assert abs(st[:, 2].mean() - sto[:, 2].mean()) <= 0.05 * sto[:, 2].mean()
-    assert np.all(st[:, 1] == sto[:, 1])
-    assert np.all(st[:, 4] <= 1e-6)
 
 
 def model_layer_checks(O, eng, dev, model, N, ocfg_of, idx, P, seed=5):
@@ -293,7 +196,7 @@ def test_solve_matches_oracle_row_by_row(dev, O, model, N, B):
         eng = mp.BatchedMPC(cfg, dev)
         keep = bind(eng, dev, table_of(cfg, rws), idx)
         U, _, st = eng.solve(T(X0, dev), T(cl, dev), T(U0, dev))
-        Uo, sto, _ = oracle_solve(O, model, N, rws, idx, X0, cl, U0, **kw)
+        Uo, sto, _ = oracle_solve(O, model, N, [rws[p] for p in idx], X0, cl, U0, **kw)
         check(U.cpu().numpy(), st.cpu().numpy(), Uo, sto)
         del keep
         eng.close()
@@ -442,7 +345,7 @@ def test_state_constraints_row_by_row(dev, O):
     keep = bind(eng, dev, table_of(cfg, rws), idx)
     U, lam, st = eng.solve(T(X0, dev), T(cl, dev), T(U0, dev))
     U, lam, st = U.cpu().numpy(), lam.cpu().numpy(), st.cpu().numpy()
-    Uo, sto, lamo = oracle_solve(O, 1, N, rws, idx, X0, cl, U0, **common)
+    Uo, sto, lamo = oracle_solve(O, 1, N, [rws[p] for p in idx], X0, cl, U0, **common)
     assert (sto[:, 0] == 1).all() and (st[:, 0] == 1).mean() >= 0.97
     conv = (st[:, 0] == 1) & (sto[:, 0] == 1)
     d = np.abs(U - Uo).max(1)

@@ -2,16 +2,14 @@
 (step_kernel<1, -1, false>) is compiled for five waves per SIMD -- at most 96 VGPRs (512 / 5, in granules of 8), no
 spills, no scratch, 264 B of static LDS -- and the host sizes the LDS copy of the L-BFGS history (P pairs) so that the
 same number of its workgroups share a CU's 160 KiB of LDS (mpc_step_lds_plan exposes that computation).  The code
-object's metadata is read as tests/test_step_kernel_registers.py reads it; skips when the LLVM tools are absent."""
+object's metadata is read by tests/codeobj_common.py; skips when the LLVM tools are absent."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import pytest
 
 from conftest import ROOT  # noqa: F401  (puts the repository on sys.path)
 
+from codeobj_common import _waves_by_vgprs, built_library_kernels
 from model_predictive_control_amd import _lib
 
 STEP_LEAN = "_ZN3mpc11step_kernelILi1ELin1ELb0EEEvNS_6DevCfgENS_9WorkspaceEPiS3_S3_iiii"
@@ -19,11 +17,6 @@ STEP_LDS_BYTES = 264          # s_req[64] + s_next (+ padding): the history copy
 LEAN_WAVES_PER_SIMD = 5
 CU_LDS = 160 * 1024
 LDS_GRANULE = 512
-
-
-def _tool(name):
-    p = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", name)
-    return p if os.access(p, os.X_OK) else shutil.which(name)
 
 
 @pytest.fixture(scope="module")
@@ -34,25 +27,7 @@ def L():
 
 @pytest.fixture(scope="module")
 def kernels(tmp_path_factory):
-    yaml = pytest.importorskip("yaml")
-    tools = {n: _tool(n) for n in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")}
-    missing = [n for n, p in tools.items() if p is None]
-    if missing:
-        pytest.skip("needs " + ", ".join(missing))
-    _lib.build()
-    d = tmp_path_factory.mktemp("codeobj")
-    fatbin, co = str(d / "fatbin.bin"), str(d / "gfx950.o")
-    subprocess.check_call([tools["llvm-objcopy"], "--dump-section=.hip_fatbin=" + fatbin, _lib.LIB_PATH, str(d / "x")])
-    subprocess.check_call([tools["clang-offload-bundler"], "--unbundle", "--type=o", "--input=" + fatbin,
-                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-    notes = subprocess.check_output([tools["llvm-readelf"], "--notes", co], text=True)
-    doc = notes[notes.index("---"):notes.index("\n...", notes.index("---"))]
-    meta = yaml.safe_load(doc)
-    return {k[".name"]: k for k in meta["amdhsa.kernels"]}
-
-
-def _waves_by_vgprs(vgprs):
-    return 512 // (-(-vgprs // 8) * 8)
+    return built_library_kernels(tmp_path_factory)
 
 
 def test_lean_step_kernel_fits_its_target(kernels):

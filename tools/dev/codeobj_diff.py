@@ -10,37 +10,24 @@ per-agent flag at its default) is matched with the old kernel of the same name w
 """
 import os
 import re
-import shutil
 import subprocess
 import sys
 import tempfile
 
-import yaml
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "tests"))
+from codeobj_common import _tool, kernel_metadata  # noqa: E402  (the reader the CPU tests use)
 
 KEYS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count",
         ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
-def tool(name):
-    p = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", name)
-    return p if os.access(p, os.X_OK) else shutil.which(name)
-
-
 def kernels(lib):
+    """{demangled kernel name: metadata}"""
     with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, "fat"), os.path.join(d, "co.o")
-        subprocess.check_call([tool("llvm-objcopy"), "--dump-section=.hip_fatbin=" + fat, lib, os.path.join(d, "x")])
-        subprocess.check_call([tool("clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-        notes = subprocess.check_output([tool("llvm-readelf"), "--notes", co], text=True)
-    doc = notes[notes.index("---"):notes.index("\n...", notes.index("---"))]
-    ks = yaml.safe_load(doc)["amdhsa.kernels"]
-    filt = tool("llvm-cxxfilt") or tool("c++filt")
+        ks = list(kernel_metadata(lib, d).values())
+    filt = _tool("llvm-cxxfilt") or _tool("c++filt")
     names = subprocess.check_output([filt] + [k[".name"] for k in ks], text=True).split("\n")
-    out = {}
-    for k, nm in zip(ks, names):
-        out[re.sub(r"\(.*$", "", nm).replace("void ", "").replace("mpc::", "")] = k
-    return out
+    return {re.sub(r"\(.*$", "", nm).replace("void ", "").replace("mpc::", ""): k for k, nm in zip(ks, names)}
 
 
 def waves(k):
