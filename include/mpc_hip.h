@@ -38,7 +38,8 @@ enum { MPC_MODEL_KINEMATIC = 0, /* dynamics.py:122-173, nx = 4 [x, y, phi, v] */
 enum { MPC_WRAP_FLOOR = 0, MPC_WRAP_FMOD = 1, MPC_WRAP_IEEE = 2 }; /* car_dynamics.py:168-172 */
 enum { MPC_CONSTR_NONE = 0,     /* m = 0 (== main.py:57 left commented: D = R^m) */
        MPC_CONSTR_STATE_SQ = 1, /* main.py:43-52: g = x_i^2 - off_i per stage, bounds D_lb/D_ub */
-       MPC_CONSTR_LANE = 2 };   /* signed lateral distance to the centerline within +-halfwidth */
+       MPC_CONSTR_LANE = 2,     /* signed lateral distance to the centerline within +-halfwidth */
+       MPC_CONSTR_DISCS = 3 };  /* MPC_NDISC keep-out discs per stage and agent (mpc_set_agent_discs): m = MPC_NDISC N */
 /* alpaqa SolverStatus values read at controller.py:59-64 */
 enum { MPC_ST_UNKNOWN = 0, MPC_ST_CONVERGED = 1, MPC_ST_MAXTIME = 2, MPC_ST_MAXITER = 3,
        MPC_ST_NOTFINITE = 4, MPC_ST_NOPROGRESS = 5, MPC_ST_INTERRUPTED = 6 };
@@ -160,6 +161,41 @@ int mpc_set_agent_bounds(mpc_handle *h, const double *table, int P, const int32_
 #define MPC_NCONSTR 19
 int mpc_default_constraints(const mpc_config *cfg, double *row);
 int mpc_set_agent_constraints(mpc_handle *h, const double *table, int P, const int32_t *index, int B);
+
+/* Per-agent, per-stage keep-out discs (constr_mode MPC_CONSTR_DISCS): a table of P rows in device memory and one row
+ * index per agent, beside the three tables above -- the one table whose data varies with the stage.  One row, all
+ * doubles: [N][MPC_NDISC][3] = (cx, cy, r), MPC_DISC_ROW(N) of them.  Constraint kk = MPC_NDISC k + j of an agent is disc
+ * j of stage k, taken -- as every general constraint is -- at the state at the end of stage k (x_{k+1}):
+ *     dx = x - cx, dy = y - cy, g = (dx dx + dy dy) - r r   within [0, +inf)
+ * every operation rounded on its own.  A disc with r = 0 is vacuous (g = d^2 >= 0): that is how "no obstacle at this
+ * stage" is said.  The bounds [0, +inf) are the same for every agent; g_off, D_lb, D_ub and lane_halfwidth of the
+ * configuration are not read in this mode.
+ * mpc_default_discs (host only): a row of zeros, MPC_DISC_ROW(cfg->N) doubles.
+ * mpc_set_agent_discs: table == NULL unbinds.  The discs have no shared value to fall back on: on a handle of
+ * MPC_CONSTR_DISCS the calls that evaluate constraints -- mpc_eval_cost_grad(_wave), mpc_solve_batch(_async),
+ * mpc_solve_active, mpc_closed_loop(_event, _track) -- return MPC_E_ARG before any launch while no disc table is bound;
+ * bound, they use row index[b] for agent b and return MPC_E_ARG for a batch size other than B.  The table is independent
+ * of the parameter and bounds tables: any of them may be bound beside it; bound together they are for the same B
+ * (MPC_E_ARG otherwise), each with its own index.  table [P][MPC_DISC_ROW(N)] and index [B] are DEVICE memory of the
+ * caller, read at every call: rows may be rewritten in place between calls without binding again (a host loop of solves
+ * that moves the obstacles does exactly that).  The P rows are checked once, at bind time, through a synchronous copy:
+ * every value finite and r >= 0; index ranges are the caller's to check (the Python front end does).  Refused
+ * (MPC_E_ARG) while an asynchronous solve is in flight and on a handle of another constr_mode;
+ * mpc_set_agent_constraints is refused on a handle of MPC_CONSTR_DISCS (there is no constraint data to bind).
+ * The closed loops read the table as it is bound -- obstacles standing on the track: stage k of every re-plan reads
+ * entry k of the agent's row.
+ * mpc_discs_from_plans: the gather for inter-agent avoidance, asynchronous on `stream`.  X [B][N][nx] is what
+ * mpc_rollout wrote for the agents' current plans, opp [B][MPC_NDISC] (int32) the opponents of agent b (< 0 or >= B:
+ * none), radius [B] the radius of agent b as an obstacle; table [B][MPC_DISC_ROW(N)] receives
+ * table[b][k][j] = (X[o][k][0], X[o][k][1], radius[o]) for o = opp[b][j], or zeros where there is no opponent.  Every
+ * word written is a copy of an input word or zero.  With index = 0 .. B-1 bound this is "everyone avoids everyone's
+ * last plan", one sweep of an iterated best response, without leaving the device.  All four are device memory. */
+#define MPC_NDISC 2
+#define MPC_DISC_ROW(N) (3 * MPC_NDISC * (N))
+int mpc_default_discs(const mpc_config *cfg, double *row);
+int mpc_set_agent_discs(mpc_handle *h, const double *table, int P, const int32_t *index, int B);
+int mpc_discs_from_plans(mpc_handle *h, int B, const double *X, const int32_t *opp, const double *radius, double *table,
+                         void *stream);
 
 /* a-1 (car_dynamics.py:93-132 / dynamics.py:67-119,:144-173): dx[B][nx] = f(x[B][nx], u[B][2]) */
 int mpc_rhs(mpc_handle *h, int B, const double *x, const double *u, double *dx, void *stream);

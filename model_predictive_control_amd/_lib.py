@@ -37,7 +37,7 @@ _HDR = os.path.join(os.path.dirname(_HERE), "include", "mpc_hip.h")
 
 MODEL_KINEMATIC, MODEL_PACEJKA = 0, 1
 WRAP_FLOOR, WRAP_FMOD, WRAP_IEEE = 0, 1, 2
-CONSTR_NONE, CONSTR_STATE_SQ, CONSTR_LANE = 0, 1, 2
+CONSTR_NONE, CONSTR_STATE_SQ, CONSTR_LANE, CONSTR_DISCS = 0, 1, 2, 3
 NSTATS = 8
 ST_CONVERGED = 1
 
@@ -54,6 +54,7 @@ EXPORTS = [
     "mpc_solve_active", "mpc_trigger_eval", "mpc_closed_loop_event",
     "mpc_default_bounds", "mpc_set_agent_bounds",
     "mpc_default_constraints", "mpc_set_agent_constraints",
+    "mpc_default_discs", "mpc_set_agent_discs", "mpc_discs_from_plans",
     "mpc_track_init", "mpc_track_windows", "mpc_track_locate", "mpc_track_select", "mpc_closed_loop_track",
 ]
 NREC = 64
@@ -61,6 +62,7 @@ NPARAM = 31     # MPC_NPARAM: doubles per row of the per-agent parameter table
 # columns of a row, by field name (include/mpc_hip.h: mpc_set_agent_params)
 NBOUND = 4      # MPC_NBOUND: doubles per row of the per-agent bounds table, [u_lb[0], u_lb[1], u_ub[0], u_ub[1]]
 NCONSTR = 19    # MPC_NCONSTR: doubles per row of the per-agent constraint table
+NDISC = 2       # MPC_NDISC: keep-out discs per stage; a row of the disc table is [N][NDISC][3] = (cx, cy, r)
 # columns of a constraint row, by field name (include/mpc_hip.h: mpc_set_agent_constraints)
 CONSTR_FIELDS = {"g_off": (0, 6), "D_lb": (6, 6), "D_ub": (12, 6), "lane_halfwidth": (18, 1)}
 PARAM_FIELDS = {"veh": (0, 22), "accel": (22, 1), "friction": (23, 1), "v_ref": (24, 1), "cost_w": (25, 6)}
@@ -175,6 +177,9 @@ def load():
     L.mpc_set_agent_bounds.argtypes = [vp, vp, ci, vp, ci]
     L.mpc_default_constraints.argtypes = [cp, C.POINTER(C.c_double)]
     L.mpc_set_agent_constraints.argtypes = [vp, vp, ci, vp, ci]
+    L.mpc_default_discs.argtypes = [cp, C.POINTER(C.c_double)]
+    L.mpc_set_agent_discs.argtypes = [vp, vp, ci, vp, ci]
+    L.mpc_discs_from_plans.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.mpc_step_lds_plan.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     L.mpc_math_probe.argtypes = [vp, ci, ci, vp, vp, vp, vp]
     L.mpc_lane_payoff.argtypes = [vp, ci, ci, C.POINTER(C.c_double), vp, vp, vp, vp, vp]
@@ -305,6 +310,37 @@ def constraint_rows(cfg, P, g_off=None, D_lb=None, D_ub=None, lane_halfwidth=Non
                               ("lane_halfwidth", lane_halfwidth, (1,))):
         if val is not None:
             _set_field("constraint_rows", tab, name, val, CONSTR_FIELDS[name][0], widths)
+    return tab
+
+
+def disc_row_width(cfg):
+    """MPC_DISC_ROW(N): doubles per row of the disc table of `cfg`'s horizon."""
+    return 3 * NDISC * int(cfg.N)
+
+
+def default_discs(cfg):
+    """mpc_default_discs: the row of the disc table that says "no obstacle at any stage", float64 [3 NDISC N] of zeros."""
+    return _default_row("mpc_default_discs", disc_row_width(cfg), cfg)
+
+
+def disc_rows(cfg, P, centres=None, radii=None):
+    """A disc table for BatchedMPC.set_agent_discs, on the host: float64 [P, 3 NDISC N], row layout [N][NDISC][3] =
+    (cx, cy, r), default_discs(cfg) with `centres` [P, N, NDISC, 2] (or [N, NDISC, 2]: every row) and `radii`
+    [P, N, NDISC] (or [N, NDISC]: every row; or a scalar) in their place.  Pure host code: usable without a GPU."""
+    import numpy as np
+    tab = _default_table("disc_rows", default_discs, cfg, P)
+    P, N = tab.shape[0], int(cfg.N)
+    v = tab.reshape(P, N, NDISC, 3)          # a view: writes land in tab
+    if centres is not None:
+        c = np.asarray(centres, dtype=np.float64)
+        if c.shape not in ((N, NDISC, 2), (P, N, NDISC, 2)):
+            raise ValueError(f"disc_rows: centres must have shape ({N}, {NDISC}, 2) or ({P}, {N}, {NDISC}, 2), got {c.shape}")
+        v[..., :2] = c
+    if radii is not None:
+        r = np.asarray(radii, dtype=np.float64)
+        if r.shape not in ((), (N, NDISC), (P, N, NDISC)):
+            raise ValueError(f"disc_rows: radii must be a scalar or have shape ({N}, {NDISC}) or ({P}, {N}, {NDISC}), got {r.shape}")
+        v[..., 2] = r
     return tab
 
 

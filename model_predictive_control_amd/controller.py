@@ -46,13 +46,16 @@ class MPCController:
         Dlb = _tiled(problem.D.lowerbound, nx, "problem.D.lowerbound")
         Dub = _tiled(problem.D.upperbound, nx, "problem.D.upperbound")
         constrained = bool(np.any(np.isfinite(Dlb)) or np.any(np.isfinite(Dub)))
+        # problem.keep_out_discs (not in the reference): the general constraints are keep-out discs per agent and stage
+        # (CONSTR_DISCS), supplied to solve() / step() as discs= ; problem.D is then not read
+        discs = bool(getattr(problem, "keep_out_discs", False))
         pad = [0.0] * (6 - nx)
         # controller.py:27-48: ProjGradNorm2, max_iter 1000, heuristic 15, memory N_horiz,
         # eps 1e-6, delta 1e-4, Sigma_0 1e5, outer max_iter 1000 (mpc_default_config holds them)
         self.cfg = _lib.default_config(
             model.MODEL_ID, N, S=S, Ts=float(model.Ts), v_ref=float(problem.v_ref), veh=list(veh),
             u_lb=list(lb), u_ub=list(ub), lbfgs_memory=N,
-            constr_mode=_lib.CONSTR_STATE_SQ if constrained else _lib.CONSTR_NONE,
+            constr_mode=_lib.CONSTR_DISCS if discs else _lib.CONSTR_STATE_SQ if constrained else _lib.CONSTR_NONE,
             D_lb=list(Dlb) + [-np.inf] * len(pad), D_ub=list(Dub) + [np.inf] * len(pad),
             wrap_mode=int(getattr(problem, "wrap_mode", _lib.WRAP_FLOOR)),
             max_total_inner=int(getattr(problem, "max_total_inner", 5000)))
@@ -60,7 +63,7 @@ class MPCController:
         self.device = self.solver.device
         self._veh0 = veh.copy()      # the vehicle part of problem.param the handle was created from
         self._nx, self._S = nx, S
-        self._constrained = constrained
+        self._constrained = constrained or discs
         self.last_stats = None
 
     # ------------------------------------------------------------------ reference entry point
@@ -103,14 +106,17 @@ class MPCController:
 
     # ------------------------------------------------------------------ batched entry points
     def solve(self, Y0, centerline, U0=None, lam0=None, cl_index=None, params=None, param_index=None,
-              bounds=None, bound_index=None, constraints=None, constraint_index=None):
+              bounds=None, bound_index=None, constraints=None, constraint_index=None, discs=None, disc_index=None):
         """Batched solve: Y0 [B, nx], centerline [2S] or [C, 2S] (+ cl_index[B]) -> (U [B, 2N], stats).
         params [P, 31] (rows as _lib.param_rows makes them) + param_index [B] (None: agent b uses row b % P): this
         solve runs agent b on its own vehicle and cost parameters (BatchedMPC.set_agent_params).
         bounds [P', 4] (rows as _lib.bound_rows makes them) + bound_index [B] (None: agent b uses row b % P'): this solve
         projects agent b's inputs onto its own box (BatchedMPC.set_agent_bounds).
         constraints [P", 19] (rows as _lib.constraint_rows makes them) + constraint_index [B] (None: agent b uses row
-        b % P"): this solve holds agent b to its own constraint data (BatchedMPC.set_agent_constraints)."""
+        b % P"): this solve holds agent b to its own constraint data (BatchedMPC.set_agent_constraints).
+        discs [P°, 6N] (rows as _lib.disc_rows makes them) + disc_index [B] (None: agent b uses row b % P°): this solve
+        keeps agent b out of the discs of its own row, stage by stage (BatchedMPC.set_agent_discs; a controller whose
+        problem has keep_out_discs set needs them in every solve)."""
         dev = self.device
         Y0 = torch.as_tensor(Y0, dtype=torch.float64, device=dev).contiguous()
         B = Y0.shape[0]
@@ -126,7 +132,8 @@ class MPCController:
         tables = []                                       # (kind, table, index) of the tables this call binds
         for kind, table, index, name in (("params", params, param_index, "param_index"),
                                          ("bounds", bounds, bound_index, "bound_index"),
-                                         ("constraints", constraints, constraint_index, "constraint_index")):
+                                         ("constraints", constraints, constraint_index, "constraint_index"),
+                                         ("discs", discs, disc_index, "disc_index")):
             if table is None:
                 if index is not None:
                     raise ValueError(f"{name} needs {kind}")
@@ -148,10 +155,10 @@ class MPCController:
         return U, stats
 
     def step(self, Y0, centerline, U0=None, lam0=None, cl_index=None, params=None, param_index=None,
-             bounds=None, bound_index=None, constraints=None, constraint_index=None):
+             bounds=None, bound_index=None, constraints=None, constraint_index=None, discs=None, disc_index=None):
         """First control of every agent, u0 [B, 2] (main.py:141 input_to_matrix(U)[:, 0])."""
         U, _ = self.solve(Y0, centerline, U0, lam0, cl_index, params, param_index, bounds, bound_index,
-                          constraints, constraint_index)
+                          constraints, constraint_index, discs, disc_index)
         return U[:, :2].contiguous()
 
 

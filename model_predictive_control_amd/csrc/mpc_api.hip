@@ -80,6 +80,15 @@ extern "C" int mpc_default_constraints(const mpc_config *c, double *row)
     return MPC_OK;
 }
 
+static_assert(MPC_NDISC == mpc::NDISC, "row layout: include/mpc_hip.h and mpc_device.hpp");
+extern "C" int mpc_default_discs(const mpc_config *c, double *row)
+{
+    if (!c || !row) return fail(MPC_E_ARG, "mpc_default_discs: null argument");
+    if (c->N < 1 || c->N > MPC_MAX_N) return fail(MPC_E_ARG, "mpc_default_discs: horizon N out of range [1, 64]");
+    for (int i = 0; i < MPC_DISC_ROW(c->N); i++) row[i] = 0.0;   // r = 0: no obstacle at any stage
+    return MPC_OK;
+}
+
 extern "C" int mpc_create(const mpc_config *cfg, int device, mpc_handle **out)
 {
     if (!cfg || !out) return fail(MPC_E_ARG, "mpc_create: null argument");
@@ -219,6 +228,18 @@ static int constr_row_rule(const mpc_handle *h, const double *r, const std::stri
     return MPC_OK;
 }
 
+// keep-out discs: every value finite, no negative radius
+static int disc_row_rule(const mpc_handle *h, const double *r, const std::string &where)
+{
+    for (int i = 0; i < h->cfg.N * MPC_NDISC; i++) {
+        const std::string which = ", stage " + std::to_string(i / MPC_NDISC) + ", disc " + std::to_string(i % MPC_NDISC);
+        for (int f = 0; f < 3; f++)
+            if (!std::isfinite(r[3 * i + f])) return fail(MPC_E_ARG, where + which + ": (cx, cy, r) must be finite");
+        if (!(r[3 * i + 2] >= 0.0)) return fail(MPC_E_ARG, where + which + ": the radius must not be negative");
+    }
+    return MPC_OK;
+}
+
 // Binds (table != NULL) or unbinds the per-agent table of one kind.  The rows are checked once, here, through a
 // synchronous copy (binding is not on the hot path; rows rewritten in place later are the caller's to keep valid).
 // Nothing else is done: the kernels read the caller's memory at every call.  The box and constraint forms of some
@@ -227,11 +248,16 @@ static int bind_agent_table(mpc_handle *h, TableKind kind, const double *table, 
                             int (*row_rule)(const mpc_handle *, const double *, const std::string &))
 {
     const char *who = k_tables[kind].setter;
-    const size_t width = (size_t)k_tables[kind].width;
     { const int rb = refuse_if_busy(h, who); if (rb) return rb; }
+    const size_t width = h->table_width(kind);
     if (!table) { h->tab[kind] = BoundTable{}; return MPC_OK; }
     if (kind == TAB_CONSTR && h->cfg.constr_mode == MPC_CONSTR_NONE)
         return fail(MPC_E_ARG, std::string(who) + ": the handle has no general constraints (constr_mode MPC_CONSTR_NONE)");
+    if (kind == TAB_CONSTR && h->cfg.constr_mode == MPC_CONSTR_DISCS)
+        return fail(MPC_E_ARG, std::string(who) + ": the handle's constraints are keep-out discs (constr_mode MPC_CONSTR_DISCS): "
+                                                  "there is no constraint data to bind (mpc_set_agent_discs)");
+    if (kind == TAB_DISCS && h->cfg.constr_mode != MPC_CONSTR_DISCS)
+        return fail(MPC_E_ARG, std::string(who) + ": the handle's constr_mode is not MPC_CONSTR_DISCS");
     if (P < 1 || B < 1 || !index) return fail(MPC_E_ARG, std::string(who) + ": need P >= 1 rows, B >= 1 agents and an index");
     { const int ra = check_tables_agree(h, B, who, kind); if (ra) return ra; }
     HIPCHK(hipSetDevice(h->device));
@@ -260,6 +286,25 @@ extern "C" int mpc_set_agent_bounds(mpc_handle *h, const double *table, int P, c
 extern "C" int mpc_set_agent_constraints(mpc_handle *h, const double *table, int P, const int32_t *index, int B)
 {
     return bind_agent_table(h, TAB_CONSTR, table, P, index, B, constr_row_rule);
+}
+
+extern "C" int mpc_set_agent_discs(mpc_handle *h, const double *table, int P, const int32_t *index, int B)
+{
+    return bind_agent_table(h, TAB_DISCS, table, P, index, B, disc_row_rule);
+}
+
+// The discs of everybody's opponents from everybody's plans: a pure gather (discs_from_plans_kernel), asynchronous
+extern "C" int mpc_discs_from_plans(mpc_handle *h, int B, const double *X, const int32_t *opp, const double *radius,
+                                    double *table, void *stream)
+{
+    int rc = check_common(h, B, "mpc_discs_from_plans"); if (rc) return rc;
+    if (B == 0) return MPC_OK;
+    if (!X || !opp || !radius || !table) return fail(MPC_E_ARG, "mpc_discs_from_plans: null buffer");
+    const size_t words = (size_t)B * h->cfg.N * MPC_NDISC;
+    hipLaunchKernelGGL(discs_from_plans_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, h->cfg.N,
+                       h->dc.nx, X, opp, radius, table);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
 }
 
 extern "C" int mpc_rhs(mpc_handle *h, int B, const double *x, const double *u, double *dx, void *stream)
@@ -354,7 +399,7 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     if (!x0 || !cl || !U || !psi) return fail(MPC_E_ARG, "mpc_eval_cost_grad: null buffer");
     const DevCfg &c = h->dc;
     if (c.m && (!y || !Sigma)) return fail(MPC_E_ARG, "mpc_eval_cost_grad: y and Sigma are required when m > 0");
-    rc = check_tables(h, B, "mpc_eval_cost_grad", READS_PARAMS | READS_CONSTR); if (rc) return rc;
+    rc = check_tables(h, B, "mpc_eval_cost_grad", READS_PARAMS | READS_CONSTR | READS_DISCS, true); if (rc) return rc;
     rc = reserve(h, B); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     // direct mode: the kernel reads and writes the caller's agent-major buffers in place
@@ -366,6 +411,7 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     w.psi_direct = psi;
     w.ptab = h->params().table; w.pidx = h->params().idx;
     w.ctab = h->tab[TAB_CONSTR].table; w.cidx = h->tab[TAB_CONSTR].idx;
+    w.dtab = h->tab[TAB_DISCS].table; w.didx = h->tab[TAB_DISCS].idx;
     if (wave_path) launch_solo_eval(h, w, s, grad ? 1 : 0);
     else launch_eval(h, w, s, nullptr, nullptr, grad ? B : 0, grad ? 0 : B);
     HIPCHK(hipGetLastError());
@@ -440,6 +486,7 @@ static int solve_core(mpc_handle *h, int B, const double *x0, const double *cl, 
     w.ptab = h->tab[TAB_PARAMS].table; w.pidx = rows_of(TAB_PARAMS);
     w.btab = h->tab[TAB_BOX].table; w.bidx = rows_of(TAB_BOX);
     w.ctab = h->tab[TAB_CONSTR].table; w.cidx = rows_of(TAB_CONSTR);
+    w.dtab = h->tab[TAB_DISCS].table; w.didx = rows_of(TAB_DISCS);
     w.xe = w.ws_xe; w.ge = w.ws_ge; w.yhe = w.ws_yhe; w.Sig = w.ws_Sig;
     rc = run_solver(h, s); if (rc) return rc;
     if (stats) hipLaunchKernelGGL(stats_kernel, grid_for(B, 256), dim3(256), 0, s, w, stats);
@@ -453,7 +500,7 @@ static int solve_batch_impl(mpc_handle *h, int B, const double *x0, const double
     if (B == 0) return MPC_OK;
     if (!x0 || !cl || !U) return fail(MPC_E_ARG, "mpc_solve_batch: null buffer");
     if (h->dc.m && !lambda) return fail(MPC_E_ARG, "mpc_solve_batch: lambda is required when m > 0");
-    rc = check_tables(h, B, "mpc_solve_batch", READS_ALL); if (rc) return rc;
+    rc = check_tables(h, B, "mpc_solve_batch", READS_ALL, true); if (rc) return rc;
     return solve_core(h, B, x0, cl, cl_index, h->bound_rows(), U, lambda, stats, (hipStream_t)stream);
 }
 extern "C" int mpc_solve_batch(mpc_handle *h, int B, const double *x0, const double *cl, const int32_t *cl_index, double *U,
@@ -520,7 +567,7 @@ extern "C" int mpc_closed_loop(mpc_handle *h, int B, int T, int shift, double *x
     if (T < 0 || !x || !cl || !U) return fail(MPC_E_ARG, "mpc_closed_loop: bad argument");
     const DevCfg &c = h->dc;
     if (c.m && !lambda) return fail(MPC_E_ARG, "mpc_closed_loop: lambda is required when m > 0");
-    rc = check_tables(h, B, "mpc_closed_loop", READS_ALL); if (rc) return rc;
+    rc = check_tables(h, B, "mpc_closed_loop", READS_ALL, true); if (rc) return rc;
     // bound table: the controller solves with row pidx[b], the plant advances with row pidx_plant[b] (null: the same)
     hipStream_t s = (hipStream_t)stream;
     double *st = stats;
@@ -560,7 +607,7 @@ static int solve_active_impl(mpc_handle *h, int B, const int32_t *active, const 
     r.cl_index = cl_index; r.pidx = h->params().idx;
     r.xs = e.xs; r.Us = e.Us; r.lams = e.lams; r.stats_s = e.stats_s; r.cis = e.cis; r.pis = e.pis;
     hipLaunchKernelGGL(active_gather_kernel, grows, dim3(EV_BLK), 0, s, r);
-    const AgentIdx gathered = {{e.pis, e.bis, e.kis}};   // (the parameter rows ride in the gather above)
+    const AgentIdx gathered = {{e.pis, e.bis, e.kis, e.dis}};   // (the parameter rows ride in the gather above)
     for (int k = TAB_BOX; k < TAB_KINDS; k++)
         if (h->tab[k].table)
             hipLaunchKernelGGL(active_index_kernel, gblk, dim3(EV_BLK), 0, s, e.list, e.count, h->tab[k].idx, const_cast<int32_t *>(gathered.of[k]));
@@ -588,7 +635,7 @@ extern "C" int mpc_solve_active(mpc_handle *h, int B, const int32_t *active, con
     if (B == 0) return MPC_OK;
     if (!active || !x0 || !cl || !U) return fail(MPC_E_ARG, "mpc_solve_active: null buffer");
     if (h->dc.m && !lambda) return fail(MPC_E_ARG, "mpc_solve_active: lambda is required when m > 0");
-    rc = check_tables(h, B, "mpc_solve_active", READS_ALL); if (rc) return rc;   // the caller's B; the compact batch is the library's
+    rc = check_tables(h, B, "mpc_solve_active", READS_ALL, true); if (rc) return rc;   // the caller's B; the compact batch is the library's
     return solve_active_impl(h, B, active, x0, cl, cl_index, U, lambda, stats, n_active, (hipStream_t)stream, true);
 }
 
@@ -738,7 +785,7 @@ static int closed_loop_event_impl(const char *who_, mpc_handle *h, int B, int T,
     if (!x || !cl || !U || (trk && !cl_index_rw)) return fail(MPC_E_ARG, who + ": null buffer");
     const DevCfg &c = h->dc;
     if (c.m && !lambda) return fail(MPC_E_ARG, who + ": lambda is required when m > 0");
-    rc = check_tables(h, B, who_, READS_ALL); if (rc) return rc;
+    rc = check_tables(h, B, who_, READS_ALL, true); if (rc) return rc;
     rc = reserve_event(h, B); if (rc) return rc;
     bool fresh = false;
     rc = reserve_xhat(h, B, &fresh); if (rc) return rc;

@@ -122,6 +122,17 @@ MPC_DEV void agent_con_uniform(DevCfg &c, const double *__restrict__ tab, const 
     agent_con_from(c, [=](int f) { return r[f]; });
 }
 
+// mpc_set_agent_discs (constr_mode 3): a table [P][N][NDISC][3] of keep-out discs (cx, cy, r) in device memory and one row
+// index per agent -- the one table whose data varies with the stage.  Constraint kk = NDISC k + j of an agent is disc j of
+// stage k, taken at the state at the end of the stage: g = (dx dx + dy dy) - r r within [0, +inf), dx = x - cx,
+// dy = y - cy, every operation rounded on its own; r = 0 makes it vacuous (g = d^2 >= 0).  The six doubles of a stage
+// never enter a DevCfg: the disc forms of the kernels that evaluate constraints (trailing DiscTab argument:
+// mpc_solver.hpp) load them where the stage is evaluated and hand them to stage_record (mpc_eval.hpp).  The bounds
+// are the same for everybody and sit in the handle's DevCfg (D_lb = 0, D_ub = +inf: make_devcfg), where
+// constraint_bounds finds them for K1b and the state machine alike.
+constexpr int NDISC = 2;
+struct StageDiscs { double v[3 * NDISC]; };
+
 // ---------------------------------------------------------------------------------- math
 // The OCML double-precision transcendentals are full-range (Payne-Hanek reduction, dozens of
 // 64-bit literals each) and dominate this kernel's instruction count.  The angles of this problem

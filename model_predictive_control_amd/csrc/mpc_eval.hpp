@@ -483,18 +483,42 @@ __device__ __forceinline__ void stage_geom(const DevCfg &c, const Workspace &w, 
 // two-kernel path (records in the slot-indexed scratch), the fused kernel and the persistent solo kernel
 // (records in LDS).  The cost arithmetic is written with fixed roundings (no contraction, explicit
 // fma): the same request must give the same bits whichever kernel this is inlined into.
-template <int MODEL, class Put>
+// DS: empty, or the stage's keep-out discs (one trailing StageDiscs: the disc forms of the kernels, constr_mode 3) -- the
+// constraints of the stage are then the NDISC discs and nothing else; the ALM terms are formed exactly as below.
+template <int MODEL, class Put, class... DS>
 __device__ __forceinline__ void stage_record(const DevCfg &c, const Workspace &w, int a, bool ch2, bool is_g,
                                              int k, const double (&xs)[ModelDim<MODEL>::NX],
                                              const double (&xe)[ModelDim<MODEL>::NX], double d, double dl,
-                                             const Geom &g, Put put)
+                                             const Geom &g, Put put, const DS &...ds)
 {
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE;
+    static_assert(sizeof...(DS) <= 1, "at most the stage's discs");
     double xb[NX], ub[2] = {0.0, 0.0};
 #pragma unroll
     for (int i = 0; i < NX; i++) xb[i] = 0.0;
     double L = is_g ? stage_cost<MODEL, true>(c, g, xe, d, dl, xb, ub)
                     : stage_cost<MODEL, false>(c, g, xe, d, dl, xb, ub);
+    if constexpr (sizeof...(DS) != 0) {
+#pragma clang fp contract(off)
+        const StageDiscs dz[1] = {ds...};
+        const size_t am = (size_t)a * c.m;
+#pragma unroll
+        for (int j = 0; j < NDISC; j++) {
+            const size_t kk = am + (size_t)(k * NDISC + j);
+            const double dx = xe[0] - dz[0].v[3 * j], dy = xe[1] - dz[0].v[3 * j + 1], r = dz[0].v[3 * j + 2];
+            const double gv = (dx * dx + dy * dy) - r * r;
+            double lb, ubd;
+            constraint_bounds(c, j, lb, ubd);
+            const double sg = w.Sig[kk];
+            const double zeta = gv + w.y[kk] / sg;
+            const double zhat = fmax(lb, fmin(zeta, ubd));
+            const double dd = zeta - zhat;
+            const double yh = sg * dd;
+            L = fma(0.5 * dd, yh, L);
+            if (!ch2) w.yhe[kk] = yh;
+            if (is_g) { xb[0] += yh * 2.0 * dx; xb[1] += yh * 2.0 * dy; }
+        }
+    } else
     if (c.sm) {
 #pragma clang fp contract(off)
         const size_t am = (size_t)a * c.m;
@@ -677,12 +701,15 @@ __device__ __forceinline__ void adjoint_rec_quad_kin(const DevCfg &c, bool is_g,
 // argument: mpc_set_agent_constraints) -- the agent's private DevCfg takes g_off, D_lb, D_ub and the lane halfwidth of
 // the agent's own row next to its parameter row.  The constraint form exists together with PA alone: without a
 // parameter table of the caller's the host binds a one-row table of the handle's own values (mpc_launch.hpp).
+// ... or the disc table (one trailing DiscTab argument: mpc_set_agent_discs, constr_mode 3), on the same terms: the
+// thread loads the six doubles of its own (agent, stage) and stage_record evaluates the discs in the constraints' place.
 template <int MODEL, bool SHARED_CL, bool PA = false, class... CT>
 __global__ void __launch_bounds__(64, (MODEL == KIN ? MPC_K1B_WAVES : MPC_K1B_WAVES_PAC))
 stage_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, int nG_imm, int nC_imm,
              int nblk_max, CT... ct)
 {
     static_assert(sizeof...(CT) == 0 || PA, "the constraint form exists in the per-agent-parameter form alone");
+    constexpr bool DA = has_tab<DiscTab, CT...>;   // the disc form: CT = DiscTab
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE;
 #if MPC_DEV_STAMP == 6
     DevStamp stamp(blockIdx.x);
@@ -719,7 +746,7 @@ stage_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, 
     const auto put = [=](int f, double v) { *(f == JS ? sl : jr + (size_t)f * St) = v; };
     DevCfg cm_;
     if constexpr (PA) { cm_ = c; agent_cfg(cm_, w.ptab, w.pidx, a); }
-    if constexpr (sizeof...(CT) != 0) agent_con(cm_, ct..., a);
+    if constexpr (sizeof...(CT) != 0 && !DA) agent_con(cm_, ct..., a);
     const DevCfg &cm = PA ? cm_ : c;
     if (is_g) stage_sens_record<MODEL>(cm, xs, xe, d, dl, put);
     Geom g;
@@ -729,6 +756,8 @@ stage_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, 
     } else {
         stage_geom(c, w, clp, SHARED_CL ? 0 : w.cl_index[a], xe[0], xe[1], g);
     }
+    if constexpr (DA) stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(ct..., a, k, c.N));
+    else
     stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put);
 }
 
@@ -776,6 +805,7 @@ stage_adjoint_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ 
                      int *__restrict__ desc, CT... ct)
 {
     static_assert(sizeof...(CT) == 0 || PA, "the constraint form exists in the per-agent-parameter form alone");
+    constexpr bool DA = has_tab<DiscTab, CT...>;   // the disc form: CT = DiscTab
     static_assert(MODEL == KIN, "the fused K1b + K1c kernel is the kinematic model's");
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE, BLK = FUSED_BLK;
     extern __shared__ double s_rec[];                    // [JS + 1][N][SPB]; row JS = stage cost
@@ -809,11 +839,13 @@ stage_adjoint_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ 
             const auto put = [=](int f, double v) { r[(size_t)f * NS] = v; };
             DevCfg cm_;
             if constexpr (PA) { cm_ = c; agent_cfg(cm_, w.ptab, w.pidx, a); }
-            if constexpr (sizeof...(CT) != 0) agent_con(cm_, ct..., a);
+            if constexpr (sizeof...(CT) != 0 && !DA) agent_con(cm_, ct..., a);
             const DevCfg &cm = PA ? cm_ : c;
             if (is_g) stage_sens_record<MODEL>(cm, xs, xe, d, dl, put);
             Geom g;
             stage_geom(c, w, clp, SHARED_CL ? 0 : w.cl_index[a], xe[0], xe[1], g);
+            if constexpr (DA) stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(ct..., a, k, N));
+            else
             stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put);
         }
     }

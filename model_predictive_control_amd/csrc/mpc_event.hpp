@@ -209,4 +209,25 @@ __global__ void __launch_bounds__(64) event_step_kernel(const DevCfg c_, int B, 
     }
 }
 
+// mpc_discs_from_plans: table[b][k][j] = (X[o][k][0], X[o][k][1], radius[o]) for o = opp[b][j], zeros where there is no such
+// agent (o < 0 or o >= B).  One thread per (agent, stage, disc); every word written is a copy of an input word or zero.
+__global__ void __launch_bounds__(256) discs_from_plans_kernel(int B, int N, int nx, const double *__restrict__ X,
+                                                               const int *__restrict__ opp, const double *__restrict__ radius,
+                                                               double *__restrict__ table)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)B * N * NDISC) return;
+    const int j = (int)(t % NDISC);
+    const size_t bk = t / NDISC;
+    const int k = (int)(bk % N), b = (int)(bk / N);
+    const int o = opp[(size_t)b * NDISC + j];
+    double cx = 0.0, cy = 0.0, r = 0.0;
+    if (o >= 0 && o < B) {
+        const double *__restrict__ xo = X + ((size_t)o * N + k) * nx;
+        cx = xo[0]; cy = xo[1]; r = radius[o];
+    }
+    double *out = table + t * 3;
+    out[0] = cx; out[1] = cy; out[2] = r;
+}
+
 } // namespace mpc

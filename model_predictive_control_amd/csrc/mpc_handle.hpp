@@ -37,14 +37,18 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
     } while (0)
 
 // The per-agent tables a caller can bind beside the handle's shared values: parameters (mpc_set_agent_params), input
-// boxes (mpc_set_agent_bounds) and constraint data (mpc_set_agent_constraints).  The kinds are walked in this order
-// wherever they are checked; an entry point names the kinds it reads as a mask of READS_* (check_tables).
-enum TableKind { TAB_PARAMS, TAB_BOX, TAB_CONSTR, TAB_KINDS };
-enum : unsigned { READS_PARAMS = 1u << TAB_PARAMS, READS_BOX = 1u << TAB_BOX, READS_CONSTR = 1u << TAB_CONSTR, READS_ALL = (1u << TAB_KINDS) - 1 };
-static constexpr struct { const char *noun, *setter; int width; } k_tables[TAB_KINDS] = {   // messages, doubles per row
-    {"parameter", "mpc_set_agent_params", MPC_NPARAM},
-    {"bounds", "mpc_set_agent_bounds", MPC_NBOUND},
-    {"constraint", "mpc_set_agent_constraints", MPC_NCONSTR}};
+// boxes (mpc_set_agent_bounds), constraint data (mpc_set_agent_constraints) and keep-out discs (mpc_set_agent_discs).  The
+// kinds are walked in this order wherever they are checked; an entry point names the kinds it reads as a mask of READS_*
+// (check_tables).
+enum TableKind { TAB_PARAMS, TAB_BOX, TAB_CONSTR, TAB_DISCS, TAB_KINDS };
+enum : unsigned { READS_PARAMS = 1u << TAB_PARAMS, READS_BOX = 1u << TAB_BOX, READS_CONSTR = 1u << TAB_CONSTR, READS_DISCS = 1u << TAB_DISCS,
+                  READS_ALL = (1u << TAB_KINDS) - 1 };
+// messages, doubles per row (width_per_N: per stage of the handle's horizon -- table_width)
+static constexpr struct { const char *noun, *setter; int width, width_per_N; } k_tables[TAB_KINDS] = {
+    {"parameter", "mpc_set_agent_params", MPC_NPARAM, 0},
+    {"bounds", "mpc_set_agent_bounds", MPC_NBOUND, 0},
+    {"constraint", "mpc_set_agent_constraints", MPC_NCONSTR, 0},
+    {"disc", "mpc_set_agent_discs", 0, 3 * MPC_NDISC}};
 struct BoundTable {
     const double *table = nullptr;         // [rows][k_tables[kind].width], null: none bound
     const int32_t *idx = nullptr;          // [B] the row per agent
@@ -56,14 +60,18 @@ struct AgentIdx { const int32_t *of[TAB_KINDS]; };
 // The workspace as the host keeps it: the kernels' Workspace, the parameter table the per-agent kernels get with it
 // (WorkspacePA), and the bounds table of mpc_set_agent_bounds (both null: none bound), which reaches the per-agent-box
 // kernels as an argument of its own (BoxTab) and no other kernel at all; the constraint table of
-// mpc_set_agent_constraints likewise (ConTab, the constraint forms alone).
+// mpc_set_agent_constraints likewise (ConTab, the constraint forms alone), and the disc table of mpc_set_agent_discs
+// (DiscTab, the disc forms alone).
 struct WorkspaceHost : WorkspacePA {
     const double *btab;                            // [P][MPC_NBOUND] caller's table
     const int *bidx;                               // [B]             caller's row index per agent
     const double *ctab;                            // [P][MPC_NCONSTR] caller's table
     const int *cidx;                               // [B]              caller's row index per agent
+    const double *dtab;                            // [P][MPC_DISC_ROW(N)] caller's table
+    const int *didx;                               // [B]              caller's row index per agent
     BoxTab box() const { return BoxTab{btab, bidx}; }
     ConTab con() const { return ConTab{ctab, cidx}; }
+    DiscTab disc() const { return DiscTab{dtab, didx}; }
 };
 
 struct mpc_handle {
@@ -147,13 +155,14 @@ struct mpc_handle {
     bool spin = false;             // the round loop busy-waits instead of napping (MPC_SPIN)
     bool host_timing = false;      // the round loop prints its host-side times to stderr (MPC_HOST_TIMING)
     std::string host_trace;        // file the round loop appends one line per polled window to (MPC_HOST_TRACE; empty: none)
-    // The caller's per-agent tables, one per kind (mpc_set_agent_params / _bounds / _constraints; device memory, read at
+    // The caller's per-agent tables, one per kind (mpc_set_agent_params / _bounds / _constraints / _discs; device memory, read at
     // every call).  A kind with none bound runs the handle's values through the kernels that have always run.
     BoundTable tab[TAB_KINDS];
     const int32_t *pidx_plant = nullptr;   // parameters alone: [B] the plant's row per agent (mpc_closed_loop), null: the controller's
     const BoundTable &params() const { return tab[TAB_PARAMS]; }
     const int32_t *plant_rows() const { return pidx_plant ? pidx_plant : params().idx; }
-    AgentIdx bound_rows() const { return AgentIdx{{tab[TAB_PARAMS].idx, tab[TAB_BOX].idx, tab[TAB_CONSTR].idx}}; }
+    AgentIdx bound_rows() const { return AgentIdx{{tab[TAB_PARAMS].idx, tab[TAB_BOX].idx, tab[TAB_CONSTR].idx, tab[TAB_DISCS].idx}}; }
+    size_t table_width(int kind) const { return (size_t)k_tables[kind].width + (size_t)k_tables[kind].width_per_N * (size_t)cfg.N; }
     // The persistent kernel has its box form together with the parameter form alone, and its constraint form -- as the
     // K1 kernels have theirs -- together with both.  With a table bound but not the ones its kernels come with, they run
     // on these one-row tables of the handle's own values (bit for bit the shared path: tests/test_gpu_agent_params.py,
@@ -171,14 +180,17 @@ struct mpc_handle {
     struct EventBufs {
         char *base = nullptr;
         int cap = 0;                                   // agents the arena holds
-        int *list = nullptr, *blk = nullptr, *count = nullptr, *fire = nullptr, *cis = nullptr, *pis = nullptr, *bis = nullptr, *kis = nullptr;
+        int *list = nullptr, *blk = nullptr, *count = nullptr, *fire = nullptr, *cis = nullptr, *pis = nullptr, *bis = nullptr, *kis = nullptr, *dis = nullptr;
         double *xs = nullptr, *Us = nullptr, *lams = nullptr, *stats_s = nullptr, *stats_own = nullptr;
         double *xhat = nullptr;                        // [xhat_B][nx]
         int xhat_B = 0;
     } ev;
 };
 
-static int stage_m(const mpc_config *c) { return c->constr_mode == MPC_CONSTR_STATE_SQ ? mpc_nx(c) : c->constr_mode == MPC_CONSTR_LANE ? 1 : 0; }
+static int stage_m(const mpc_config *c)
+{
+    return c->constr_mode == MPC_CONSTR_STATE_SQ ? mpc_nx(c) : c->constr_mode == MPC_CONSTR_LANE ? 1 : c->constr_mode == MPC_CONSTR_DISCS ? MPC_NDISC : 0;
+}
 
 // the input box rule of mpc_create and mpc_set_agent_bounds: u_lb[i] <= u_ub[i] (a NaN fails it, infinities pass)
 static bool box_ok(const double *lb, const double *ub)
@@ -195,7 +207,7 @@ static int make_devcfg(const mpc_config &c, DevCfg &d)
     if (c.nfe < 1 || c.nfe > 16) return fail(MPC_E_ARG, "nfe out of range [1, 16]");
     if (c.lbfgs_memory < 1 || c.lbfgs_memory > 64) return fail(MPC_E_ARG, "lbfgs_memory out of range [1, 64]");
     if (c.model != MPC_MODEL_KINEMATIC && c.model != MPC_MODEL_PACEJKA) return fail(MPC_E_ARG, "unknown model");
-    if (c.constr_mode < 0 || c.constr_mode > 2) return fail(MPC_E_ARG, "unknown constr_mode");
+    if (c.constr_mode < 0 || c.constr_mode > MPC_CONSTR_DISCS) return fail(MPC_E_ARG, "unknown constr_mode");
     if (c.max_no_progress < 1) return fail(MPC_E_ARG, "max_no_progress must be >= 1");
     if (c.max_iter < 1 || c.max_outer < 1 || c.max_total_inner < 1 || c.max_total_evals < 0)
         return fail(MPC_E_ARG, "max_iter, max_outer, max_total_inner must be >= 1 and max_total_evals >= 0");
@@ -229,6 +241,10 @@ static int make_devcfg(const mpc_config &c, DevCfg &d)
     d.accel = c.accel; d.friction = c.friction;
     for (int i = 0; i < 2; i++) { d.u_lb[i] = c.u_lb[i]; d.u_ub[i] = c.u_ub[i]; }
     d.lane_hw = c.lane_halfwidth;
+    // keep-out discs: g >= 0 for every agent and disc -- the bounds constraint_bounds serves K1b and the state machine with
+    // (the configuration's g_off / D_lb / D_ub are STATE_SQ's and are not read in this mode)
+    if (c.constr_mode == MPC_CONSTR_DISCS)
+        for (int i = 0; i < MPC_NDISC; i++) { d.D_lb[i] = 0.0; d.D_ub[i] = INFINITY; }
     d.alm_eps = c.alm_eps; d.alm_delta = c.alm_delta; d.Sigma0 = c.Sigma0; d.eps0 = c.eps0; d.rho = c.rho;
     d.Delta = c.Delta; d.theta = c.theta; d.Mcap = c.M; d.Sigma_max = c.Sigma_max;
     d.Delta_lower = c.Delta_lower; d.Sigma0_lower = c.Sigma0_lower; d.eps0_increase = c.eps0_increase;
@@ -400,7 +416,7 @@ static int reserve_event(mpc_handle *h, int B)
     const DevCfg &c = h->dc;
     const size_t Bp = ((size_t)B + 63) & ~(size_t)63, m = c.m ? c.m : 1, nblk = (Bp + EV_BLK - 1) / EV_BLK;
     const size_t nd = (size_t)c.nx + c.n + m + 8 + 8;            // doubles per agent: xs, Us, lams, stats_s, stats_own
-    const size_t bytes = nd * 8 * Bp + 4 * (6 * Bp + nblk + 64);  // ints: list, fire, cis, pis, bis, kis [Bp], blk [nblk], count
+    const size_t bytes = nd * 8 * Bp + 4 * (7 * Bp + nblk + 64);  // ints: list, fire, cis, pis, bis, kis, dis [Bp], blk [nblk], count
     char *base = nullptr;
     if (hipMalloc((void **)&base, bytes) != hipSuccess) return fail(MPC_E_ALLOC, "masked-solve staging hipMalloc failed");
     e.base = base; e.cap = (int)Bp;
@@ -409,7 +425,7 @@ static int reserve_event(mpc_handle *h, int B)
     e.xs = takeD(c.nx); e.Us = takeD(c.n); e.lams = takeD(m); e.stats_s = takeD(8); e.stats_own = takeD(8);
     int *ip = (int *)dp;
     auto takeI = [&](size_t cnt) { int *r = ip; ip += cnt; return r; };
-    e.list = takeI(Bp); e.fire = takeI(Bp); e.cis = takeI(Bp); e.pis = takeI(Bp); e.bis = takeI(Bp); e.kis = takeI(Bp); e.blk = takeI(nblk); e.count = takeI(64);
+    e.list = takeI(Bp); e.fire = takeI(Bp); e.cis = takeI(Bp); e.pis = takeI(Bp); e.bis = takeI(Bp); e.kis = takeI(Bp); e.dis = takeI(Bp); e.blk = takeI(nblk); e.count = takeI(64);
     HIPCHK(hipMemset(base, 0, bytes));
     return MPC_OK;
 }
@@ -429,9 +445,14 @@ static int reserve_xhat(mpc_handle *h, int B, bool *fresh)
 }
 
 // A handle with a table bound serves the batch size the table's indices were bound for, and no other, in the calls
-// that read that kind of table (`kinds`: a mask of READS_*).  Parameters, box, constraints: the first mismatch wins.
-static int check_tables(const mpc_handle *h, int B, const char *who, unsigned kinds)
+// that read that kind of table (`kinds`: a mask of READS_*).  Parameters, box, constraints, discs: the first mismatch wins.
+// The discs have no shared values to fall back on: a call that evaluates constraints (`needs_discs`) on a handle of
+// MPC_CONSTR_DISCS with no disc table bound is refused.
+static int check_tables(const mpc_handle *h, int B, const char *who, unsigned kinds, bool needs_discs = false)
 {
+    if (needs_discs && h->cfg.constr_mode == MPC_CONSTR_DISCS && !h->tab[TAB_DISCS].table)
+        return fail(MPC_E_ARG, std::string(who) + ": the handle's constraints are keep-out discs (MPC_CONSTR_DISCS) and no disc table is bound (" +
+                               k_tables[TAB_DISCS].setter + ")");
     for (int k = 0; k < TAB_KINDS; k++) {
         const BoundTable &t = h->tab[k];
         if ((kinds >> k & 1u) && t.table && B != t.B)

@@ -4,7 +4,8 @@
 // added once.  What is instantiated is what the `if constexpr`s below let through -- never the cross product: the
 // Pacejka model has no fused K1b + K1c, lookahead exists for <PAC, NE = 1> alone, adjoint_kernel has no per-agent form,
 // the constraint forms exist beside the parameter form alone (K1b, the wave evaluation), beside the parameter and box
-// forms alone (the persistent kernel) and for constrained problems alone (the step kernel).  Where a form needs a table
+// forms alone (the persistent kernel) and for constrained problems alone (the step kernel); the disc forms stand where
+// the constraint forms stand, except that the step kernel has none (it reads no discs).  Where a form needs a table
 // the caller has not bound, with_own_params / with_own_box put the handle's own one-row table in its place.
 #pragma once
 #include "mpc_handle.hpp"
@@ -106,6 +107,11 @@ static bool launch_eval_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
                     hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, ConTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
                                        with_own_params(h, w), counts, nG, nC, desc, w.con());
                 });
+            else if (w.dtab)     // a disc table is bound (a handle of MPC_CONSTR_DISCS): the disc form of K1b (here and below)
+                with_flag(shared, [&](auto SH) {
+                    hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, DiscTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
+                                       with_own_params(h, w), counts, nG, nC, desc, w.disc());
+                });
             else
             with_flags(shared, pa, [&](auto SH, auto PA) {
                 hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), PA()>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c, w, counts, nG, nC, desc);
@@ -122,6 +128,11 @@ static bool launch_eval_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
         with_flag(shared, [&](auto SH) {
             hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, ConTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
                                with_own_params(h, w), counts, nG, nC, nblk, w.con());
+        });
+    else if (w.dtab)
+        with_flag(shared, [&](auto SH) {
+            hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, DiscTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
+                               with_own_params(h, w), counts, nG, nC, nblk, w.disc());
         });
     else
     with_flags(shared, pa, [&](auto SH, auto PA) {
@@ -146,6 +157,14 @@ static void launch_solo_eval(mpc_handle *h, const WorkspaceHost &w, hipStream_t 
             const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
             hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, ConTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
                                want_grad, w.con());
+        });
+        return;
+    }
+    if (w.dtab) {
+        with_model(c.model, [&](auto MODEL) {
+            const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
+            hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, DiscTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
+                               want_grad, w.disc());
         });
         return;
     }
@@ -268,6 +287,12 @@ static void launch_solo_t(mpc_handle *h, const WorkspaceHost &v, hipStream_t s, 
     if (v.ctab) {
         hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, ConTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
                            with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), v.con());
+        return;
+    }
+    // v.dtab: a disc table is bound, the disc form, on the constraint form's terms
+    if (v.dtab) {
+        hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, DiscTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
+                           with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), v.disc());
         return;
     }
     if (v.btab) {

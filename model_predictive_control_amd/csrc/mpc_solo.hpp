@@ -69,9 +69,11 @@ struct SoloClk { long long roll = 0, recs = 0, adj = 0; };
 #define SOLO_CLK_ARG
 #define SOLO_CLK(field, t) do { } while (0)
 #endif
-template <int MODEL>
+// DS: empty, or the disc table (the disc forms: one trailing DiscTab) -- lane k loads the discs of its stage from the
+// agent's row, whose address is wave-uniform
+template <int MODEL, class... DS>
 __device__ __forceinline__ void solo_eval(const DevCfg &c, const Workspace &w, int a, int lane, int req,
-                                          double *traj, double *rec SOLO_CLK_ARG)
+                                          double *traj, double *rec SOLO_CLK_ARG, const DS &...ds)
 {
 #if MPC_DEV_STAMP == 5
     long long tclk = __builtin_amdgcn_s_memrealtime();
@@ -133,6 +135,8 @@ __device__ __forceinline__ void solo_eval(const DevCfg &c, const Workspace &w, i
         if (is_g) stage_sens_record<MODEL>(c, xs, xe, d, dl, put);
         Geom g;
         stage_geom(c, w, clp, w.cl_index ? w.cl_index[a] : 0, xe[0], xe[1], g);
+        if constexpr (sizeof...(DS) != 0) stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_discs_uniform(ds..., a, hl, N));
+        else
         stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put);
     }
     __builtin_amdgcn_wave_barrier();
@@ -240,14 +244,19 @@ __global__ void __launch_bounds__(64, 1) solo_eval_kernel(const DevCfg c_, const
     // constraint row, the same way)
     DevCfg cm_;
     if constexpr (PA) { cm_ = c_; agent_cfg_uniform(cm_, w.ptab, w.pidx, blockIdx.x); }
-    if constexpr (sizeof...(CT) != 0) agent_con_uniform(cm_, ct..., blockIdx.x);
+    constexpr bool DA = has_tab<DiscTab, CT...>;   // the disc form (CT = DiscTab): the table goes on to the evaluation
+    if constexpr (sizeof...(CT) != 0 && !DA) agent_con_uniform(cm_, ct..., blockIdx.x);
     const DevCfg &c = PA ? cm_ : c_;
     double *traj = s_solo;
     double *rec = traj + (size_t)(c.N + 1) * ModelDim<MODEL>::NX;
 #if MPC_DEV_STAMP == 5
     SoloClk clk;
+    if constexpr (DA) solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, want_grad ? REQ_GRAD : REQ_COST, traj, rec, clk, ct...);
+    else
     solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, want_grad ? REQ_GRAD : REQ_COST, traj, rec, clk);
 #else
+    if constexpr (DA) solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, want_grad ? REQ_GRAD : REQ_COST, traj, rec, ct...);
+    else
     solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, want_grad ? REQ_GRAD : REQ_COST, traj, rec);
 #endif
 }
@@ -407,14 +416,16 @@ template <int MODEL> struct SoloOcc { static constexpr int WPS = MODEL == KIN ? 
 // constraint row with its parameter row, and the state machine projects the multipliers with the row's bounds (RowCon).
 // It exists together with the box form alone (the host supplies a one-row box table of the handle's own values when the
 // caller bound none), and never with the lookahead, which is an unconstrained problem's.
+// BT = (BoxTab, DiscTab): the disc form (mpc_set_agent_discs), on the same terms -- the evaluations read the discs of the
+// agent's row; the state machine projects the multipliers with the handle's bounds [0, +inf), the same for every agent.
 template <int MODEL, int NE, int MC, bool LA = false, bool PA = false, class... BT>
 __global__ void __launch_bounds__(64 * SOLO_WAVES, SoloOcc<MODEL>::WPS)
 solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int *__restrict__ ctr,
             long long max_trips, BT... bt)
 {
-    constexpr bool BA = sizeof...(BT) != 0, CA = sizeof...(BT) == 2;
+    constexpr bool BA = sizeof...(BT) != 0, DA = has_tab<DiscTab, BT...>, CA = sizeof...(BT) == 2 && !DA;
     static_assert(!BA || PA, "the box form of the persistent kernel exists in the per-agent-parameter form alone");
-    static_assert(!CA || !LA, "the lookahead is an unconstrained problem's: it has no constraint form");
+    static_assert((!CA && !DA) || !LA, "the lookahead is an unconstrained problem's: it has no constraint or disc form");
     using BOX = BoxOf<BA, LaneBox>;
     using CON = ConOf<CA, RowCon>;
     extern __shared__ double s_solo[];
@@ -481,9 +492,13 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
             if ((req & (REQ_GRAD | REQ_COST)) == 0) break;              // uniform: the agent is done
 #if MPC_DEV_STAMP == 5
             t_adv += __builtin_amdgcn_s_memrealtime() - ta;
+            if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk, pack_disc(bt...));
+            else
             solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk);
             ntrip++;
 #else
+            if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, pack_disc(bt...));
+            else
             solo_eval<MODEL>(cm, w, a, lane, req, traj, rec);
 #endif
         }

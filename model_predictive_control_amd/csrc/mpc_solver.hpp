@@ -119,6 +119,35 @@ struct ConTab {
 };
 __device__ __forceinline__ void agent_con(DevCfg &c, const ConTab &t, int a) { agent_con(c, t.ctab, t.cidx, a); }
 __device__ __forceinline__ void agent_con_uniform(DevCfg &c, const ConTab &t, int a) { agent_con_uniform(c, t.ctab, t.cidx, a); }
+// The disc table of mpc_set_agent_discs, as the disc forms of the kernels receive it: the same trailing argument, in the
+// ConTab's place (a handle has constraint data or discs, never both).
+struct DiscTab {
+    const double *dtab;                            // [P][N][NDISC][3] caller's table
+    const int *didx;                               // [B]              caller's row index per agent
+};
+// the discs of stage k of agent a's row: a different agent in every lane (vector loads of the thread's own six doubles)
+__device__ __forceinline__ StageDiscs stage_discs(const DiscTab &t, int a, int k, int N)
+{
+    const double *__restrict__ r = t.dtab + ((size_t)t.didx[a] * N + k) * (3 * NDISC);
+    StageDiscs s;
+#pragma unroll
+    for (int i = 0; i < 3 * NDISC; i++) s.v[i] = r[i];
+    return s;
+}
+// ... one agent per wave: the row address is wave-uniform, lane k loads its stage
+__device__ __forceinline__ StageDiscs stage_discs_uniform(const DiscTab &t, int a, int k, int N)
+{
+    const int row = __builtin_amdgcn_readfirstlane(t.didx[a]);
+    const double *__restrict__ r = t.dtab + (size_t)row * N * (3 * NDISC) + (size_t)k * (3 * NDISC);
+    StageDiscs s;
+#pragma unroll
+    for (int i = 0; i < 3 * NDISC; i++) s.v[i] = r[i];
+    return s;
+}
+// which table a kernel's trailing pack holds
+template <class A, class B> struct SameTab { static constexpr bool v = false; };
+template <class A> struct SameTab<A, A> { static constexpr bool v = true; };
+template <class X, class... T> constexpr bool has_tab = (SameTab<X, T>::v || ... || false);
 template <bool PA> struct WsArgT { using type = Workspace; };
 template <> struct WsArgT<true> { using type = WorkspacePA; };
 template <bool PA> using WsArg = typename WsArgT<PA>::type;
@@ -415,6 +444,9 @@ __device__ __forceinline__ RowCon row_con_uniform(const ConTab &ct, int a)
 __device__ __forceinline__ const BoxTab &pack_box(const BoxTab &b) { return b; }
 __device__ __forceinline__ const BoxTab &pack_box(const BoxTab &b, const ConTab &) { return b; }
 __device__ __forceinline__ const ConTab &pack_con(const BoxTab &, const ConTab &c) { return c; }
+// ... or (BoxTab, DiscTab)
+__device__ __forceinline__ const BoxTab &pack_box(const BoxTab &b, const DiscTab &) { return b; }
+__device__ __forceinline__ const DiscTab &pack_disc(const BoxTab &, const DiscTab &d) { return d; }
 
 template <class BOX>
 __device__ __forceinline__ double prox_p(const DevCfg &c, const BOX &bx, int par, double x, double g, double gamma)

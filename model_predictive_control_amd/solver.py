@@ -48,11 +48,13 @@ class Track:
                 f"closed={self.closed}, R={self.R})")
 
 
-# the per-agent tables of an engine, by kind: doubles per row, the library's setter, whether the setter takes a plant index
-_AgentTable = collections.namedtuple("_AgentTable", "width setter plant")
-_AGENT_TABLES = {"params": _AgentTable(_lib.NPARAM, "mpc_set_agent_params", True),
-                 "bounds": _AgentTable(_lib.NBOUND, "mpc_set_agent_bounds", False),
-                 "constraints": _AgentTable(_lib.NCONSTR, "mpc_set_agent_constraints", False)}
+# the per-agent tables of an engine, by kind: doubles per row (and per stage of the engine's horizon on top), the
+# library's setter, whether the setter takes a plant index
+_AgentTable = collections.namedtuple("_AgentTable", "width width_per_N setter plant")
+_AGENT_TABLES = {"params": _AgentTable(_lib.NPARAM, 0, "mpc_set_agent_params", True),
+                 "bounds": _AgentTable(_lib.NBOUND, 0, "mpc_set_agent_bounds", False),
+                 "constraints": _AgentTable(_lib.NCONSTR, 0, "mpc_set_agent_constraints", False),
+                 "discs": _AgentTable(0, 3 * _lib.NDISC, "mpc_set_agent_discs", False)}
 
 
 class BatchedMPC:
@@ -163,9 +165,10 @@ class BatchedMPC:
         """set_agent_<kind>: the shape, dtype, device and range checks, the library's setter, and the tensors kept alive.
         indices: `index`, and `plant_index` (or None) for the kind that has one."""
         d = _AGENT_TABLES[kind]
+        width = d.width + d.width_per_N * self.N
         self._free()
-        if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] != d.width or table.shape[0] < 1:
-            raise ValueError(f"table: expected a tensor [P >= 1, {d.width}]")
+        if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] != width or table.shape[0] < 1:
+            raise ValueError(f"table: expected a tensor [P >= 1, {width}]")
         self._chk(table, table.shape, "table")
         index = indices[0]
         if not isinstance(index, torch.Tensor) or index.dim() != 1 or index.shape[0] < 1:
@@ -238,6 +241,43 @@ class BatchedMPC:
     @property
     def agent_constraints_bound(self):
         return "constraints" in self._keep
+
+    def set_agent_discs(self, table, index):
+        """Binds a per-agent table of keep-out discs (mpc_set_agent_discs; an engine of CONSTR_DISCS alone): table
+        [P, 3 * NDISC * N] float64 (rows [N][NDISC][3] = (cx, cy, r), as _lib.disc_rows makes them; r = 0: no obstacle),
+        index [B] int32 = the row of agent b.  An engine of CONSTR_DISCS needs it bound in every call that evaluates
+        constraints (eval_cost_grad, solve, solve_async, solve_active, the closed loops); they use agent b's row, stage k of
+        the horizon reading entry k, and serve batches of exactly B agents.  Independent of the parameter and bounds
+        tables (together they are for the same B).  The tensors stay the caller's: the library reads them at every call,
+        so rows may be rewritten in place between calls (moving obstacles in a host loop of solves); the engine keeps
+        them alive until clear_agent_discs()."""
+        self._bind_agent_table("discs", table, index)
+
+    def clear_agent_discs(self):
+        """Unbinds the disc table (an engine of CONSTR_DISCS then refuses to evaluate until one is bound again)."""
+        self._clear_agent_table("discs")
+
+    @property
+    def agent_discs_bound(self):
+        return "discs" in self._keep
+
+    def discs_from_plans(self, X, opp, radius, out=None):
+        """mpc_discs_from_plans: the disc table [B, 3 * NDISC * N] in which agent b's discs are the plans of its
+        opponents -- X [B, N, nx] as rollout() returns it for the agents' current plans, opp [B, NDISC] int32 (the
+        opponents of agent b; < 0 or >= B: none, a disc of radius 0), radius [B] (of agent b as an obstacle).  A gather
+        on the current stream; `out`: a table to write in place (one that is bound, say), else a new one.  Bound with
+        index = arange(B) it makes the next solve "everyone avoids everyone's last plan"."""
+        self._free()
+        if not isinstance(X, torch.Tensor) or X.dim() != 3:
+            raise ValueError(f"X: expected [B, {self.N}, {self.nx}]")
+        B = X.shape[0]
+        self._chk(X, (B, self.N, self.nx), "X")
+        self._chk(opp, (B, _lib.NDISC), "opp", torch.int32)
+        self._chk(radius, (B,), "radius")
+        width = 3 * _lib.NDISC * self.N
+        table = self._empty(B, width) if out is None else self._chk(out, (B, width), "out")
+        _lib.check(self.lib.mpc_discs_from_plans(self._h, B, _ptr(X), _ptr(opp), _ptr(radius), _ptr(table), self._stream()))
+        return table
 
     def invalidate_centerline_tables(self):
         """Forget the nearest-point search tables: the next call rebuilds them for the table it is given."""
