@@ -197,6 +197,45 @@ int mpc_set_agent_discs(mpc_handle *h, const double *table, int P, const int32_t
 int mpc_discs_from_plans(mpc_handle *h, int B, const double *X, const int32_t *opp, const double *radius, double *table,
                          void *stream);
 
+/* Traffic: who the opponents are, decided on the device, and the closed loop around it.
+ * Scenes are contiguous blocks of G agents: agent b belongs to scene b / G, 1 <= G <= MPC_SCENE_MAX and B % G == 0
+ * (unequal scenes are the caller's to pad); agents of different scenes never see each other.
+ * mpc_opponents_from_plans: X [B][Nst][nx] are positions per stage as mpc_rollout writes them (Nst = 1 with X = x:
+ * the states as they are now), radius [B] the radius of agent b as an obstacle; opp [B][MPC_NDISC] (int32, out) and
+ * clear [B][MPC_NDISC] (out, NULL ok).  All four are DEVICE memory; asynchronous on `stream`.  The rule, every operation
+ * rounded on its own (a host loop in IEEE doubles gets the same bits): for o != b of b's scene and stage k < Nst
+ *     dx = X[b][k][0] - X[o][k][0], dy = X[b][k][1] - X[o][k][1], g_k = (dx dx + dy dy) - r_o r_o,   c(b, o) = min_k g_k
+ * -- the disc expression above, operand for operand, so c is the smallest constraint value the next solve sees at the
+ * current plans.  A pair with a g_k that is not finite is no candidate (a diverged agent does not poison its scene);
+ * o is a candidate iff c(b, o) < reach reach (reach >= 0; +inf: all).  Selected are the MPC_NDISC candidates smallest
+ * in the lexicographic order (c, o): slot 0 holds the smallest, ties go to the smaller agent index; opp holds GLOBAL
+ * agent indices, an unused slot opp = -1 and clear = +inf.  No atomics: the same input gives the same output.  Works
+ * on a handle of any constr_mode (it reads nx alone); radius is device data and is not checked.  MPC_E_ARG, before any
+ * launch: G outside [1, MPC_SCENE_MAX], B % G != 0, Nst < 1, reach negative or NaN, NULL X, radius or opp, an
+ * asynchronous solve in flight, and, with tables bound, a B other than the bound one.
+ * mpc_closed_loop_traffic: T closed-loop steps in which every agent avoids the current plans of the nearest agents of
+ * its scene.  Blocking; the arguments it shares with mpc_closed_loop mean what they mean there (the plant's parameter
+ * rows and `shift` included).  Only on a handle of MPC_CONSTR_DISCS; `table` must be the disc table currently bound, with
+ * P == B rows (MPC_E_ARG otherwise) -- the loop rewrites it in place; its index being 0 .. B-1 is the caller's to ensure
+ * (the Python front end does).  Step t, every numbered launch being the one the public call of that name makes:
+ *   1. X = mpc_rollout(x, U), N stages, into a buffer of the handle
+ *   2. opp = the selection above on X (G, radius, reach); traj_opp [B][T][MPC_NDISC] records it (NULL ok)
+ *   3. table = mpc_discs_from_plans(X, opp, radius)
+ *   4. mpc_solve_batch; U and lambda are warm starts as the step before left them.  lambda is NOT re-slotted when an
+ *      agent's opponents change: a multiplier that belonged to another opponent is a warm start like any other, and the
+ *      augmented Lagrangian absorbs it
+ *   5. the plant step of mpc_closed_loop: u0, the plant's rows, shift, traj_x, traj_u, fail_count
+ *   6. traj_clear [B][T] (NULL ok) = slot 0 of `clear` of the selection on the NEW states (Nst = 1, reach = +inf): the
+ *      realised worst clearance of agent b at time t + 1, d^2 - r_o^2 to the nearest agent of its scene; +inf for G = 1
+ * Nothing but the solve's own polls returns to the host. */
+#define MPC_SCENE_MAX 64
+int mpc_opponents_from_plans(mpc_handle *h, int B, int G, int Nst, const double *X, const double *radius, double reach,
+                             int32_t *opp, double *clear, void *stream);
+int mpc_closed_loop_traffic(mpc_handle *h, int B, int T, int shift, int G, const double *radius, double reach,
+                            double *x, const double *cl, const int32_t *cl_index, double *U, double *lambda,
+                            double *table, double *traj_x, double *traj_u, int32_t *traj_opp, double *traj_clear,
+                            int32_t *fail_count, double *stats, void *stream);
+
 /* a-1 (car_dynamics.py:93-132 / dynamics.py:67-119,:144-173): dx[B][nx] = f(x[B][nx], u[B][2]) */
 int mpc_rhs(mpc_handle *h, int B, const double *x, const double *u, double *dx, void *stream);
 

@@ -32,7 +32,7 @@ LIB_PATH = os.environ.get("MPC_LIB_PATH", os.path.join(_HERE, "libmpc_hip.so")) 
 _SRC = [os.path.join(_HERE, "csrc", f) for f in ("mpc_api.hip", "mpc_handle.hpp", "mpc_launch.hpp", "mpc_rounds.hpp",
                                                   "mpc_aux.hpp", "mpc_eval.hpp", "mpc_solver.hpp", "mpc_device.hpp",
                                                   "mpc_game.hpp", "mpc_solo.hpp", "mpc_event.hpp", "mpc_step_body.hpp",
-                                                  "mpc_track.hpp")]
+                                                  "mpc_track.hpp", "mpc_traffic.hpp")]
 _HDR = os.path.join(os.path.dirname(_HERE), "include", "mpc_hip.h")
 
 MODEL_KINEMATIC, MODEL_PACEJKA = 0, 1
@@ -55,6 +55,7 @@ EXPORTS = [
     "mpc_default_bounds", "mpc_set_agent_bounds",
     "mpc_default_constraints", "mpc_set_agent_constraints",
     "mpc_default_discs", "mpc_set_agent_discs", "mpc_discs_from_plans",
+    "mpc_opponents_from_plans", "mpc_closed_loop_traffic",
     "mpc_track_init", "mpc_track_windows", "mpc_track_locate", "mpc_track_select", "mpc_closed_loop_track",
 ]
 NREC = 64
@@ -63,6 +64,7 @@ NPARAM = 31     # MPC_NPARAM: doubles per row of the per-agent parameter table
 NBOUND = 4      # MPC_NBOUND: doubles per row of the per-agent bounds table, [u_lb[0], u_lb[1], u_ub[0], u_ub[1]]
 NCONSTR = 19    # MPC_NCONSTR: doubles per row of the per-agent constraint table
 NDISC = 2       # MPC_NDISC: keep-out discs per stage; a row of the disc table is [N][NDISC][3] = (cx, cy, r)
+SCENE_MAX = 64  # MPC_SCENE_MAX: agents per scene at most (mpc_opponents_from_plans, mpc_closed_loop_traffic)
 # columns of a constraint row, by field name (include/mpc_hip.h: mpc_set_agent_constraints)
 CONSTR_FIELDS = {"g_off": (0, 6), "D_lb": (6, 6), "D_ub": (12, 6), "lane_halfwidth": (18, 1)}
 PARAM_FIELDS = {"veh": (0, 22), "accel": (22, 1), "friction": (23, 1), "v_ref": (24, 1), "cost_w": (25, 6)}
@@ -180,6 +182,8 @@ def load():
     L.mpc_default_discs.argtypes = [cp, C.POINTER(C.c_double)]
     L.mpc_set_agent_discs.argtypes = [vp, vp, ci, vp, ci]
     L.mpc_discs_from_plans.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    L.mpc_opponents_from_plans.argtypes = [vp, ci, ci, ci, vp, vp, C.c_double, vp, vp, vp]
+    L.mpc_closed_loop_traffic.argtypes = [vp, ci, ci, ci, ci, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mpc_step_lds_plan.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     L.mpc_math_probe.argtypes = [vp, ci, ci, vp, vp, vp, vp]
     L.mpc_lane_payoff.argtypes = [vp, ci, ci, C.POINTER(C.c_double), vp, vp, vp, vp, vp]

@@ -138,6 +138,7 @@ extern "C" int mpc_destroy(mpc_handle *h)
     if (h->stage) (void)hipFree(h->stage);
     if (h->ev.base) (void)hipFree(h->ev.base);
     if (h->ev.xhat) (void)hipFree(h->ev.xhat);
+    if (h->tr.base) (void)hipFree(h->tr.base);
     if (h->own_ptab) (void)hipFree(h->own_ptab);
     if (h->cl_gmeta) (void)hipFree(h->cl_gmeta);
     if (h->cl_gxy) (void)hipFree(h->cl_gxy);
@@ -834,6 +835,94 @@ extern "C" int mpc_closed_loop_track(mpc_handle *h, int B, int T, int shift, con
     if (!trk) return fail(MPC_E_ARG, "mpc_closed_loop_track: null track");
     return closed_loop_event_impl("mpc_closed_loop_track", h, B, T, shift, w, thr, max_hold, x, win, cl_index, U, lambda, held,
                                   disturbance, traj_x, traj_u, solved, solve_count, fail_count, stats, stream, trk, cl_index, traj_row);
+}
+
+// ---------------------------------------------------------------------------------- traffic (mpc_traffic.hpp)
+static_assert(MPC_SCENE_MAX == mpc::SCENE_MAX, "scene size: include/mpc_hip.h and mpc_traffic.hpp");
+// what mpc_opponents_from_plans and mpc_closed_loop_traffic ask of the scene arguments (checked without a device)
+static int check_scene_args(const std::string &who, int B, int G, double reach, const void *radius)
+{
+    if (G < 1 || G > MPC_SCENE_MAX) return fail(MPC_E_ARG, who + ": the scene size G must be in [1, " + std::to_string(MPC_SCENE_MAX) + "]");
+    if (B < 0) return fail(MPC_E_ARG, who + ": negative batch");
+    if (B % G) return fail(MPC_E_ARG, who + ": the batch of " + std::to_string(B) + " agents is not a whole number of scenes of G = " +
+                                       std::to_string(G) + " (B % G != 0: pad the scenes)");
+    if (!(reach >= 0.0)) return fail(MPC_E_ARG, who + ": reach must be >= 0 (+inf: every agent of the scene)");
+    if (!radius) return fail(MPC_E_ARG, who + ": null radius");
+    return MPC_OK;
+}
+// the selection on plans X [B][Nst][nx] (see opponents_kernel for the three outputs)
+static void launch_opponents(mpc_handle *h, hipStream_t s, int B, int G, int Nst, const double *X, const double *radius, double reach,
+                             int32_t *opp, int32_t *opp_rec, size_t rec_stride, double *clear, size_t clear_stride, int clear_slots)
+{
+    int Gp = 1;
+    while (Gp < G) Gp <<= 1;
+    const int spw = 64 / Gp, scenes = B / G;
+    hipLaunchKernelGGL(opponents_kernel, dim3((unsigned)((scenes + spw - 1) / spw)), dim3(TR_BLK), 0, s, B, G, Gp, spw, Nst, h->dc.nx, X,
+                       radius, reach * reach, opp, opp_rec, rec_stride, clear, clear_stride, clear_slots);
+}
+
+extern "C" int mpc_opponents_from_plans(mpc_handle *h, int B, int G, int Nst, const double *X, const double *radius, double reach,
+                                        int32_t *opp, double *clear, void *stream)
+{
+    const char *who = "mpc_opponents_from_plans";
+    int rc = check_scene_args(who, B, G, reach, radius); if (rc) return rc;
+    if (Nst < 1) return fail(MPC_E_ARG, std::string(who) + ": Nst must be >= 1 stages");
+    if (!X || !opp) return fail(MPC_E_ARG, std::string(who) + ": null X or opp");
+    rc = check_common(h, B, who); if (rc) return rc;
+    rc = check_tables(h, B, who, READS_ALL); if (rc) return rc;
+    if (B == 0) return MPC_OK;
+    launch_opponents(h, (hipStream_t)stream, B, G, Nst, X, radius, reach, opp, nullptr, 0, clear, MPC_NDISC, MPC_NDISC);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
+// Traffic closed loop: per step everybody's plans (mpc_rollout), the nearest opponents of every agent on them, their
+// discs into the bound table (mpc_discs_from_plans), the solve, the plant step of mpc_closed_loop, and the clearance
+// realised on the new states.  Every step is what the public call of that name launches; control returns to the host
+// inside the solve alone.
+extern "C" int mpc_closed_loop_traffic(mpc_handle *h, int B, int T, int shift, int G, const double *radius, double reach,
+                                       double *x, const double *cl, const int32_t *cl_index, double *U, double *lambda,
+                                       double *table, double *traj_x, double *traj_u, int32_t *traj_opp, double *traj_clear,
+                                       int32_t *fail_count, double *stats, void *stream)
+{
+    const std::string who = "mpc_closed_loop_traffic";
+    int rc = check_scene_args(who, B, G, reach, radius); if (rc) return rc;
+    if (T < 0) return fail(MPC_E_ARG, who + ": negative T");
+    rc = check_common(h, B, who.c_str()); if (rc) return rc;
+    if (h->cfg.constr_mode != MPC_CONSTR_DISCS) return fail(MPC_E_ARG, who + ": the handle's constr_mode is not MPC_CONSTR_DISCS");
+    const BoundTable &dt = h->tab[TAB_DISCS];
+    rc = check_tables(h, B, who.c_str(), READS_ALL, true); if (rc) return rc;
+    if (!table || table != dt.table)
+        return fail(MPC_E_ARG, who + ": table must be the disc table that is bound (mpc_set_agent_discs): the loop rewrites it in place");
+    if (dt.rows != B)
+        return fail(MPC_E_ARG, who + ": the bound disc table has " + std::to_string(dt.rows) + " rows, the loop needs one per agent (P == B = " +
+                               std::to_string(B) + ", index 0 .. B-1)");
+    if (B == 0 || T == 0) return MPC_OK;
+    if (!x || !cl || !U || !lambda) return fail(MPC_E_ARG, who + ": null buffer");
+    rc = reserve_traffic(h, B); if (rc) return rc;
+    const DevCfg &c = h->dc;
+    mpc_handle::TrafficBufs &tr = h->tr;
+    hipStream_t s = (hipStream_t)stream;
+    double *st = stats;
+    if (!st) {
+        rc = reserve_stage(h, sizeof(double) * 8 * (size_t)B); if (rc) return rc;
+        st = h->stage;
+    }
+    for (int t = 0; t < T; t++) {
+        rc = mpc_rollout(h, B, c.N, x, U, tr.X, stream); if (rc) return rc;
+        launch_opponents(h, s, B, G, c.N, tr.X, radius, reach, tr.opp, traj_opp ? traj_opp + (size_t)t * MPC_NDISC : nullptr,
+                         (size_t)T * MPC_NDISC, nullptr, 0, 0);
+        rc = mpc_discs_from_plans(h, B, tr.X, tr.opp, radius, table, stream); if (rc) return rc;
+        rc = mpc_solve_batch(h, B, x, cl, cl_index, U, lambda, st, stream); if (rc) return rc;
+        with_model_table(h, h->plant_rows(), [&](auto MODEL, auto PA, auto... pt) {
+            hipLaunchKernelGGL((plant_step_kernel<MODEL(), PA(), decltype(pt)...>), grid_for(B, 64), dim3(64), 0,
+                               s, c, B, t, T, shift, x, U, traj_x, traj_u, st, fail_count, pt...);
+        });
+        if (traj_clear)
+            launch_opponents(h, s, B, G, 1, x, radius, INFINITY, nullptr, nullptr, 0, traj_clear + t, (size_t)T, 1);
+    }
+    HIPCHK(hipGetLastError());
+    return bounded_sync(h, s, who.c_str());
 }
 
 extern "C" int mpc_last_speculation(mpc_handle *h, int64_t *issued, int64_t *used)

@@ -8,6 +8,7 @@
 #include "mpc_solo.hpp"
 #include "mpc_game.hpp"
 #include "mpc_event.hpp"
+#include "mpc_traffic.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -185,6 +186,14 @@ struct mpc_handle {
         double *xhat = nullptr;                        // [xhat_B][nx]
         int xhat_B = 0;
     } ev;
+    // mpc_closed_loop_traffic: everybody's plans X [cap][N][nx] of the step and the opponents chosen from them
+    // [cap][MPC_NDISC] (one allocation, grown like the workspace)
+    struct TrafficBufs {
+        char *base = nullptr;
+        int cap = 0;
+        double *X = nullptr;
+        int32_t *opp = nullptr;
+    } tr;
 };
 
 static int stage_m(const mpc_config *c)
@@ -426,6 +435,23 @@ static int reserve_event(mpc_handle *h, int B)
     int *ip = (int *)dp;
     auto takeI = [&](size_t cnt) { int *r = ip; ip += cnt; return r; };
     e.list = takeI(Bp); e.fire = takeI(Bp); e.cis = takeI(Bp); e.pis = takeI(Bp); e.bis = takeI(Bp); e.kis = takeI(Bp); e.dis = takeI(Bp); e.blk = takeI(nblk); e.count = takeI(64);
+    HIPCHK(hipMemset(base, 0, bytes));
+    return MPC_OK;
+}
+// buffers of the traffic loop for up to B agents (see mpc_handle::TrafficBufs)
+static int reserve_traffic(mpc_handle *h, int B)
+{
+    mpc_handle::TrafficBufs &t = h->tr;
+    if (B <= t.cap) return MPC_OK;
+    HIPCHK(hipSetDevice(h->device));
+    if (t.base) { HIPCHK(hipFree(t.base)); t.base = nullptr; t.cap = 0; }
+    const size_t Bp = ((size_t)B + 63) & ~(size_t)63;
+    const size_t nd = (size_t)h->dc.N * h->dc.nx;                // doubles per agent: X
+    const size_t bytes = nd * 8 * Bp + 4 * MPC_NDISC * Bp;
+    char *base = nullptr;
+    if (hipMalloc((void **)&base, bytes) != hipSuccess) return fail(MPC_E_ALLOC, "traffic-loop hipMalloc failed");
+    t.base = base; t.cap = (int)Bp;
+    t.X = (double *)base; t.opp = (int32_t *)(t.X + nd * Bp);
     HIPCHK(hipMemset(base, 0, bytes));
     return MPC_OK;
 }

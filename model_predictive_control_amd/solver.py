@@ -27,6 +27,13 @@ EventLoopResult = collections.namedtuple(
 TrackLoopResult = collections.namedtuple(
     "TrackLoopResult", EventLoopResult._fields + ("cl_index", "traj_row"))
 
+# what BatchedMPC.closed_loop_traffic returns: what closed_loop returns -- x, U, lam, traj_x [B, T, nx], traj_u [B, T, 2],
+# failures [B], stats [B, 8] of the last solve --, then traj_opp [B, T, NDISC] int32 (the opponents every agent avoided at
+# every step, -1: none), traj_clear [B, T] (the clearance d^2 - r^2 to the nearest agent of the scene after every step)
+# and the disc table [B, 3 NDISC N] as the last step left it (bound to the engine)
+TrafficLoopResult = collections.namedtuple(
+    "TrafficLoopResult", "x U lam traj_x traj_u failures stats traj_opp traj_clear table")
+
 
 class Track:
     """A table of track windows (BatchedMPC.track_windows): `win` [K * R, 2S], the window tensor -- an ordinary
@@ -279,6 +286,37 @@ class BatchedMPC:
         _lib.check(self.lib.mpc_discs_from_plans(self._h, B, _ptr(X), _ptr(opp), _ptr(radius), _ptr(table), self._stream()))
         return table
 
+    def _scene_args(self, B, G, radius, reach):
+        G, reach = int(G), float(reach)
+        if not 1 <= G <= _lib.SCENE_MAX:
+            raise ValueError(f"G: a scene holds 1 .. {_lib.SCENE_MAX} agents")
+        if B % G:
+            raise ValueError(f"the batch of {B} agents is not a whole number of scenes of {G} (pad the scenes)")
+        if not reach >= 0.0:
+            raise ValueError("reach must be >= 0 (inf: every agent of the scene)")
+        self._chk(radius, (B,), "radius")
+        return G, reach
+
+    def opponents_from_plans(self, X, G, radius, reach=float("inf")):
+        """mpc_opponents_from_plans: (opp [B, NDISC] int32, clear [B, NDISC]) -- for every agent the NDISC agents of its
+        scene (agents b // G == const) that come closest along everybody's plans X [B, Nst, nx] (rollout(); [B, nx]: the
+        states as they are now): c(b, o) = min_k (dx dx + dy dy) - radius[o]^2, candidates c < reach^2 with every stage
+        finite, the smallest in the order (c, o) first.  opp holds global agent indices, -1 for an unused slot (clear
+        +inf): what discs_from_plans takes.  On the current stream."""
+        self._free()
+        if isinstance(X, torch.Tensor) and X.dim() == 2:
+            X = X.unsqueeze(1)
+        if not isinstance(X, torch.Tensor) or X.dim() != 3 or X.shape[1] < 1:
+            raise ValueError(f"X: expected [B, Nst >= 1, {self.nx}]")
+        B, Nst = int(X.shape[0]), int(X.shape[1])
+        self._chk(X, (B, Nst, self.nx), "X")
+        G, reach = self._scene_args(B, G, radius, reach)
+        opp = torch.full((B, _lib.NDISC), -1, dtype=torch.int32, device=self.device)
+        clear = torch.full((B, _lib.NDISC), float("inf"), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.mpc_opponents_from_plans(self._h, B, G, Nst, _ptr(X), _ptr(radius), reach, _ptr(opp), _ptr(clear),
+                                                     self._stream()))
+        return opp, clear
+
     def invalidate_centerline_tables(self):
         """Forget the nearest-point search tables: the next call rebuilds them for the table it is given."""
         self._cl_key, self._cl_keep = None, None
@@ -436,6 +474,41 @@ class BatchedMPC:
                                             _ptr(cl_index), _ptr(U), _ptr(lam), _ptr(tx), _ptr(tu),
                                             _ptr(fails), _ptr(stats), self._stream()))
         return x, U, lam, tx, tu, fails, stats
+
+    def closed_loop_traffic(self, x, centerline, U, T, G, radius, reach=float("inf"), lam=None, cl_index=None, shift=False,
+                            table=None):
+        """mpc_closed_loop_traffic (an engine of CONSTR_DISCS): closed_loop in which, at every step, every agent avoids
+        the current plans of the NDISC nearest agents of its scene (opponents_from_plans on rollout(x, U), then
+        discs_from_plans into the bound table, then the solve and the plant step).  radius [B]: of agent b as an
+        obstacle.  table: the bound disc table [B, 3 NDISC N] (set_agent_discs with index = arange(B)), rewritten in
+        place; None: a table of zeros is made, bound with arange(B) and left bound.  Returns a TrafficLoopResult (x, U
+        and lam are copies; the table is the bound one)."""
+        B, T = x.shape[0], int(T)
+        self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
+        if T < 0:
+            raise ValueError("T must be >= 0")
+        G, reach = self._scene_args(B, G, radius, reach)
+        if int(self.cfg.constr_mode) != _lib.CONSTR_DISCS:     # before a table is made and bound for the caller
+            raise _lib.MpcError("libmpc_hip error -1: mpc_closed_loop_traffic: the handle's constr_mode is not MPC_CONSTR_DISCS")
+        width = 3 * _lib.NDISC * self.N
+        if table is None:
+            table = torch.zeros(B, width, dtype=torch.float64, device=self.device)
+            self.set_agent_discs(table, torch.arange(B, dtype=torch.int32, device=self.device))
+        else:
+            self._chk(table, (B, width), "table")
+        cl = self._centerline(centerline, cl_index, B)
+        x, U = x.clone(), U.clone()
+        lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None else lam.clone()
+        self._chk(lam, (B, self.m), "lam")
+        tx, tu = self._empty(B, T, self.nx), self._empty(B, T, 2)
+        topp = torch.full((B, T, _lib.NDISC), -1, dtype=torch.int32, device=self.device)
+        tclear = torch.full((B, T), float("inf"), dtype=torch.float64, device=self.device)
+        fails = torch.zeros(B, dtype=torch.int32, device=self.device)
+        stats = self._empty(B, _lib.NSTATS)
+        _lib.check(self.lib.mpc_closed_loop_traffic(
+            self._h, B, T, int(bool(shift)), G, _ptr(radius), reach, _ptr(x), _ptr(cl), _ptr(cl_index), _ptr(U), _ptr(lam),
+            _ptr(table), _ptr(tx), _ptr(tu), _ptr(topp), _ptr(tclear), _ptr(fails), _ptr(stats), self._stream()))
+        return TrafficLoopResult(x, U, lam, tx, tu, fails, stats, topp, tclear, table)
 
     # ------------------------------------------------------------------ masked solve, event-triggered loop
     def _weights(self, w):
