@@ -236,7 +236,38 @@ int mpc_closed_loop_traffic(mpc_handle *h, int B, int T, int shift, int G, const
                             double *table, double *traj_x, double *traj_u, int32_t *traj_opp, double *traj_clear,
                             int32_t *fail_count, double *stats, void *stream);
 
-/* a-1 (car_dynamics.py:93-132 / dynamics.py:67-119,:144-173): dx[B][nx] = f(x[B][nx], u[B][2]) */
+/* Input-rate cost: per-agent move penalties and the input applied last -- a fifth table of P rows in device memory and one
+ * row index per agent.  One row, MPC_NRATE doubles: [w_d, w_delta, d_prev, delta_prev].  With u_k = (d_k, delta_k) the
+ * decision variables of stage k (as they are, before the model clips them) and u_{-1} = (d_prev, delta_prev), stage k's
+ * cost -- behind the six terms of the reference and before the ALM terms -- gets the move penalty, and the stage's direct
+ * input gradient its derivative, every operation rounded on its own and in this order (i = 0 drive, 1 steering):
+ *     e_i = u_k[i] - u_{k-1}[i],   t_i = w_i e_i,   L_k = L_k + (t_0 e_0 + t_1 e_1)
+ *     dL/du_k[i] = dL/du_k[i] + 2 t_i;   and for k < N - 1:   f_i = u_{k+1}[i] - u_k[i],   dL/du_k[i] = dL/du_k[i] - 2 (w_i f_i)
+ * psi stays the sum of the stage costs in stage order.  The four evaluation routes (K1b, the fused K1b + K1c kernel, the
+ * wave evaluation, the persistent kernel) call one device function, so a request gets the same bits whichever serves
+ * it.  Zero weights change no bit of a solve.  The table is read by mpc_eval_cost_grad(_wave), mpc_solve_batch(_async),
+ * mpc_solve_active and the closed loops; mpc_stage_cost, mpc_rhs, mpc_rollout and mpc_prox_step do not read it (a single
+ * stage has no neighbour).  Handles of every constr_mode take it (MPC_CONSTR_DISCS: beside the disc table).
+ * mpc_default_rates (host only): a row of zeros.
+ * mpc_set_agent_rates: the semantics of the other tables.  table == NULL unbinds; bound, the calls above use row
+ * index[b] for agent b and return MPC_E_ARG for a batch size other than B; bound beside other tables it is for the same
+ * B.  table [P][MPC_NRATE] and index [B] are DEVICE memory of the caller, read at every call: rows may be rewritten in
+ * place between calls (a host loop writes the input it applies into columns 2 and 3).  The P rows are checked once, at
+ * bind time: all four values finite, both weights >= 0.  Refused (MPC_E_ARG) while an asynchronous solve is in flight,
+ * and while a constraint table is bound -- as mpc_set_agent_constraints is while a rate table is bound (the kernels have
+ * no form that takes both; a handle's own constraint data works).
+ * The closed loops carry u_{-1} themselves.  With a rate table bound, mpc_closed_loop, mpc_closed_loop_event,
+ * mpc_closed_loop_track and mpc_closed_loop_traffic need one row per agent (P == B, MPC_E_ARG otherwise; the index being
+ * 0 .. B-1 is the caller's to ensure, the Python front end does) and, behind the solve of a step and before the plant
+ * moves or the plan shifts, write the input about to be applied into columns 2 and 3 of row index[b]: U[b][0..1]
+ * (mpc_closed_loop, _traffic) or U[b][2 held .. 2 held + 1] (_event, _track; held = 0 for an agent that has just
+ * re-planned).  That is, bit for bit, the host loop of the public calls in which the caller writes those two columns
+ * between the solve and the rollout; the table holds the last applied inputs when the loop returns. */
+#define MPC_NRATE 4
+int mpc_default_rates(const mpc_config *cfg, double *row);
+int mpc_set_agent_rates(mpc_handle *h, const double *table, int P, const int32_t *index, int B);
+
+/* a-1(car_dynamics.py:93-132 / dynamics.py:67-119,:144-173): dx[B][nx] = f(x[B][nx], u[B][2]) */
 int mpc_rhs(mpc_handle *h, int B, const double *x, const double *u, double *dx, void *stream);
 
 /* a-2/a-3 (car_dynamics.py:134-147,:159-166 simulate/mapaccum): X[B][Nsim][nx] = x_1..x_Nsim;

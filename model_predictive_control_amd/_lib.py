@@ -55,6 +55,7 @@ EXPORTS = [
     "mpc_default_bounds", "mpc_set_agent_bounds",
     "mpc_default_constraints", "mpc_set_agent_constraints",
     "mpc_default_discs", "mpc_set_agent_discs", "mpc_discs_from_plans",
+    "mpc_default_rates", "mpc_set_agent_rates",
     "mpc_opponents_from_plans", "mpc_closed_loop_traffic",
     "mpc_track_init", "mpc_track_windows", "mpc_track_locate", "mpc_track_select", "mpc_closed_loop_track",
 ]
@@ -63,6 +64,7 @@ NPARAM = 31     # MPC_NPARAM: doubles per row of the per-agent parameter table
 # columns of a row, by field name (include/mpc_hip.h: mpc_set_agent_params)
 NBOUND = 4      # MPC_NBOUND: doubles per row of the per-agent bounds table, [u_lb[0], u_lb[1], u_ub[0], u_ub[1]]
 NCONSTR = 19    # MPC_NCONSTR: doubles per row of the per-agent constraint table
+NRATE = 4       # MPC_NRATE: doubles per row of the per-agent rate table, [w_d, w_delta, d_prev, delta_prev]
 NDISC = 2       # MPC_NDISC: keep-out discs per stage; a row of the disc table is [N][NDISC][3] = (cx, cy, r)
 SCENE_MAX = 64  # MPC_SCENE_MAX: agents per scene at most (mpc_opponents_from_plans, mpc_closed_loop_traffic)
 # columns of a constraint row, by field name (include/mpc_hip.h: mpc_set_agent_constraints)
@@ -182,6 +184,8 @@ def load():
     L.mpc_default_discs.argtypes = [cp, C.POINTER(C.c_double)]
     L.mpc_set_agent_discs.argtypes = [vp, vp, ci, vp, ci]
     L.mpc_discs_from_plans.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    L.mpc_default_rates.argtypes = [cp, C.POINTER(C.c_double)]
+    L.mpc_set_agent_rates.argtypes = [vp, vp, ci, vp, ci]
     L.mpc_opponents_from_plans.argtypes = [vp, ci, ci, ci, vp, vp, C.c_double, vp, vp, vp]
     L.mpc_closed_loop_traffic.argtypes = [vp, ci, ci, ci, ci, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mpc_step_lds_plan.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
@@ -345,6 +349,37 @@ def disc_rows(cfg, P, centres=None, radii=None):
         if r.shape not in ((), (N, NDISC), (P, N, NDISC)):
             raise ValueError(f"disc_rows: radii must be a scalar or have shape ({N}, {NDISC}) or ({P}, {N}, {NDISC}), got {r.shape}")
         v[..., 2] = r
+    return tab
+
+
+def default_rates(cfg):
+    """mpc_default_rates: the row of the rate table that says "no move penalty", float64 [NRATE] of zeros."""
+    return _default_row("mpc_default_rates", NRATE, cfg)
+
+
+def rate_rows(w_d, w_delta, u_prev=None):
+    """A rate table for BatchedMPC.set_agent_rates, on the host: float64 [P, NRATE], rows [w_d, w_delta, d_prev,
+    delta_prev].  w_d and w_delta: scalars or [P] (a scalar beside a [P] is every row's), finite and >= 0; u_prev: the
+    input applied last, [2] (every row) or [P, 2], finite; None: zeros.  P is the longest of the three (1 when all are
+    scalars / [2]).  Pure host code: usable without a GPU."""
+    import numpy as np
+    wd, wl = np.asarray(w_d, dtype=np.float64), np.asarray(w_delta, dtype=np.float64)
+    up = np.zeros(2) if u_prev is None else np.asarray(u_prev, dtype=np.float64)
+    if wd.ndim > 1 or wl.ndim > 1:
+        raise ValueError(f"rate_rows: w_d and w_delta must be scalars or have shape (P,), got {wd.shape} and {wl.shape}")
+    if up.ndim not in (1, 2) or up.shape[-1] != 2:
+        raise ValueError(f"rate_rows: u_prev must have shape (2,) or (P, 2), got {up.shape}")
+    sizes = {int(a.shape[0]) for a, nd in ((wd, 1), (wl, 1), (up, 2)) if a.ndim == nd}
+    if len(sizes) > 1 or 0 in sizes:
+        raise ValueError(f"rate_rows: w_d, w_delta and u_prev disagree about the number of rows P >= 1: {sorted(sizes)}")
+    P = sizes.pop() if sizes else 1
+    for name, a in (("w_d", wd), ("w_delta", wl)):
+        if not np.all(np.isfinite(a)) or np.any(a < 0.0):
+            raise ValueError(f"rate_rows: {name} must be finite and >= 0")
+    if not np.all(np.isfinite(up)):
+        raise ValueError("rate_rows: u_prev must be finite")
+    tab = np.empty((P, NRATE), dtype=np.float64)
+    tab[:, 0], tab[:, 1], tab[:, 2:] = wd, wl, up
     return tab
 
 

@@ -106,7 +106,8 @@ class MPCController:
 
     # ------------------------------------------------------------------ batched entry points
     def solve(self, Y0, centerline, U0=None, lam0=None, cl_index=None, params=None, param_index=None,
-              bounds=None, bound_index=None, constraints=None, constraint_index=None, discs=None, disc_index=None):
+              bounds=None, bound_index=None, constraints=None, constraint_index=None, discs=None, disc_index=None,
+              rates=None, rate_index=None):
         """Batched solve: Y0 [B, nx], centerline [2S] or [C, 2S] (+ cl_index[B]) -> (U [B, 2N], stats).
         params [P, 31] (rows as _lib.param_rows makes them) + param_index [B] (None: agent b uses row b % P): this
         solve runs agent b on its own vehicle and cost parameters (BatchedMPC.set_agent_params).
@@ -116,7 +117,10 @@ class MPCController:
         b % P"): this solve holds agent b to its own constraint data (BatchedMPC.set_agent_constraints).
         discs [P°, 6N] (rows as _lib.disc_rows makes them) + disc_index [B] (None: agent b uses row b % P°): this solve
         keeps agent b out of the discs of its own row, stage by stage (BatchedMPC.set_agent_discs; a controller whose
-        problem has keep_out_discs set needs them in every solve)."""
+        problem has keep_out_discs set needs them in every solve).
+        rates [P*, 4] (rows as _lib.rate_rows makes them) + rate_index [B] (None: agent b uses row b % P*): this solve
+        penalises agent b's input moves with the weights, and from the last applied input, of its own row
+        (BatchedMPC.set_agent_rates; not together with constraints=)."""
         dev = self.device
         Y0 = torch.as_tensor(Y0, dtype=torch.float64, device=dev).contiguous()
         B = Y0.shape[0]
@@ -133,7 +137,8 @@ class MPCController:
         for kind, table, index, name in (("params", params, param_index, "param_index"),
                                          ("bounds", bounds, bound_index, "bound_index"),
                                          ("constraints", constraints, constraint_index, "constraint_index"),
-                                         ("discs", discs, disc_index, "disc_index")):
+                                         ("discs", discs, disc_index, "disc_index"),
+                                         ("rates", rates, rate_index, "rate_index")):
             if table is None:
                 if index is not None:
                     raise ValueError(f"{name} needs {kind}")
@@ -155,10 +160,11 @@ class MPCController:
         return U, stats
 
     def step(self, Y0, centerline, U0=None, lam0=None, cl_index=None, params=None, param_index=None,
-             bounds=None, bound_index=None, constraints=None, constraint_index=None, discs=None, disc_index=None):
+             bounds=None, bound_index=None, constraints=None, constraint_index=None, discs=None, disc_index=None,
+             rates=None, rate_index=None):
         """First control of every agent, u0 [B, 2] (main.py:141 input_to_matrix(U)[:, 0])."""
         U, _ = self.solve(Y0, centerline, U0, lam0, cl_index, params, param_index, bounds, bound_index,
-                          constraints, constraint_index, discs, disc_index)
+                          constraints, constraint_index, discs, disc_index, rates, rate_index)
         return U[:, :2].contiguous()
 
 

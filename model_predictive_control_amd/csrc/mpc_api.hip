@@ -89,6 +89,14 @@ extern "C" int mpc_default_discs(const mpc_config *c, double *row)
     return MPC_OK;
 }
 
+static_assert(MPC_NRATE == mpc::NRATE, "row layout: include/mpc_hip.h and mpc_device.hpp");
+extern "C" int mpc_default_rates(const mpc_config *c, double *row)
+{
+    if (!c || !row) return fail(MPC_E_ARG, "mpc_default_rates: null argument");
+    for (int i = 0; i < MPC_NRATE; i++) row[i] = 0.0;   // no move penalty, u_{-1} = 0
+    return MPC_OK;
+}
+
 extern "C" int mpc_create(const mpc_config *cfg, int device, mpc_handle **out)
 {
     if (!cfg || !out) return fail(MPC_E_ARG, "mpc_create: null argument");
@@ -241,6 +249,15 @@ static int disc_row_rule(const mpc_handle *h, const double *r, const std::string
     return MPC_OK;
 }
 
+// move penalties: everything finite, no negative weight
+static int rate_row_rule(const mpc_handle *, const double *r, const std::string &where)
+{
+    for (int i = 0; i < MPC_NRATE; i++)
+        if (!std::isfinite(r[i])) return fail(MPC_E_ARG, where + ": (w_d, w_delta, d_prev, delta_prev) must be finite");
+    if (!(r[0] >= 0.0) || !(r[1] >= 0.0)) return fail(MPC_E_ARG, where + ": the weights must not be negative");
+    return MPC_OK;
+}
+
 // Binds (table != NULL) or unbinds the per-agent table of one kind.  The rows are checked once, here, through a
 // synchronous copy (binding is not on the hot path; rows rewritten in place later are the caller's to keep valid).
 // Nothing else is done: the kernels read the caller's memory at every call.  The box and constraint forms of some
@@ -259,6 +276,11 @@ static int bind_agent_table(mpc_handle *h, TableKind kind, const double *table, 
                                                   "there is no constraint data to bind (mpc_set_agent_discs)");
     if (kind == TAB_DISCS && h->cfg.constr_mode != MPC_CONSTR_DISCS)
         return fail(MPC_E_ARG, std::string(who) + ": the handle's constr_mode is not MPC_CONSTR_DISCS");
+    // a rate table and a constraint table together would need kernel forms that take both: whichever comes second is refused
+    if ((kind == TAB_RATES && h->tab[TAB_CONSTR].table) || (kind == TAB_CONSTR && h->tab[TAB_RATES].table))
+        return fail(MPC_E_ARG, std::string(who) + ": a " + k_tables[kind == TAB_RATES ? TAB_CONSTR : TAB_RATES].noun + " table is bound (" +
+                               k_tables[kind == TAB_RATES ? TAB_CONSTR : TAB_RATES].setter + "): a rate table and a constraint table "
+                               "cannot be bound together");
     if (P < 1 || B < 1 || !index) return fail(MPC_E_ARG, std::string(who) + ": need P >= 1 rows, B >= 1 agents and an index");
     { const int ra = check_tables_agree(h, B, who, kind); if (ra) return ra; }
     HIPCHK(hipSetDevice(h->device));
@@ -292,6 +314,28 @@ extern "C" int mpc_set_agent_constraints(mpc_handle *h, const double *table, int
 extern "C" int mpc_set_agent_discs(mpc_handle *h, const double *table, int P, const int32_t *index, int B)
 {
     return bind_agent_table(h, TAB_DISCS, table, P, index, B, disc_row_rule);
+}
+
+extern "C" int mpc_set_agent_rates(mpc_handle *h, const double *table, int P, const int32_t *index, int B)
+{
+    return bind_agent_table(h, TAB_RATES, table, P, index, B, rate_row_rule);
+}
+// The closed loops carry u_{-1} themselves: with a rate table bound they need a row per agent (P == B; index 0 .. B-1 is
+// the caller's to ensure, as with the traffic loop's disc table) ...
+static int check_rate_rows(const mpc_handle *h, int B, const std::string &who)
+{
+    const BoundTable &rt = h->tab[TAB_RATES];
+    if (rt.table && rt.rows != B)
+        return fail(MPC_E_ARG, who + ": the bound rate table has " + std::to_string(rt.rows) + " rows, the loop writes the applied input into "
+                               "one per agent (P == B = " + std::to_string(B) + ", index 0 .. B-1)");
+    return MPC_OK;
+}
+// ... and write the input about to be applied into it, behind the solve and before the plant moves (rate_prev_kernel)
+static void launch_rate_prev(mpc_handle *h, hipStream_t s, int B, const double *U, const int32_t *held, const int32_t *fire)
+{
+    const BoundTable &rt = h->tab[TAB_RATES];
+    if (rt.table)
+        hipLaunchKernelGGL(rate_prev_kernel, grid_for(B, 64), dim3(64), 0, s, B, h->cfg.N, U, held, fire, const_cast<double *>(rt.table), rt.idx);
 }
 
 // The discs of everybody's opponents from everybody's plans: a pure gather (discs_from_plans_kernel), asynchronous
@@ -400,7 +444,7 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     if (!x0 || !cl || !U || !psi) return fail(MPC_E_ARG, "mpc_eval_cost_grad: null buffer");
     const DevCfg &c = h->dc;
     if (c.m && (!y || !Sigma)) return fail(MPC_E_ARG, "mpc_eval_cost_grad: y and Sigma are required when m > 0");
-    rc = check_tables(h, B, "mpc_eval_cost_grad", READS_PARAMS | READS_CONSTR | READS_DISCS, true); if (rc) return rc;
+    rc = check_tables(h, B, "mpc_eval_cost_grad", READS_PARAMS | READS_CONSTR | READS_DISCS | READS_RATES, true); if (rc) return rc;
     rc = reserve(h, B); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     // direct mode: the kernel reads and writes the caller's agent-major buffers in place
@@ -413,6 +457,7 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     w.ptab = h->params().table; w.pidx = h->params().idx;
     w.ctab = h->tab[TAB_CONSTR].table; w.cidx = h->tab[TAB_CONSTR].idx;
     w.dtab = h->tab[TAB_DISCS].table; w.didx = h->tab[TAB_DISCS].idx;
+    w.rtab = h->tab[TAB_RATES].table; w.ridx = h->tab[TAB_RATES].idx;
     if (wave_path) launch_solo_eval(h, w, s, grad ? 1 : 0);
     else launch_eval(h, w, s, nullptr, nullptr, grad ? B : 0, grad ? 0 : B);
     HIPCHK(hipGetLastError());
@@ -488,6 +533,7 @@ static int solve_core(mpc_handle *h, int B, const double *x0, const double *cl, 
     w.btab = h->tab[TAB_BOX].table; w.bidx = rows_of(TAB_BOX);
     w.ctab = h->tab[TAB_CONSTR].table; w.cidx = rows_of(TAB_CONSTR);
     w.dtab = h->tab[TAB_DISCS].table; w.didx = rows_of(TAB_DISCS);
+    w.rtab = h->tab[TAB_RATES].table; w.ridx = rows_of(TAB_RATES);
     w.xe = w.ws_xe; w.ge = w.ws_ge; w.yhe = w.ws_yhe; w.Sig = w.ws_Sig;
     rc = run_solver(h, s); if (rc) return rc;
     if (stats) hipLaunchKernelGGL(stats_kernel, grid_for(B, 256), dim3(256), 0, s, w, stats);
@@ -569,6 +615,7 @@ extern "C" int mpc_closed_loop(mpc_handle *h, int B, int T, int shift, double *x
     const DevCfg &c = h->dc;
     if (c.m && !lambda) return fail(MPC_E_ARG, "mpc_closed_loop: lambda is required when m > 0");
     rc = check_tables(h, B, "mpc_closed_loop", READS_ALL, true); if (rc) return rc;
+    rc = check_rate_rows(h, B, "mpc_closed_loop"); if (rc) return rc;
     // bound table: the controller solves with row pidx[b], the plant advances with row pidx_plant[b] (null: the same)
     hipStream_t s = (hipStream_t)stream;
     double *st = stats;
@@ -578,6 +625,7 @@ extern "C" int mpc_closed_loop(mpc_handle *h, int B, int T, int shift, double *x
     }
     for (int t = 0; t < T; t++) {
         rc = mpc_solve_batch(h, B, x, cl, cl_index, U, lambda, st, stream); if (rc) return rc;
+        launch_rate_prev(h, s, B, U, nullptr, nullptr);
         with_model_table(h, h->plant_rows(), [&](auto MODEL, auto PA, auto... pt) {
             hipLaunchKernelGGL((plant_step_kernel<MODEL(), PA(), decltype(pt)...>), grid_for(B, 64), dim3(64), 0,
                                s, c, B, t, T, shift, x, U, traj_x, traj_u, st, fail_count, pt...);
@@ -608,7 +656,7 @@ static int solve_active_impl(mpc_handle *h, int B, const int32_t *active, const 
     r.cl_index = cl_index; r.pidx = h->params().idx;
     r.xs = e.xs; r.Us = e.Us; r.lams = e.lams; r.stats_s = e.stats_s; r.cis = e.cis; r.pis = e.pis;
     hipLaunchKernelGGL(active_gather_kernel, grows, dim3(EV_BLK), 0, s, r);
-    const AgentIdx gathered = {{e.pis, e.bis, e.kis, e.dis}};   // (the parameter rows ride in the gather above)
+    const AgentIdx gathered = {{e.pis, e.bis, e.kis, e.dis, e.ris}};   // (the parameter rows ride in the gather above)
     for (int k = TAB_BOX; k < TAB_KINDS; k++)
         if (h->tab[k].table)
             hipLaunchKernelGGL(active_index_kernel, gblk, dim3(EV_BLK), 0, s, e.list, e.count, h->tab[k].idx, const_cast<int32_t *>(gathered.of[k]));
@@ -787,6 +835,7 @@ static int closed_loop_event_impl(const char *who_, mpc_handle *h, int B, int T,
     const DevCfg &c = h->dc;
     if (c.m && !lambda) return fail(MPC_E_ARG, who + ": lambda is required when m > 0");
     rc = check_tables(h, B, who_, READS_ALL, true); if (rc) return rc;
+    rc = check_rate_rows(h, B, who); if (rc) return rc;
     rc = reserve_event(h, B); if (rc) return rc;
     bool fresh = false;
     rc = reserve_xhat(h, B, &fresh); if (rc) return rc;
@@ -801,6 +850,7 @@ static int closed_loop_event_impl(const char *who_, mpc_handle *h, int B, int T,
             hipLaunchKernelGGL(track_select_kernel, grid_for(B, 64), dim3(64), 0, s, c, track_geom(trk), B, c.nx, x, cl, e.fire,
                                near_for(h, cl), cl_index_rw, (int *)nullptr, traj_row, t, T);
         rc = solve_active_impl(h, B, e.fire, x, cl, cl_index, U, lambda, st, nullptr, s, false); if (rc) return rc;
+        launch_rate_prev(h, s, B, U, held, e.fire);
         // bound table: the plant advances with row pidx_plant[b] (null: the controller's), the nominal state with pidx[b]
         with_model_table(h, h->plant_rows(), [&](auto MODEL, auto PA, auto... pt) {
             if constexpr (PA())
@@ -897,6 +947,7 @@ extern "C" int mpc_closed_loop_traffic(mpc_handle *h, int B, int T, int shift, i
     if (dt.rows != B)
         return fail(MPC_E_ARG, who + ": the bound disc table has " + std::to_string(dt.rows) + " rows, the loop needs one per agent (P == B = " +
                                std::to_string(B) + ", index 0 .. B-1)");
+    rc = check_rate_rows(h, B, who); if (rc) return rc;
     if (B == 0 || T == 0) return MPC_OK;
     if (!x || !cl || !U || !lambda) return fail(MPC_E_ARG, who + ": null buffer");
     rc = reserve_traffic(h, B); if (rc) return rc;
@@ -914,6 +965,7 @@ extern "C" int mpc_closed_loop_traffic(mpc_handle *h, int B, int T, int shift, i
                          (size_t)T * MPC_NDISC, nullptr, 0, 0);
         rc = mpc_discs_from_plans(h, B, tr.X, tr.opp, radius, table, stream); if (rc) return rc;
         rc = mpc_solve_batch(h, B, x, cl, cl_index, U, lambda, st, stream); if (rc) return rc;
+        launch_rate_prev(h, s, B, U, nullptr, nullptr);
         with_model_table(h, h->plant_rows(), [&](auto MODEL, auto PA, auto... pt) {
             hipLaunchKernelGGL((plant_step_kernel<MODEL(), PA(), decltype(pt)...>), grid_for(B, 64), dim3(64), 0,
                                s, c, B, t, T, shift, x, U, traj_x, traj_u, st, fail_count, pt...);

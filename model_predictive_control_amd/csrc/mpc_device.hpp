@@ -133,6 +133,39 @@ MPC_DEV void agent_con_uniform(DevCfg &c, const double *__restrict__ tab, const 
 constexpr int NDISC = 2;
 struct StageDiscs { double v[3 * NDISC]; };
 
+// mpc_set_agent_rates: a table [P][NRATE] of move penalties in device memory and one row index per agent.  A row is
+// [w_d, w_delta, d_prev, delta_prev]: the weights on the change of the two inputs from one stage to the next, and u_{-1},
+// the input applied last.  Stage k's cost gets w_d e_k[0]^2 + w_delta e_k[1]^2 with e_k = u_k - u_{k-1} -- the one term
+// that couples neighbouring stages -- on the decision variables as stage_record receives them.  Like the discs the row
+// never enters a DevCfg: the rate forms of the kernels that evaluate the cost (trailing RateTab argument:
+// mpc_solver.hpp) collect the stage's neighbours where the stage is evaluated and hand them to stage_record
+// (mpc_eval.hpp), which adds rate_term to the stage cost.
+constexpr int NRATE = 4;
+struct StageRate {
+    double w[2];       // w_d, w_delta
+    double prev[2];    // u_{k-1} (stage 0: u_{-1} of the agent's row)
+    double next[2];    // u_{k+1} (not read at the last stage)
+    bool last;         // k == N - 1: no successor
+};
+// The move penalty of one stage and its direct input gradient, every operation rounded on its own (one function for the
+// four evaluation routes: the same request gets the same bits whichever serves it):
+//     e_i = u_i - prev_i,  t_i = w_i e_i,  term = t_0 e_0 + t_1 e_1                              (returned)
+//     ub_i = ub_i + 2 t_i,  and unless the stage is the last:  f_i = next_i - u_i,  ub_i = ub_i - 2 (w_i f_i)
+MPC_DEV double rate_term(const StageRate &r, double d, double dl, bool is_g, double (&ub)[2])
+{
+#pragma clang fp contract(off)
+    const double e0 = d - r.prev[0], e1 = dl - r.prev[1];
+    const double t0 = r.w[0] * e0, t1 = r.w[1] * e1;
+    if (is_g) {
+        ub[0] = ub[0] + 2.0 * t0; ub[1] = ub[1] + 2.0 * t1;
+        if (!r.last) {
+            const double f0 = r.next[0] - d, f1 = r.next[1] - dl;
+            ub[0] = ub[0] - 2.0 * (r.w[0] * f0); ub[1] = ub[1] - 2.0 * (r.w[1] * f1);
+        }
+    }
+    return t0 * e0 + t1 * e1;
+}
+
 // ---------------------------------------------------------------------------------- math
 // The OCML double-precision transcendentals are full-range (Payne-Hanek reduction, dozens of
 // 64-bit literals each) and dominate this kernel's instruction count.  The angles of this problem

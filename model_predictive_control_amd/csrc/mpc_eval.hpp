@@ -484,7 +484,9 @@ __device__ __forceinline__ void stage_geom(const DevCfg &c, const Workspace &w, 
 // (records in LDS).  The cost arithmetic is written with fixed roundings (no contraction, explicit
 // fma): the same request must give the same bits whichever kernel this is inlined into.
 // DS: empty, or the stage's keep-out discs (one trailing StageDiscs: the disc forms of the kernels, constr_mode 3) -- the
-// constraints of the stage are then the NDISC discs and nothing else; the ALM terms are formed exactly as below.
+// constraints of the stage are then the NDISC discs and nothing else; the ALM terms are formed exactly as below --
+// and / or the stage's move penalty (one trailing StageRate, last: the rate forms): rate_term is added to the stage cost
+// and to its direct input gradient right behind stage_cost, before the ALM terms, so psi stays the stage-order sum.
 template <int MODEL, class Put, class... DS>
 __device__ __forceinline__ void stage_record(const DevCfg &c, const Workspace &w, int a, bool ch2, bool is_g,
                                              int k, const double (&xs)[ModelDim<MODEL>::NX],
@@ -492,15 +494,20 @@ __device__ __forceinline__ void stage_record(const DevCfg &c, const Workspace &w
                                              const Geom &g, Put put, const DS &...ds)
 {
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE;
-    static_assert(sizeof...(DS) <= 1, "at most the stage's discs");
+    constexpr bool DD = has_tab<StageDiscs, DS...>, RR = has_tab<StageRate, DS...>;
+    static_assert(sizeof...(DS) == (DD ? 1 : 0) + (RR ? 1 : 0), "at most the stage's discs and its move penalty");
     double xb[NX], ub[2] = {0.0, 0.0};
 #pragma unroll
     for (int i = 0; i < NX; i++) xb[i] = 0.0;
     double L = is_g ? stage_cost<MODEL, true>(c, g, xe, d, dl, xb, ub)
                     : stage_cost<MODEL, false>(c, g, xe, d, dl, xb, ub);
-    if constexpr (sizeof...(DS) != 0) {
+    if constexpr (RR) {
 #pragma clang fp contract(off)
-        const StageDiscs dz[1] = {ds...};
+        L = L + rate_term(pack_get<StageRate>(ds...), d, dl, is_g, ub);
+    }
+    if constexpr (DD) {
+#pragma clang fp contract(off)
+        const StageDiscs dz[1] = {pack_get<StageDiscs>(ds...)};
         const size_t am = (size_t)a * c.m;
 #pragma unroll
         for (int j = 0; j < NDISC; j++) {
@@ -703,6 +710,9 @@ __device__ __forceinline__ void adjoint_rec_quad_kin(const DevCfg &c, bool is_g,
 // parameter table of the caller's the host binds a one-row table of the handle's own values (mpc_launch.hpp).
 // ... or the disc table (one trailing DiscTab argument: mpc_set_agent_discs, constr_mode 3), on the same terms: the
 // thread loads the six doubles of its own (agent, stage) and stage_record evaluates the discs in the constraints' place.
+// ... or the rate table (a trailing RateTab, alone or behind the DiscTab: mpc_set_agent_rates), on the same terms: the
+// thread loads the weights of its agent's row and its stage's two neighbours -- u_{k-1} and u_{k+1} from useq at its own
+// slot (u_{-1} from the row at stage 0, nothing past stage N - 1) -- and stage_record adds the move penalty.
 template <int MODEL, bool SHARED_CL, bool PA = false, class... CT>
 __global__ void __launch_bounds__(64, (MODEL == KIN ? MPC_K1B_WAVES : MPC_K1B_WAVES_PAC))
 stage_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, int nG_imm, int nC_imm,
@@ -710,6 +720,7 @@ stage_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, 
 {
     static_assert(sizeof...(CT) == 0 || PA, "the constraint form exists in the per-agent-parameter form alone");
     constexpr bool DA = has_tab<DiscTab, CT...>;   // the disc form: CT = DiscTab
+    constexpr bool RA = has_tab<RateTab, CT...>;   // the rate form: CT = RateTab or DiscTab, RateTab
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE;
 #if MPC_DEV_STAMP == 6
     DevStamp stamp(blockIdx.x);
@@ -746,7 +757,7 @@ stage_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, 
     const auto put = [=](int f, double v) { *(f == JS ? sl : jr + (size_t)f * St) = v; };
     DevCfg cm_;
     if constexpr (PA) { cm_ = c; agent_cfg(cm_, w.ptab, w.pidx, a); }
-    if constexpr (sizeof...(CT) != 0 && !DA) agent_con(cm_, ct..., a);
+    if constexpr (has_tab<ConTab, CT...>) agent_con(cm_, ct..., a);
     const DevCfg &cm = PA ? cm_ : c;
     if (is_g) stage_sens_record<MODEL>(cm, xs, xe, d, dl, put);
     Geom g;
@@ -756,7 +767,12 @@ stage_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, 
     } else {
         stage_geom(c, w, clp, SHARED_CL ? 0 : w.cl_index[a], xe[0], xe[1], g);
     }
-    if constexpr (DA) stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(ct..., a, k, c.N));
+    if constexpr (DA && RA)
+        stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(pack_get<DiscTab>(ct...), a, k, c.N),
+                            stage_rate(pack_get<RateTab>(ct...), a, k, c.N, w.useq + uslot, St));
+    else if constexpr (RA)
+        stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_rate(pack_get<RateTab>(ct...), a, k, c.N, w.useq + uslot, St));
+    else if constexpr (DA) stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(ct..., a, k, c.N));
     else
     stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put);
 }
@@ -806,6 +822,7 @@ stage_adjoint_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ 
 {
     static_assert(sizeof...(CT) == 0 || PA, "the constraint form exists in the per-agent-parameter form alone");
     constexpr bool DA = has_tab<DiscTab, CT...>;   // the disc form: CT = DiscTab
+    constexpr bool RA = has_tab<RateTab, CT...>;   // the rate form: CT = RateTab or DiscTab, RateTab
     static_assert(MODEL == KIN, "the fused K1b + K1c kernel is the kinematic model's");
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE, BLK = FUSED_BLK;
     extern __shared__ double s_rec[];                    // [JS + 1][N][SPB]; row JS = stage cost
@@ -839,12 +856,17 @@ stage_adjoint_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ 
             const auto put = [=](int f, double v) { r[(size_t)f * NS] = v; };
             DevCfg cm_;
             if constexpr (PA) { cm_ = c; agent_cfg(cm_, w.ptab, w.pidx, a); }
-            if constexpr (sizeof...(CT) != 0 && !DA) agent_con(cm_, ct..., a);
+            if constexpr (has_tab<ConTab, CT...>) agent_con(cm_, ct..., a);
             const DevCfg &cm = PA ? cm_ : c;
             if (is_g) stage_sens_record<MODEL>(cm, xs, xe, d, dl, put);
             Geom g;
             stage_geom(c, w, clp, SHARED_CL ? 0 : w.cl_index[a], xe[0], xe[1], g);
-            if constexpr (DA) stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(ct..., a, k, N));
+            if constexpr (DA && RA)
+                stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(pack_get<DiscTab>(ct...), a, k, N),
+                                    stage_rate(pack_get<RateTab>(ct...), a, k, N, w.useq + uslot, St));
+            else if constexpr (RA)
+                stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_rate(pack_get<RateTab>(ct...), a, k, N, w.useq + uslot, St));
+            else if constexpr (DA) stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(ct..., a, k, N));
             else
             stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put);
         }

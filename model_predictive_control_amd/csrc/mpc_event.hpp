@@ -209,6 +209,23 @@ __global__ void __launch_bounds__(64) event_step_kernel(const DevCfg c_, int B, 
     }
 }
 
+// mpc_set_agent_rates in the closed loops: the input about to be applied goes into columns 2 and 3 of the agent's row of the
+// bound rate table -- u_{-1} of its next solve.  That is stage hd of the plan: hd = 0 in mpc_closed_loop(_traffic) (held
+// and fire null); in the event loops the stage event_step_kernel is about to apply (0 for an agent that fired, held[a]
+// otherwise, clamped as there).  Launched between the solve and the kernel that advances the plant (and may shift the
+// plan).  Every word written is a copy of a word of U.  Rows are the agents' own: the loops require P == B.
+__global__ void __launch_bounds__(64) rate_prev_kernel(int B, int N, const double *__restrict__ U, const int *__restrict__ held,
+                                                       const int *__restrict__ fire, double *__restrict__ rtab,
+                                                       const int *__restrict__ ridx)
+{
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= B) return;
+    int hd = held && !(fire && fire[a] != 0) ? held[a] : 0;
+    hd = max(0, min(hd, N - 1));
+    double *r = rtab + (size_t)ridx[a] * NRATE;
+    r[2] = U[(size_t)a * 2 * N + 2 * hd]; r[3] = U[(size_t)a * 2 * N + 2 * hd + 1];
+}
+
 // mpc_discs_from_plans: table[b][k][j] = (X[o][k][0], X[o][k][1], radius[o]) for o = opp[b][j], zeros where there is no such
 // agent (o < 0 or o >= B).  One thread per (agent, stage, disc); every word written is a copy of an input word or zero.
 __global__ void __launch_bounds__(256) discs_from_plans_kernel(int B, int N, int nx, const double *__restrict__ X,

@@ -5,7 +5,8 @@
 // Pacejka model has no fused K1b + K1c, lookahead exists for <PAC, NE = 1> alone, adjoint_kernel has no per-agent form,
 // the constraint forms exist beside the parameter form alone (K1b, the wave evaluation), beside the parameter and box
 // forms alone (the persistent kernel) and for constrained problems alone (the step kernel); the disc forms stand where
-// the constraint forms stand, except that the step kernel has none (it reads no discs).  Where a form needs a table
+// the constraint forms stand, except that the step kernel has none (it reads no discs); the rate forms (RateTab alone, and
+// DiscTab + RateTab) stand where the disc forms stand, never with the lookahead.  Where a form needs a table
 // the caller has not bound, with_own_params / with_own_box put the handle's own one-row table in its place.
 #pragma once
 #include "mpc_handle.hpp"
@@ -107,6 +108,15 @@ static bool launch_eval_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
                     hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, ConTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
                                        with_own_params(h, w), counts, nG, nC, desc, w.con());
                 });
+            else if (w.rtab)     // a rate table is bound: the rate form of K1b, beside the disc form where discs are bound too (here and below)
+                with_flags(shared, w.dtab != nullptr, [&](auto SH, auto DA) {
+                    if constexpr (DA())
+                        hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, DiscTab, RateTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
+                                           with_own_params(h, w), counts, nG, nC, desc, w.disc(), w.rate());
+                    else
+                        hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, RateTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
+                                           with_own_params(h, w), counts, nG, nC, desc, w.rate());
+                });
             else if (w.dtab)     // a disc table is bound (a handle of MPC_CONSTR_DISCS): the disc form of K1b (here and below)
                 with_flag(shared, [&](auto SH) {
                     hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, DiscTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
@@ -128,6 +138,15 @@ static bool launch_eval_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
         with_flag(shared, [&](auto SH) {
             hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, ConTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
                                with_own_params(h, w), counts, nG, nC, nblk, w.con());
+        });
+    else if (w.rtab)
+        with_flags(shared, w.dtab != nullptr, [&](auto SH, auto DA) {
+            if constexpr (DA())
+                hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, DiscTab, RateTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
+                                   with_own_params(h, w), counts, nG, nC, nblk, w.disc(), w.rate());
+            else
+                hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, RateTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
+                                   with_own_params(h, w), counts, nG, nC, nblk, w.rate());
         });
     else if (w.dtab)
         with_flag(shared, [&](auto SH) {
@@ -157,6 +176,18 @@ static void launch_solo_eval(mpc_handle *h, const WorkspaceHost &w, hipStream_t 
             const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
             hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, ConTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
                                want_grad, w.con());
+        });
+        return;
+    }
+    if (w.rtab) {
+        with_model(c.model, [&](auto MODEL) {
+            const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
+            if (w.dtab)
+                hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, DiscTab, RateTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
+                                   want_grad, w.disc(), w.rate());
+            else
+                hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, RateTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
+                                   want_grad, w.rate());
         });
         return;
     }
@@ -287,6 +318,17 @@ static void launch_solo_t(mpc_handle *h, const WorkspaceHost &v, hipStream_t s, 
     if (v.ctab) {
         hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, ConTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
                            with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), v.con());
+        return;
+    }
+    // v.rtab: a rate table is bound, the rate form, on the disc form's terms and beside it where discs are bound too
+    // (the kernel without the lookahead on the lookahead's LDS size: results do not depend on the lookahead)
+    if (v.rtab) {
+        if (v.dtab)
+            hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, DiscTab, RateTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
+                               with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), v.disc(), v.rate());
+        else
+            hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, RateTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
+                               with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), v.rate());
         return;
     }
     // v.dtab: a disc table is bound, the disc form, on the constraint form's terms

@@ -70,7 +70,8 @@ struct SoloClk { long long roll = 0, recs = 0, adj = 0; };
 #define SOLO_CLK(field, t) do { } while (0)
 #endif
 // DS: empty, or the disc table (the disc forms: one trailing DiscTab) -- lane k loads the discs of its stage from the
-// agent's row, whose address is wave-uniform
+// agent's row, whose address is wave-uniform -- and / or the rate table (the rate forms: a trailing RateTab, last) -- lane k
+// takes u_{k-1} and u_{k+1} from the row it evaluates (`row`: xe, or xe2 on the speculative half), u_{-1} from the table
 template <int MODEL, class... DS>
 __device__ __forceinline__ void solo_eval(const DevCfg &c, const Workspace &w, int a, int lane, int req,
                                           double *traj, double *rec SOLO_CLK_ARG, const DS &...ds)
@@ -135,7 +136,13 @@ __device__ __forceinline__ void solo_eval(const DevCfg &c, const Workspace &w, i
         if (is_g) stage_sens_record<MODEL>(c, xs, xe, d, dl, put);
         Geom g;
         stage_geom(c, w, clp, w.cl_index ? w.cl_index[a] : 0, xe[0], xe[1], g);
-        if constexpr (sizeof...(DS) != 0) stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_discs_uniform(ds..., a, hl, N));
+        constexpr bool DA = has_tab<DiscTab, DS...>, RA = has_tab<RateTab, DS...>;
+        if constexpr (DA && RA)
+            stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_discs_uniform(pack_get<DiscTab>(ds...), a, hl, N),
+                                stage_rate_uniform(pack_get<RateTab>(ds...), a, hl, N, row));
+        else if constexpr (RA)
+            stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_rate_uniform(pack_get<RateTab>(ds...), a, hl, N, row));
+        else if constexpr (DA) stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_discs_uniform(ds..., a, hl, N));
         else
         stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put);
     }
@@ -244,8 +251,9 @@ __global__ void __launch_bounds__(64, 1) solo_eval_kernel(const DevCfg c_, const
     // constraint row, the same way)
     DevCfg cm_;
     if constexpr (PA) { cm_ = c_; agent_cfg_uniform(cm_, w.ptab, w.pidx, blockIdx.x); }
-    constexpr bool DA = has_tab<DiscTab, CT...>;   // the disc form (CT = DiscTab): the table goes on to the evaluation
-    if constexpr (sizeof...(CT) != 0 && !DA) agent_con_uniform(cm_, ct..., blockIdx.x);
+    // the disc and rate forms (CT = DiscTab, RateTab or both): the tables go on to the evaluation
+    constexpr bool DA = has_tab<DiscTab, CT...> || has_tab<RateTab, CT...>;
+    if constexpr (has_tab<ConTab, CT...>) agent_con_uniform(cm_, ct..., blockIdx.x);
     const DevCfg &c = PA ? cm_ : c_;
     double *traj = s_solo;
     double *rec = traj + (size_t)(c.N + 1) * ModelDim<MODEL>::NX;
@@ -418,14 +426,18 @@ template <int MODEL> struct SoloOcc { static constexpr int WPS = MODEL == KIN ? 
 // caller bound none), and never with the lookahead, which is an unconstrained problem's.
 // BT = (BoxTab, DiscTab): the disc form (mpc_set_agent_discs), on the same terms -- the evaluations read the discs of the
 // agent's row; the state machine projects the multipliers with the handle's bounds [0, +inf), the same for every agent.
+// BT = (BoxTab, RateTab) or (BoxTab, DiscTab, RateTab): the rate forms (mpc_set_agent_rates), on the disc form's terms --
+// the evaluations add the move penalty of the agent's row; the state machine is what it is without them.  Never with the
+// lookahead (results do not depend on it).
 template <int MODEL, int NE, int MC, bool LA = false, bool PA = false, class... BT>
 __global__ void __launch_bounds__(64 * SOLO_WAVES, SoloOcc<MODEL>::WPS)
 solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int *__restrict__ ctr,
             long long max_trips, BT... bt)
 {
-    constexpr bool BA = sizeof...(BT) != 0, DA = has_tab<DiscTab, BT...>, CA = sizeof...(BT) == 2 && !DA;
+    constexpr bool BA = sizeof...(BT) != 0, DA = has_tab<DiscTab, BT...>, CA = has_tab<ConTab, BT...>, RA = has_tab<RateTab, BT...>;
     static_assert(!BA || PA, "the box form of the persistent kernel exists in the per-agent-parameter form alone");
     static_assert((!CA && !DA) || !LA, "the lookahead is an unconstrained problem's: it has no constraint or disc form");
+    static_assert(!RA || !LA, "the rate forms run without the lookahead");
     using BOX = BoxOf<BA, LaneBox>;
     using CON = ConOf<CA, RowCon>;
     extern __shared__ double s_solo[];
@@ -451,7 +463,7 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
             if constexpr (BA) {
                 DevCfg cm = c;
                 agent_cfg_uniform(cm, w.ptab, w.pidx, a);
-                solo_agent_la<MC>(c, cm, w, a, lane, hist, traj, rec, la_base, max_trips, lane_box_uniform(pack_box(bt...), a, lane));
+                solo_agent_la<MC>(c, cm, w, a, lane, hist, traj, rec, la_base, max_trips, lane_box_uniform(pack_get<BoxTab>(bt...), a, lane));
             } else if constexpr (PA) {
                 DevCfg cm = c;
                 agent_cfg_uniform(cm, w.ptab, w.pidx, a);
@@ -471,10 +483,10 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
         if constexpr (PA) { cm_ = c; agent_cfg_uniform(cm_, w.ptab, w.pidx, a); }
         const DevCfg &cm = PA ? cm_ : c;
         BOX bx{};
-        if constexpr (BA) bx = lane_box_uniform(pack_box(bt...), a, lane);
+        if constexpr (BA) bx = lane_box_uniform(pack_get<BoxTab>(bt...), a, lane);
         CON cn{};
         if constexpr (CA) {
-            const ConTab &ct = pack_con(bt...);
+            const ConTab &ct = pack_get<ConTab>(bt...);
             agent_con_uniform(cm_, ct.ctab, ct.cidx, a);
             cn = row_con_uniform(ct, a);
         }
@@ -492,12 +504,16 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
             if ((req & (REQ_GRAD | REQ_COST)) == 0) break;              // uniform: the agent is done
 #if MPC_DEV_STAMP == 5
             t_adv += __builtin_amdgcn_s_memrealtime() - ta;
-            if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk, pack_disc(bt...));
+            if constexpr (DA && RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...));
+            else if constexpr (RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk, pack_get<RateTab>(bt...));
+            else if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk, pack_get<DiscTab>(bt...));
             else
             solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk);
             ntrip++;
 #else
-            if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, pack_disc(bt...));
+            if constexpr (DA && RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...));
+            else if constexpr (RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, pack_get<RateTab>(bt...));
+            else if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, pack_get<DiscTab>(bt...));
             else
             solo_eval<MODEL>(cm, w, a, lane, req, traj, rec);
 #endif

@@ -144,10 +144,52 @@ __device__ __forceinline__ StageDiscs stage_discs_uniform(const DiscTab &t, int 
     for (int i = 0; i < 3 * NDISC; i++) s.v[i] = r[i];
     return s;
 }
+// The rate table of mpc_set_agent_rates, as the rate forms of the kernels receive it: the LAST trailing argument, alone
+// or behind the DiscTab (a handle with a rate table has no constraint table: the binder refuses the second of the two).
+struct RateTab {
+    const double *rtab;                            // [P][NRATE] caller's table
+    const int *ridx;                               // [B]        caller's row index per agent
+};
+// The move penalty's view of stage k of agent a: the weights of the agent's row and the stage's two neighbours.
+// `prev_of(i)` / `next_of(i)` read element i of u_{k-1} / u_{k+1} from where the route holds the agent's inputs; stage 0
+// takes u_{-1} from the row, the last stage reads no successor (nothing past stage N - 1 is touched).
+template <class Prev, class Next>
+__device__ __forceinline__ StageRate stage_rate_from(const double *__restrict__ r, int k, int N, Prev prev_of, Next next_of)
+{
+    StageRate s;
+    s.w[0] = r[0]; s.w[1] = r[1];
+    s.last = k == N - 1;
+    if (k == 0) { s.prev[0] = r[2]; s.prev[1] = r[3]; }
+    else { s.prev[0] = prev_of(0); s.prev[1] = prev_of(1); }
+    if (s.last) { s.next[0] = 0.0; s.next[1] = 0.0; }
+    else { s.next[0] = next_of(0); s.next[1] = next_of(1); }
+    return s;
+}
+// a different agent in every lane (K1b, the fused kernel): the neighbours are the slot's own entries of useq
+__device__ __forceinline__ StageRate stage_rate(const RateTab &t, int a, int k, int N, const double *__restrict__ useq_slot, size_t St)
+{
+    return stage_rate_from(t.rtab + (size_t)t.ridx[a] * NRATE, k, N,
+                           [=](int i) { return useq_slot[(size_t)(2 * (k - 1) + i) * St]; },
+                           [=](int i) { return useq_slot[(size_t)(2 * (k + 1) + i) * St]; });
+}
+// ... one agent per wave (the wave evaluation): the row address is wave-uniform, the neighbours are the evaluated row's
+__device__ __forceinline__ StageRate stage_rate_uniform(const RateTab &t, int a, int k, int N, const double *__restrict__ row)
+{
+    const int ri = __builtin_amdgcn_readfirstlane(t.ridx[a]);
+    return stage_rate_from(t.rtab + (size_t)ri * NRATE, k, N, [=](int i) { return row[2 * (k - 1) + i]; },
+                           [=](int i) { return row[2 * (k + 1) + i]; });
+}
 // which table a kernel's trailing pack holds
 template <class A, class B> struct SameTab { static constexpr bool v = false; };
 template <class A> struct SameTab<A, A> { static constexpr bool v = true; };
 template <class X, class... T> constexpr bool has_tab = (SameTab<X, T>::v || ... || false);
+// ... and that table out of the pack
+template <class X, class T0, class... T>
+__device__ __forceinline__ const X &pack_get(const T0 &t0, const T &...t)
+{
+    if constexpr (SameTab<X, T0>::v) return t0;
+    else return pack_get<X>(t...);
+}
 template <bool PA> struct WsArgT { using type = Workspace; };
 template <> struct WsArgT<true> { using type = WorkspacePA; };
 template <bool PA> using WsArg = typename WsArgT<PA>::type;
@@ -440,14 +482,6 @@ __device__ __forceinline__ RowCon row_con_uniform(const ConTab &ct, int a)
 {
     return RowCon{ct.ctab + (size_t)__builtin_amdgcn_readfirstlane(ct.cidx[a]) * NCONSTR};
 }
-// the tables out of a kernel's trailing pack (BoxTab) or (BoxTab, ConTab)
-__device__ __forceinline__ const BoxTab &pack_box(const BoxTab &b) { return b; }
-__device__ __forceinline__ const BoxTab &pack_box(const BoxTab &b, const ConTab &) { return b; }
-__device__ __forceinline__ const ConTab &pack_con(const BoxTab &, const ConTab &c) { return c; }
-// ... or (BoxTab, DiscTab)
-__device__ __forceinline__ const BoxTab &pack_box(const BoxTab &b, const DiscTab &) { return b; }
-__device__ __forceinline__ const DiscTab &pack_disc(const BoxTab &, const DiscTab &d) { return d; }
-
 template <class BOX>
 __device__ __forceinline__ double prox_p(const DevCfg &c, const BOX &bx, int par, double x, double g, double gamma)
 {

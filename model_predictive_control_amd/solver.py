@@ -61,7 +61,8 @@ _AgentTable = collections.namedtuple("_AgentTable", "width width_per_N setter pl
 _AGENT_TABLES = {"params": _AgentTable(_lib.NPARAM, 0, "mpc_set_agent_params", True),
                  "bounds": _AgentTable(_lib.NBOUND, 0, "mpc_set_agent_bounds", False),
                  "constraints": _AgentTable(_lib.NCONSTR, 0, "mpc_set_agent_constraints", False),
-                 "discs": _AgentTable(0, 3 * _lib.NDISC, "mpc_set_agent_discs", False)}
+                 "discs": _AgentTable(0, 3 * _lib.NDISC, "mpc_set_agent_discs", False),
+                 "rates": _AgentTable(_lib.NRATE, 0, "mpc_set_agent_rates", False)}
 
 
 class BatchedMPC:
@@ -268,6 +269,37 @@ class BatchedMPC:
     def agent_discs_bound(self):
         return "discs" in self._keep
 
+    def set_agent_rates(self, table, index):
+        """Binds a per-agent table of move penalties (mpc_set_agent_rates): table [P, 4] float64 (rows
+        [w_d, w_delta, d_prev, delta_prev], as _lib.rate_rows makes them), index [B] int32 = the row of agent b.  Bound,
+        every call that evaluates the horizon's cost (eval_cost_grad(_wave), solve, solve_async, solve_active, the closed
+        loops) adds w_d (d_k - d_{k-1})^2 + w_delta (delta_k - delta_{k-1})^2 to stage k of agent b, u_{-1} being the
+        row's (d_prev, delta_prev), and serves batches of exactly B agents.  Beside the parameter, bounds and disc tables
+        (together they are for the same B); not beside a constraint table.  The tensors stay the caller's: the library
+        reads them at every call, so rows may be rewritten in place between calls (a host loop writes the input it
+        applies into columns 2 and 3; the closed loops do that themselves and need P == B with index = arange(B)); the
+        engine keeps them alive until clear_agent_rates()."""
+        self._bind_agent_table("rates", table, index)
+
+    def clear_agent_rates(self):
+        """Unbinds the rate table: the engine is what it was before set_agent_rates."""
+        self._clear_agent_table("rates")
+
+    @property
+    def agent_rates_bound(self):
+        return "rates" in self._keep
+
+    def _check_rate_rows(self, B):
+        """What the closed loops ask of a bound rate table: they write the applied input into agent b's own row."""
+        if "rates" not in self._keep:
+            return
+        table, index = self._keep["rates"]
+        if int(table.shape[0]) != B or int(index.shape[0]) != B:
+            raise ValueError(f"the bound rate table has {int(table.shape[0])} rows for {int(index.shape[0])} agents: a closed loop "
+                             f"needs one row per agent (P == B = {B}, index = arange(B))")
+        if not torch.equal(index, torch.arange(B, dtype=torch.int32, device=index.device)):
+            raise ValueError("the bound rate table's index is not arange(B): a closed loop writes the applied input into row b of agent b")
+
     def discs_from_plans(self, X, opp, radius, out=None):
         """mpc_discs_from_plans: the disc table [B, 3 * NDISC * N] in which agent b's discs are the plans of its
         opponents -- X [B, N, nx] as rollout() returns it for the agents' current plans, opp [B, NDISC] int32 (the
@@ -460,6 +492,7 @@ class BatchedMPC:
         failures[B], stats of the last solve)."""
         B = x.shape[0]
         self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
+        self._check_rate_rows(B)
         cl = self._centerline(centerline, cl_index, B)
         x, U = x.clone(), U.clone()
         if self.m:
@@ -485,6 +518,7 @@ class BatchedMPC:
         and lam are copies; the table is the bound one)."""
         B, T = x.shape[0], int(T)
         self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
+        self._check_rate_rows(B)
         if T < 0:
             raise ValueError("T must be >= 0")
         G, reach = self._scene_args(B, G, radius, reach)
@@ -576,6 +610,7 @@ class BatchedMPC:
         step.  Returns an EventLoopResult (copies; the arguments are not written)."""
         B, T = x.shape[0], int(T)
         self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
+        self._check_rate_rows(B)
         thr, max_hold = self._trigger_args(thr, max_hold)
         if T < 0:
             raise ValueError("T must be >= 0")
@@ -676,6 +711,7 @@ class BatchedMPC:
         trk = self._track(track_obj)
         B, T = x.shape[0], int(T)
         self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
+        self._check_rate_rows(B)
         thr, max_hold = self._trigger_args(thr, max_hold)
         if T < 0:
             raise ValueError("T must be >= 0")
