@@ -43,6 +43,14 @@ struct DevCfg {
     double alm_eps, alm_delta, Sigma0, eps0, rho, Delta, theta, Mcap, Sigma_max;
     double Delta_lower, Sigma0_lower, eps0_increase, rho_increase;
     double lip_eps, lip_delta, Lgamma, L_min, L_max, tau_min, qub_tol;
+    // (appended: every offset above -- and with it the code of the kernels that read none of these -- is what it was)
+    int spec_policy;     // MPC_SPEC_POLICY: 0 = a speculative gradient is issued whenever its point exists; >= 1 = not when the
+                         // line-search condition or the stop test, both known by then, will throw it away (spec_is_lost:
+                         // mpc_solver.hpp; same results, same rounds)
+    int spec_retry;      // descent-lemma retries of a line-search trial from this depth on (1 = every retry, 2 = from the second
+                         // doubling, Ln >= 4 Lk) issue no speculative gradient: the next iteration asks for it itself, a round
+                         // later (0 = all of them speculate; the host sets it per launch, with `chain`: the launches that carry chain
+                         // blocks, under MPC_SPEC_POLICY=2 only, never for the persistent kernels -- same results, more rounds)
 };
 
 #define MPC_DEV __device__ __forceinline__

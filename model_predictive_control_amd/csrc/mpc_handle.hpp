@@ -97,6 +97,11 @@ struct mpc_handle {
                                 // (chain_block) ride in its step launch.  Measured with the one-wave form (r03_experiments 18):
                                 // 65 536 agents (groups of 16 384) +1.2 % with them; 32 768 agents (groups of 10 923)
                                 // and 16 384 (groups of 8 192) -1 ... -2 %: only the full rounds of big groups
+    int spec_depth = 1;         // MPC_SPEC_DEPTH: under MPC_SPEC_POLICY=2, the descent-lemma retry of a line-search trial from which
+                                // no speculative gradient is issued in the launches that carry chain blocks (1 = every retry, 2 = from the second doubling on).
+                                // Measured, 65 536 kinematic agents, alternating on one box (profiles/r16_speculation.txt): policy 0
+                                // 498.9 - 500.9 k solves/s, policy 1 502.9 - 504.0 k, policy 2 at depth 2 503.2 - 505.2 k, at depth 1
+                                // 505.6 - 507.6 k
     int lds_pairs = 0;          // MPC_LDS_PAIRS: history pairs the step kernel's LDS copy holds (0 = chosen by launch_step_t)
     int num_cus = 256;
     int nearest_mode = 2;                 // mpc_set_nearest_blocks: 0 full scan (MPC_NEAREST_SCAN), 2 grid of index ranges (default);
@@ -331,6 +336,14 @@ static void read_switches(mpc_handle *h)
     const auto num = [](const char *e, int &v) { if (e) v = atoi(e); };
     DevCfg &d = h->dc;
     d.no_spec = getenv("MPC_NO_SPEC") != nullptr;
+    // which speculative gradients are not issued (DevCfg::spec_policy, spec_retry): 0 none, 1 the ones the line search or
+    // the stop test is known to throw away, 2 also those of descent-lemma retries in the launches that carry chain blocks (launch_step_t)
+    d.spec_policy = 2;
+    num(getenv("MPC_SPEC_POLICY"), d.spec_policy);
+    d.spec_policy = std::max(0, std::min(2, d.spec_policy));
+    d.spec_retry = 0;
+    num(getenv("MPC_SPEC_DEPTH"), h->spec_depth);
+    h->spec_depth = std::max(1, std::min(30, h->spec_depth));
     d.no_memo = getenv("MPC_NO_MEMO") != nullptr;
     d.no_la = getenv("MPC_NO_LOOKAHEAD") != nullptr;
     d.all_rows = getenv("MPC_ALL_ROWS") != nullptr;

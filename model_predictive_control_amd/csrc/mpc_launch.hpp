@@ -226,7 +226,7 @@ static int step_lds_pairs(int ne, int n, int M, int m, int lds_pairs)
 static size_t step_dyn_lds(int ne, int n, int P, bool chain)
 {
     size_t lds = (size_t)STEP_WAVES * 2 * P * n * sizeof(double);
-    if (ne == 1 && chain) lds = std::max(lds, sizeof(double) * CHAIN_SLOTS * (size_t)(n + 1) + sizeof(int) * CHAIN_SLOTS);
+    if (ne == 1 && chain) lds = std::max(lds, chain_lds_bytes(n));
     return lds;
 }
 
@@ -243,6 +243,11 @@ static void launch_step_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
     int nchain = 0;
     DevCfg dcl = h->dc;
     dcl.chain = h->dc.chain && slot_bound >= h->chain_min;
+    // MPC_SPEC_POLICY=2: descent-lemma retries do not speculate in the launches that carry the chain blocks -- the full rounds
+    // of big groups, where the round of latency it costs an agent is hidden, and only where the blocks are on at all (not
+    // under MPC_NO_CHAIN, for n > 64 or, unless MPC_CHAIN_MIN is set, on the Pacejka model: no workload but the one the
+    // policy was measured on gets more rounds from it)
+    dcl.spec_retry = h->dc.spec_policy >= 2 && dcl.chain ? h->spec_depth : 0;
     if (NE == 1 && dcl.chain) {
         nchain = w.Bp / 64;
         if (slot_bound >= 0) nchain = std::min(nchain, (slot_bound + 126) / 64 + 1);

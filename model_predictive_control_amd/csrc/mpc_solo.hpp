@@ -500,7 +500,7 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
             const long long ta = __builtin_amdgcn_s_memrealtime();
 #endif
             const AgentIn<NE> in = load_agent<NE>(c, w, a, lane);
-            const int req = advance_agent<NE, MC, true, false, BOX, CON>(c, w, a, lane, in, hist, false, /*allow_spec=*/spec, false, 1 << 30, bx, cn);
+            const int req = advance_agent<NE, MC, true, false, BOX, CON, /*PRED=*/false>(c, w, a, lane, in, hist, false, /*allow_spec=*/spec, false, 1 << 30, bx, cn);
             if ((req & (REQ_GRAD | REQ_COST)) == 0) break;              // uniform: the agent is done
 #if MPC_DEV_STAMP == 5
             t_adv += __builtin_amdgcn_s_memrealtime() - ta;

@@ -692,6 +692,26 @@ __device__ __forceinline__ int spec_point(const DevCfg &c, const BOX &bx, int pa
     }
     return nj;
 }
+// Two of the ways a speculative gradient is lost are decided by numbers the agent holds BEFORE it is issued (PH_W_LS_G,
+// and again at every descent-lemma retry of PH_W_LS_C, with that retry's gamma+, ||p+||^2 and grad+'p+): the cost at the
+// prox point that the agent then waits for enters the descent-lemma test alone, and when that test fails the step halves
+// and the question is asked again.  If it passes, the trial is REJECTED when the line-search condition of PH_W_LS_C fails
+// -- the same expressions in the same order on the same operands -- and an accepted iterate STOPS at PH_AFTER_DL when its
+// measure sqrt(||p+||^2) / gamma+ is <= eps or not finite or the iteration limit is reached (a step-size heuristic on the
+// way either keeps gamma, and with it ||p||^2, or the gradient was for another gamma and is not taken anyway).  Either
+// way nothing reads the channel-2 gradient: true = do not ask for it.  The evaluation budget and the no-progress count
+// are not predicted (a gradient issued for nothing costs time, never a bit).
+__device__ __forceinline__ bool spec_is_lost(const DevCfg &c, double psin, double ppn, double gpn, double gamman, double phik,
+                                             double sigpp, double tau, double eps, int k, int max_it)
+{
+#pragma clang fp contract(off)   // fixed roundings: the decisions of PH_W_LS_C and PH_AFTER_DL bit for bit
+    const double phin = psin + ppn / (2.0 * gamman) + gpn;
+    const double ls_cond = phin - (phik - sigpp);
+    const double margin = (1.0 + fabs(phik)) * c.qub_tol;
+    if (!(ls_cond <= margin) && tau / 2.0 >= c.tau_min) return true;
+    const double epsn = sqrt(ppn) / gamman;
+    return epsn <= eps || k + 1 == max_it || !isfinite(epsn);
+}
 
 // K5 helper: alpaqa detail::update_penalty_weights (per-constraint factors), lanes stride over m
 __device__ __forceinline__ void update_penalty(const DevCfg &c, const Workspace &w, size_t am, int lane,
@@ -760,7 +780,11 @@ __device__ __forceinline__ AgentIn<NE> load_agent(const DevCfg &c, const Workspa
 // bounds table, fetched with the agent's rows)
 // CON: where the projection of the multipliers takes the constraint bounds from (CfgCon: the DevCfg's; RowCon: `cn`, the
 // agent's own row of a bound constraint table)
-template <int NE, int MC, bool HASM = true, bool LEAN = false, class BOX = CfgBox, class CON = CfgCon>
+// PRED = false: the instantiation holds no predictor of lost speculation (spec_is_lost; MPC_SPEC_POLICY is then 0 whatever
+// the DevCfg says).  The persistent kernel without the lookahead: its speculative gradient rides along on lanes the
+// evaluation leaves idle (solo_dual) or is not issued at all, so a dropped one saves nothing there, and the kinematic
+// variant is compiled against 256 registers with spills that the extra code made worse (4 096 agents: -2.8 %).
+template <int NE, int MC, bool HASM = true, bool LEAN = false, class BOX = CfgBox, class CON = CfgCon, bool PRED = true>
 __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int lane, const AgentIn<NE> &in,
                              double *hist, bool hist_ready, bool allow_spec = true, bool allow_chain = false,
                              int P = 1 << 30, const BOX &bx = BOX(), const CON &cn = CON())
@@ -857,11 +881,17 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
         // needs for its Hessian-vector product (at x+ + h q_J, PH_AFTER_DL) is evaluated as well, on the
         // second channel, assuming x+ is accepted with step gm.  Same formulas as PH_AFTER_DL on the same
         // inputs, so the point -- and the gradient -- are bit-identical when the assumption holds.
-        auto speculate = [&](double gm) {
-            if (c.no_spec || !allow_spec) { spec = 0; return; }
+        // Not issued (MPC_SPEC_POLICY): when the trial will be rejected or the accepted iterate will stop whatever the
+        // pending cost turns out to be (spec_is_lost: exact), and -- on a descent-lemma retry of depth >= c.spec_retry,
+        // a policy the host sets for the full rounds of the round path -- when the step may well halve once more;
+        // PH_AFTER_DL then asks for the gradient itself, a round later.
+        auto speculate = [&](double gm, bool retry = false) {
+            spec = 0;
+            if (c.no_spec || !allow_spec) return;
+            if (PRED && c.spec_policy != 0 && spec_is_lost(c, psin, ppn, gpn, gm, phik, sigpp, tau, eps, k, max_it)) return;
+            if (PRED && retry && c.spec_retry > 0 && Ln >= Lk * (double)(1 << c.spec_retry)) return;
             Row<NE> xh;
             const int nj = spec_point<NE>(c, bx, par, n, lane, XN, GE, gm, xh);
-            spec = 0;
             if (nj > 0 && nj < n) {
                 strow<NE>(w.xe2 + an, n, lane, xh);
                 spec = 1; spec_gamma = gm;
@@ -1145,7 +1175,7 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
                 Ln *= 2.0; gamman /= 2.0;
                 prox_to_xe<NE>(c, bx, w.xe + an, n, lane, XN, GE, gamman, t_pp, t_gp); ppn = t_pp; gpn = t_gp;
                 req = REQ_COST; // stay
-                speculate(gamman);
+                speculate(gamman, /*retry=*/true);
                 break;
             }
             const double phin = psin + ppn / (2.0 * gamman) + gpn;
@@ -1348,6 +1378,11 @@ __device__ __forceinline__ int wave_append(int *counter, bool on)
 constexpr int CHAIN_SLOTS = 64;   // slots per workgroup: one tile of 64 x (n + 1) doubles, 21 KB at n = 40 -- under the 31 KB of
                                   // history the wave-per-agent blocks of the launch hold (12 pairs), so that five workgroups of
                                   // either kind share a CU (both kinds get the launch's one dynamic-LDS size)
+// dynamic LDS of a chain block: the tile, the slots' agents, and whether they speculate, their finite-difference steps and sets J
+__host__ __device__ constexpr size_t chain_lds_bytes(int n)
+{
+    return sizeof(double) * CHAIN_SLOTS * (size_t)(n + 1) + (2 * sizeof(int) + sizeof(double) + sizeof(unsigned long long)) * CHAIN_SLOTS;
+}
 // BA: every agent projects onto its own box, row bt.bidx[a] of the bounds table.  The thread that will own the agent of
 // slot t is the one that reads the slot's entry, so the row is asked for there, ahead of the gradient tile.
 template <bool BA>
@@ -1369,6 +1404,11 @@ __device__ __forceinline__ void chain_block(const DevCfg &c, const Workspace &w,
     if (slot0 < 0 || slot0 >= gpad) return;              // uniform: no gradient slots here
     double *tA = lds;
     int *s_agent = (int *)(tA + CHAIN_SLOTS * ld);       // agent of the slot or -1
+    // the speculation of the slot's agent, for the copy-out below: whether a speculative gradient is issued, the
+    // finite-difference step and the set J as a bit per element
+    int *s_spec = s_agent + CHAIN_SLOTS;
+    double *s_h = (double *)(s_spec + CHAIN_SLOTS);
+    unsigned long long *s_inJ = (unsigned long long *)(s_h + CHAIN_SLOTS);
     BoxOf<BA, AgentBox> bx{};
     const int total = CHAIN_SLOTS * n;
     {
@@ -1400,6 +1440,9 @@ __device__ __forceinline__ void chain_block(const DevCfg &c, const Workspace &w,
     }
     __builtin_amdgcn_wave_barrier();
     const int a = s_agent[t];
+    double spec_h = 0.0;
+    int spec_on = 0;
+    unsigned long long inJ = 0ull;
     if (a >= 0) {
         double *r = w.rec + (size_t)a * REC;
         const double gm = r[R_GAMMAN];
@@ -1412,26 +1455,30 @@ __device__ __forceinline__ void chain_block(const DevCfg &c, const Workspace &w,
         }
         const double h = fd_step(sxx.total(n));
         double *ga = tA + t * ld;
-        double *x2 = w.xe2 + (size_t)a * n;              // the speculative point goes straight to its row (16 bytes per stage)
         TreeSum spp, sgp;
         int cnt = 0;
         for (int k = N - 1; k >= 0; k--) {
             const double x0 = useq[(size_t)(2 * k) * St], x1 = useq[(size_t)(2 * k + 1) * St];
             const double g0 = ga[2 * k], g1 = ga[2 * k + 1];
             const double p0 = prox_p(c, bx, 0, x0, g0, gm), p1 = prox_p(c, bx, 1, x1, g1, gm);   // prox_to_xe
-            ga[2 * k] = x0 + p0; ga[2 * k + 1] = x1 + p1;
+            ga[2 * k] = p0; ga[2 * k + 1] = p1;          // (the step: the copy-out forms xhat+ and the speculative point from it)
             spp.add(k, fma(p0, p0, 0.0), fma(p1, p1, 0.0));
             sgp.add(k, fma(g0, p0, 0.0), fma(g1, p1, 0.0));
             if (!c.no_spec) {                                                          // speculate()
                 const bool in0 = in_J(c, bx, 0, x0, g0, gm), in1 = in_J(c, bx, 1, x1, g1, gm);
                 cnt += (in0 ? 1 : 0) + (in1 ? 1 : 0);
-                const double q0 = in0 ? 0.0 : p0, q1 = in1 ? 0.0 : p1;
-                x2[2 * k] = x0 + h * q0; x2[2 * k + 1] = x1 + h * q1;
+                inJ |= (in0 ? 1ull : 0ull) << (2 * k) | (in1 ? 2ull : 0ull) << (2 * k);
             }
         }
-        const bool spec = !c.no_spec && cnt > 0 && cnt < n;
-        r[R_PSIN] = rec_int_of(r[R_FALLBACK]) != 0 ? r[R_PSIXH] : r[R_PSIE];
-        r[R_PPN] = spp.total(n); r[R_GPN] = sgp.total(n);
+        const double psin = rec_int_of(r[R_FALLBACK]) != 0 ? r[R_PSIXH] : r[R_PSIE];
+        const double ppn = spp.total(n), gpn = sgp.total(n);
+        bool spec = !c.no_spec && cnt > 0 && cnt < n;
+        // (MPC_SPEC_POLICY: not when the trial will be rejected or the accepted iterate will stop -- as speculate() decides it)
+        if (spec && c.spec_policy != 0)
+            spec = !spec_is_lost(c, psin, ppn, gpn, gm, r[R_PHI], r[R_SIGPP], r[R_TAU], r[R_EPS], rec_int_of(r[R_K]), rec_int_of(r[R_MAXIT]));
+        spec_on = spec ? 1 : 0; spec_h = h;
+        r[R_PSIN] = psin;
+        r[R_PPN] = ppn; r[R_GPN] = gpn;
         r[R_SPEC] = rec_int(spec ? 1 : 0);
         if (spec) { r[R_SPEC_GAMMA] = gm; r[R_NSPEC] += 1.0; r[R_NGRAD] += 1.0; }
         r[R_NEVALS] = rec_int(rec_int_of(r[R_NEVALS]) + 1); r[R_NCOST] += 1.0;
@@ -1441,14 +1488,30 @@ __device__ __forceinline__ void chain_block(const DevCfg &c, const Workspace &w,
         const int pg = wave_append(&counts_out[0], spec);
         if (spec && pg >= 0 && pg < w.Bp) lists_out[pg] = a | CH2_BIT;
     }
+    s_spec[t] = spec_on; s_h[t] = spec_h; s_inJ[t] = inJ;
     __builtin_amdgcn_wave_barrier();
-    for (int base = 0; base < total; base += 64 * 8) {   // the tile (now xhat+) -> xe rows
+    // the tile (now the steps p) -> xe rows, xhat+ = x+ + p, and -- for the agents that speculate, and only for them -- xe2
+    // rows, x+ + h q with q = p outside J and 0 inside: x+ from the agent's xn row, whose bits the finished round copied
+    // into useq (coalesced, like the two stores)
+    for (int base = 0; base < total; base += 64 * 8) {   // eight loads in flight per lane, as on the way in
+        double x[8];
+        int row[8], col[8];
 #pragma unroll
         for (int u = 0; u < 8; u++) {
             const int idx = base + u * 64 + t;
             const int r = idx / n, j = idx - r * n;
             const int ar = idx < total ? s_agent[r] : -1;
-            if (ar >= 0) w.xe[(size_t)ar * n + j] = tA[r * ld + j];
+            row[u] = ar >= 0 ? r : -1; col[u] = j;
+            x[u] = ar >= 0 ? w.xn[(size_t)ar * n + j] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            if (row[u] < 0) continue;
+            const int r = row[u], j = col[u];
+            const size_t o = (size_t)s_agent[r] * n + j;
+            const double p = tA[r * ld + j];
+            w.xe[o] = x[u] + p;
+            if (s_spec[r] != 0) w.xe2[o] = x[u] + s_h[r] * ((s_inJ[r] >> j & 1ull) != 0ull ? 0.0 : p);
         }
     }
 }
