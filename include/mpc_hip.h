@@ -267,6 +267,64 @@ int mpc_closed_loop_traffic(mpc_handle *h, int B, int T, int shift, int G, const
 int mpc_default_rates(const mpc_config *cfg, double *row);
 int mpc_set_agent_rates(mpc_handle *h, const double *table, int P, const int32_t *index, int B);
 
+/* Risk-field cost: soft obstacle potentials per agent and stage -- a sixth table of P rows in device memory and one row
+ * index per agent; like the disc table its data varies with the stage.  One row, all doubles:
+ * [N][MPC_NFIELD][MPC_NFSRC], MPC_FIELD_ROW(N) of them.  One source is [cx, cy, c, s, A, kx, ky, alpha]: a skewed
+ * anisotropic Gaussian (the `dnf` part of the reference's driving-risk potential field) of height A around (cx, cy);
+ * (c, s) are the cosine and sine of the source's own frame, kx = 1 / (2 sigma_x^2) acts along the frame and ky across it,
+ * alpha is the skew along it (in the reference (v - v_obs) / 5; here frozen into the data).  With (x, y) the position at
+ * the end of stage k (x_{k+1}, where every stage term is taken), stage k's cost -- behind the move penalty and before the
+ * ALM terms -- gets its sources, and the stage's state gradient their derivative, every operation rounded on its own and
+ * in this order, source j = 0 before j = 1:
+ *     dx = x - cx,  dy = y - cy,  a = (c dx) + (s dy),  l = (c dy) - (s dx)
+ *     E = ((kx a) a + (ky l) l) + alpha a,   V = A exp(-E),   L_k = L_k + V
+ *     ga = -(V (2 (kx a) + alpha)),  gl = -(V (2 (ky l)))
+ *     dL/dx_k[0] = dL/dx_k[0] + ((c ga) - (s gl)),   dL/dx_k[1] = dL/dx_k[1] + ((s ga) + (c gl))
+ * psi stays the sum of the stage costs in stage order; the adjoint recursion carries the state gradient like any other.
+ * A source with A == 0 is skipped: it adds nothing, not even a signed zero -- that is how "no obstacle at this stage" is
+ * said, and a table of zeros gives the bits of the call without a table.  exp is the device library's, full range, one
+ * out-of-line body for the four evaluation routes (K1b, the fused K1b + K1c kernel, the wave evaluation, the persistent
+ * kernel), which call one device function: a request gets the same bits whichever serves it.  It is a cost, not a
+ * constraint: no multiplier, and the inner problem stays feasible whatever the sources are.
+ * The table is read by mpc_eval_cost_grad(_wave), mpc_solve_batch(_async), mpc_solve_active and the closed loops (which
+ * read it as it is bound -- obstacles standing on the track: stage k of every re-plan reads entry k of the agent's row);
+ * mpc_stage_cost, mpc_rhs, mpc_rollout and mpc_prox_step do not read it.  Handles of MPC_CONSTR_NONE, _STATE_SQ and _LANE
+ * take it, with the handle's own constraint data (a lane band and soft obstacles in one solve); beside a rate table the
+ * two terms add up.
+ * mpc_default_fields (host only): a row of zeros, MPC_FIELD_ROW(cfg->N) doubles.
+ * mpc_set_agent_fields: the semantics of the other tables.  table == NULL unbinds; bound, the calls above use row
+ * index[b] for agent b and return MPC_E_ARG for a batch size other than B; bound beside other tables it is for the same
+ * B.  table [P][MPC_FIELD_ROW(N)] and index [B] are DEVICE memory of the caller, read at every call: rows may be
+ * rewritten in place between calls.  At P == B = 65 536, N = 20 the table is 168 MB.  The P rows are checked once, at bind
+ * time: every value finite, A >= 0, kx >= 0, ky >= 0, and alpha != 0 only with kx > 0 (or the skew is unbounded); index
+ * ranges are the caller's to check (the Python front end does).  Refused (MPC_E_ARG) while an asynchronous solve is in
+ * flight, on a handle of MPC_CONSTR_DISCS (there an obstacle is a disc), and while a constraint table is bound -- as
+ * mpc_set_agent_constraints is while a field table is bound (the kernels have no form that takes both).
+ * mpc_fields_from_plans: the gather for inter-agent avoidance, asynchronous on `stream`.  X [B][N][nx] is what
+ * mpc_rollout wrote for the agents' current plans, opp [B][MPC_NFIELD] (int32) the opponents of agent b (< 0 or >= B:
+ * none; MPC_NFIELD == MPC_NDISC, so an opp of mpc_opponents_from_plans serves), shape [B][4] = [A, kx, ky, gain] agent b
+ * AS AN OBSTACLE; table [B][MPC_FIELD_ROW(N)] receives, for o = opp[b][j],
+ *     table[b][k][j] = [X[o][k][0], X[o][k][1], cos X[o][k][2], sin X[o][k][2], shape[o][0], shape[o][1], shape[o][2],
+ *                       shape[o][3] * (X[b][k][3] - X[o][k][3])]
+ * -- cos and sin by the device's sincos, the subtraction and the product each rounded on its own; column 3 is v on the
+ * kinematic model and vx on the Pacejka model -- or eight zeros where there is no opponent.  shape is device data and is
+ * not checked, as radius is not.  All four are device memory.
+ * mpc_closed_loop_traffic_field: mpc_closed_loop_traffic with soft obstacles -- its arguments and its steps, `shape`
+ * beside `radius` (which still drives the selection and traj_clear), step 3 being table = mpc_fields_from_plans(X, opp,
+ * shape), and `table` the FIELD table currently bound, with P == B rows.  On a handle of any constr_mode except
+ * MPC_CONSTR_DISCS (lambda may be NULL where m == 0). */
+#define MPC_NFIELD 2
+#define MPC_NFSRC 8
+#define MPC_FIELD_ROW(N) (MPC_NFIELD * MPC_NFSRC * (N))
+int mpc_default_fields(const mpc_config *cfg, double *row);
+int mpc_set_agent_fields(mpc_handle *h, const double *table, int P, const int32_t *index, int B);
+int mpc_fields_from_plans(mpc_handle *h, int B, const double *X, const int32_t *opp, const double *shape, double *table,
+                          void *stream);
+int mpc_closed_loop_traffic_field(mpc_handle *h, int B, int T, int shift, int G, const double *radius, const double *shape,
+                                  double reach, double *x, const double *cl, const int32_t *cl_index, double *U,
+                                  double *lambda, double *table, double *traj_x, double *traj_u, int32_t *traj_opp,
+                                  double *traj_clear, int32_t *fail_count, double *stats, void *stream);
+
 /* a-1(car_dynamics.py:93-132 / dynamics.py:67-119,:144-173): dx[B][nx] = f(x[B][nx], u[B][2]) */
 int mpc_rhs(mpc_handle *h, int B, const double *x, const double *u, double *dx, void *stream);
 
@@ -452,7 +510,7 @@ int mpc_lane_payoff(mpc_handle *h, int B, int K, const double *params15, const d
                     const double *cars, const int32_t *ncars, double *out, void *stream);
 
 /* test aid: evaluates the device math used by the kernels; op 0 sin, 1 cos, 2 atan, 3 atan2(a,b),
- * 4 tan on n values */
+ * 4 tan, 5 exp (the out-of-line one the risk field calls) on n values */
 int mpc_math_probe(mpc_handle *h, int n, int op, const double *a, const double *b, double *out,
                    void *stream);
 /* more figures of the last solve: launch pairs (step, eval) issued over all sub-batch groups and

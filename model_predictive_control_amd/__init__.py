@@ -3,13 +3,17 @@ controller.MPCController hot path).  Host code is Python; kernels are hand-writt
 behind the C-ABI in include/mpc_hip.h."""
 from . import _lib
 from ._lib import (MODEL_KINEMATIC, MODEL_PACEJKA, WRAP_FLOOR, WRAP_FMOD, WRAP_IEEE, CONSTR_NONE,
-                   CONSTR_STATE_SQ, CONSTR_LANE, CONSTR_DISCS, NDISC, SCENE_MAX, default_discs, disc_rows, NRATE, default_rates, rate_rows, NSTATS, NPARAM, MpcConfig, default_config, default_params, param_rows,
-                   NBOUND, default_bounds, bound_rows, NCONSTR, default_constraints, constraint_rows, MpcError)
+                   CONSTR_STATE_SQ, CONSTR_LANE, CONSTR_DISCS, NDISC, SCENE_MAX, default_discs, disc_rows,
+                   NRATE, default_rates, rate_rows, NFIELD, NFSRC, field_row, default_fields, field_rows,
+                   NSTATS, NPARAM, MpcConfig, default_config, default_params, param_rows, NBOUND,
+                   default_bounds, bound_rows, NCONSTR, default_constraints, constraint_rows, MpcError)
 from .solver import BatchedMPC, Track, TrafficLoopResult
 from .tracks import stadium_track, circle_track
 
-__all__ = ["BatchedMPC", "MpcConfig", "default_config", "MpcError", "MODEL_KINEMATIC",
-           "MODEL_PACEJKA", "WRAP_FLOOR", "WRAP_FMOD", "WRAP_IEEE", "CONSTR_NONE", "CONSTR_STATE_SQ",
-           "CONSTR_LANE", "CONSTR_DISCS", "NDISC", "SCENE_MAX", "default_discs", "disc_rows", "NRATE", "default_rates", "rate_rows", "NSTATS", "NPARAM", "default_params", "param_rows",
-           "NBOUND", "default_bounds", "bound_rows", "NCONSTR", "default_constraints", "constraint_rows",
-           "Track", "TrafficLoopResult", "stadium_track", "circle_track"]
+__all__ = ["BatchedMPC", "MpcConfig", "default_config", "MpcError", "MODEL_KINEMATIC", "MODEL_PACEJKA",
+           "WRAP_FLOOR", "WRAP_FMOD", "WRAP_IEEE", "CONSTR_NONE", "CONSTR_STATE_SQ", "CONSTR_LANE",
+           "CONSTR_DISCS", "NDISC", "SCENE_MAX", "default_discs", "disc_rows", "NRATE", "default_rates",
+           "rate_rows", "NFIELD", "NFSRC", "field_row", "default_fields", "field_rows", "NSTATS", "NPARAM",
+           "default_params", "param_rows", "NBOUND", "default_bounds", "bound_rows", "NCONSTR",
+           "default_constraints", "constraint_rows", "Track", "TrafficLoopResult", "stadium_track",
+           "circle_track"]

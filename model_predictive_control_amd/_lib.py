@@ -56,6 +56,7 @@ EXPORTS = [
     "mpc_default_constraints", "mpc_set_agent_constraints",
     "mpc_default_discs", "mpc_set_agent_discs", "mpc_discs_from_plans",
     "mpc_default_rates", "mpc_set_agent_rates",
+    "mpc_default_fields", "mpc_set_agent_fields", "mpc_fields_from_plans", "mpc_closed_loop_traffic_field",
     "mpc_opponents_from_plans", "mpc_closed_loop_traffic",
     "mpc_track_init", "mpc_track_windows", "mpc_track_locate", "mpc_track_select", "mpc_closed_loop_track",
 ]
@@ -65,6 +66,8 @@ NPARAM = 31     # MPC_NPARAM: doubles per row of the per-agent parameter table
 NBOUND = 4      # MPC_NBOUND: doubles per row of the per-agent bounds table, [u_lb[0], u_lb[1], u_ub[0], u_ub[1]]
 NCONSTR = 19    # MPC_NCONSTR: doubles per row of the per-agent constraint table
 NRATE = 4       # MPC_NRATE: doubles per row of the per-agent rate table, [w_d, w_delta, d_prev, delta_prev]
+NFIELD = 2      # MPC_NFIELD: sources of the risk field per stage (== NDISC: one opp [B, 2] serves both)
+NFSRC = 8       # MPC_NFSRC: doubles per source, [cx, cy, c, s, A, kx, ky, alpha]; a row of the field table is [N][NFIELD][NFSRC]
 NDISC = 2       # MPC_NDISC: keep-out discs per stage; a row of the disc table is [N][NDISC][3] = (cx, cy, r)
 SCENE_MAX = 64  # MPC_SCENE_MAX: agents per scene at most (mpc_opponents_from_plans, mpc_closed_loop_traffic)
 # columns of a constraint row, by field name (include/mpc_hip.h: mpc_set_agent_constraints)
@@ -186,6 +189,10 @@ def load():
     L.mpc_discs_from_plans.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.mpc_default_rates.argtypes = [cp, C.POINTER(C.c_double)]
     L.mpc_set_agent_rates.argtypes = [vp, vp, ci, vp, ci]
+    L.mpc_default_fields.argtypes = [cp, C.POINTER(C.c_double)]
+    L.mpc_set_agent_fields.argtypes = [vp, vp, ci, vp, ci]
+    L.mpc_fields_from_plans.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    L.mpc_closed_loop_traffic_field.argtypes = [vp, ci, ci, ci, ci, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mpc_opponents_from_plans.argtypes = [vp, ci, ci, ci, vp, vp, C.c_double, vp, vp, vp]
     L.mpc_closed_loop_traffic.argtypes = [vp, ci, ci, ci, ci, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mpc_step_lds_plan.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
@@ -380,6 +387,55 @@ def rate_rows(w_d, w_delta, u_prev=None):
         raise ValueError("rate_rows: u_prev must be finite")
     tab = np.empty((P, NRATE), dtype=np.float64)
     tab[:, 0], tab[:, 1], tab[:, 2:] = wd, wl, up
+    return tab
+
+
+def field_row(N):
+    """MPC_FIELD_ROW(N): doubles per row of the field table of a horizon of N stages."""
+    return NFIELD * NFSRC * int(N)
+
+
+def default_fields(cfg):
+    """mpc_default_fields: the row of the field table that says "no obstacle at any stage", float64 [field_row(N)] of
+    zeros."""
+    return _default_row("mpc_default_fields", field_row(cfg.N), cfg)
+
+
+def field_rows(centres, heading, A, sigma_x, sigma_y, alpha=0):
+    """A field table for BatchedMPC.set_agent_fields, on the host: float64 [P, N, NFIELD, NFSRC], sources
+    [cx, cy, cos heading, sin heading, A, 1 / (2 sigma_x^2), 1 / (2 sigma_y^2), alpha] (reshape(P, -1) is the table).
+    centres: [P, N, NFIELD, 2], or anything that broadcasts to it ([2]: the same standing point in every slot of every
+    stage).  heading, A, sigma_x, sigma_y, alpha: scalars or arrays that broadcast to [P, N, NFIELD]; A >= 0 (0: the
+    slot holds no source -- A = [0.3, 0] fills slot 0 alone), sigma > 0, everything finite.  Pure host code: usable
+    without a GPU."""
+    import numpy as np
+    c = np.asarray(centres, dtype=np.float64)
+    if c.ndim < 1 or c.shape[-1] != 2:
+        raise ValueError(f"field_rows: centres must end in a dimension of 2 (x, y), got {c.shape}")
+    if c.ndim > 4 or (c.ndim >= 2 and c.shape[-2] not in (1, NFIELD)):
+        raise ValueError(f"field_rows: centres must broadcast to (P, N, {NFIELD}, 2), got {c.shape}")
+    c = c.reshape((1,) * (4 - c.ndim) + c.shape)
+    others = [np.asarray(v, dtype=np.float64) for v in (heading, A, sigma_x, sigma_y, alpha)]
+    if any(v.ndim > 3 for v in others):
+        raise ValueError(f"field_rows: heading, A, sigma_x, sigma_y and alpha must broadcast to (P, N, {NFIELD})")
+    try:
+        shape = np.broadcast_shapes(c.shape[:3], (1, 1, NFIELD), *(v.shape for v in others))
+    except ValueError:
+        raise ValueError("field_rows: the arguments do not broadcast to one (P, N, NFIELD)") from None
+    if shape[2] != NFIELD:
+        raise ValueError(f"field_rows: {NFIELD} sources per stage, got {shape[2]}")
+    hd, Av, sx, sy, al = (np.broadcast_to(v, shape) for v in others)
+    for name, v in (("centres", c), ("heading", hd), ("A", Av), ("sigma_x", sx), ("sigma_y", sy), ("alpha", al)):
+        if not np.all(np.isfinite(v)):
+            raise ValueError(f"field_rows: {name} must be finite")
+    if np.any(Av < 0.0):
+        raise ValueError("field_rows: A must be >= 0")
+    if np.any(sx <= 0.0) or np.any(sy <= 0.0):
+        raise ValueError("field_rows: sigma_x and sigma_y must be > 0")
+    tab = np.empty(shape + (NFSRC,), dtype=np.float64)
+    tab[..., 0:2] = np.broadcast_to(c, shape + (2,))
+    tab[..., 2], tab[..., 3], tab[..., 4] = np.cos(hd), np.sin(hd), Av
+    tab[..., 5], tab[..., 6], tab[..., 7] = 1.0 / (2.0 * sx * sx), 1.0 / (2.0 * sy * sy), al
     return tab
 
 

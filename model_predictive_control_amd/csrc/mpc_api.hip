@@ -97,6 +97,16 @@ extern "C" int mpc_default_rates(const mpc_config *c, double *row)
     return MPC_OK;
 }
 
+static_assert(MPC_NFIELD == mpc::NFIELD && MPC_NFSRC == mpc::NFSRC, "row layout: include/mpc_hip.h and mpc_device.hpp");
+static_assert(MPC_NFIELD == MPC_NDISC, "one opp [B][2] of mpc_opponents_from_plans serves the discs and the fields");
+extern "C" int mpc_default_fields(const mpc_config *c, double *row)
+{
+    if (!c || !row) return fail(MPC_E_ARG, "mpc_default_fields: null argument");
+    if (c->N < 1 || c->N > MPC_MAX_N) return fail(MPC_E_ARG, "mpc_default_fields: horizon N out of range [1, 64]");
+    for (int i = 0; i < MPC_FIELD_ROW(c->N); i++) row[i] = 0.0;   // A = 0: no obstacle at any stage
+    return MPC_OK;
+}
+
 extern "C" int mpc_create(const mpc_config *cfg, int device, mpc_handle **out)
 {
     if (!cfg || !out) return fail(MPC_E_ARG, "mpc_create: null argument");
@@ -188,20 +198,21 @@ extern "C" int mpc_centerline_blocks(mpc_handle *h, const double *cl, int C, voi
     return MPC_OK;
 }
 
-// the handle's own one-row parameter and box tables and an index of B zeros (see mpc_handle::own_ptab)
+// the handle's own one-row parameter, box and rate tables and an index of B zeros (see mpc_handle::own_ptab)
 static int reserve_own_tables(mpc_handle *h, int B, const char *who)
 {
     if (B <= h->own_cap) return MPC_OK;
-    if (h->own_ptab) { HIPCHK(hipFree(h->own_ptab)); h->own_ptab = h->own_btab = nullptr; h->own_pidx = nullptr; h->own_cap = 0; }
+    if (h->own_ptab) { HIPCHK(hipFree(h->own_ptab)); h->own_ptab = h->own_btab = h->own_rtab = nullptr; h->own_pidx = nullptr; h->own_cap = 0; }
     const size_t cap = ((size_t)B + 63) & ~(size_t)63;
-    constexpr int ND = MPC_NPARAM + 1 + MPC_NBOUND;
+    constexpr int ND = MPC_NPARAM + 1 + MPC_NBOUND + MPC_NRATE;
     char *base = nullptr;
     if (hipMalloc((void **)&base, sizeof(double) * ND + sizeof(int32_t) * cap) != hipSuccess)
         return fail(MPC_E_ALLOC, std::string(who) + ": hipMalloc failed");
     double own[ND] = {0};
     (void)mpc_default_params(&h->cfg, own);
     (void)mpc_default_bounds(&h->cfg, own + MPC_NPARAM + 1);
-    h->own_ptab = (double *)base; h->own_btab = h->own_ptab + MPC_NPARAM + 1;
+    (void)mpc_default_rates(&h->cfg, own + MPC_NPARAM + 1 + MPC_NBOUND);
+    h->own_ptab = (double *)base; h->own_btab = h->own_ptab + MPC_NPARAM + 1; h->own_rtab = h->own_btab + MPC_NBOUND;
     h->own_pidx = (int32_t *)(base + sizeof(double) * ND); h->own_cap = (int)cap;
     HIPCHK(hipMemcpy(base, own, sizeof own, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(h->own_pidx, 0, sizeof(int32_t) * cap));
@@ -258,6 +269,21 @@ static int rate_row_rule(const mpc_handle *, const double *r, const std::string 
     return MPC_OK;
 }
 
+// risk fields: every value finite, no negative height or width coefficient, and a skew only where the Gaussian along the
+// frame bounds it (alpha != 0 with kx = 0 would make E = alpha a unbounded below)
+static int field_row_rule(const mpc_handle *h, const double *r, const std::string &where)
+{
+    for (int i = 0; i < h->cfg.N * MPC_NFIELD; i++) {
+        const double *q = r + (size_t)MPC_NFSRC * i;
+        const std::string which = ", stage " + std::to_string(i / MPC_NFIELD) + ", source " + std::to_string(i % MPC_NFIELD);
+        for (int f = 0; f < MPC_NFSRC; f++)
+            if (!std::isfinite(q[f])) return fail(MPC_E_ARG, where + which + ": (cx, cy, c, s, A, kx, ky, alpha) must be finite");
+        if (!(q[4] >= 0.0) || !(q[5] >= 0.0) || !(q[6] >= 0.0)) return fail(MPC_E_ARG, where + which + ": A, kx and ky must not be negative");
+        if (q[7] != 0.0 && !(q[5] > 0.0)) return fail(MPC_E_ARG, where + which + ": a skew (alpha != 0) needs kx > 0");
+    }
+    return MPC_OK;
+}
+
 // Binds (table != NULL) or unbinds the per-agent table of one kind.  The rows are checked once, here, through a
 // synchronous copy (binding is not on the hot path; rows rewritten in place later are the caller's to keep valid).
 // Nothing else is done: the kernels read the caller's memory at every call.  The box and constraint forms of some
@@ -276,7 +302,15 @@ static int bind_agent_table(mpc_handle *h, TableKind kind, const double *table, 
                                                   "there is no constraint data to bind (mpc_set_agent_discs)");
     if (kind == TAB_DISCS && h->cfg.constr_mode != MPC_CONSTR_DISCS)
         return fail(MPC_E_ARG, std::string(who) + ": the handle's constr_mode is not MPC_CONSTR_DISCS");
-    // a rate table and a constraint table together would need kernel forms that take both: whichever comes second is refused
+    if (kind == TAB_FIELDS && h->cfg.constr_mode == MPC_CONSTR_DISCS)
+        return fail(MPC_E_ARG, std::string(who) + ": the handle's constraints are keep-out discs (constr_mode MPC_CONSTR_DISCS): there an "
+                                                  "obstacle is a disc (mpc_set_agent_discs)");
+    // a field table and a constraint table together would need kernel forms that take both: whichever comes second is refused
+    for (const TableKind other : {TAB_CONSTR, TAB_FIELDS})
+        if ((kind == TAB_FIELDS || kind == TAB_CONSTR) && kind != other && h->tab[other].table)
+            return fail(MPC_E_ARG, std::string(who) + ": a " + k_tables[other].noun + " table is bound (" + k_tables[other].setter +
+                                   "): a field table and a constraint table cannot be bound together");
+    // ... and so would a rate table and a constraint table
     if ((kind == TAB_RATES && h->tab[TAB_CONSTR].table) || (kind == TAB_CONSTR && h->tab[TAB_RATES].table))
         return fail(MPC_E_ARG, std::string(who) + ": a " + k_tables[kind == TAB_RATES ? TAB_CONSTR : TAB_RATES].noun + " table is bound (" +
                                k_tables[kind == TAB_RATES ? TAB_CONSTR : TAB_RATES].setter + "): a rate table and a constraint table "
@@ -320,6 +354,10 @@ extern "C" int mpc_set_agent_rates(mpc_handle *h, const double *table, int P, co
 {
     return bind_agent_table(h, TAB_RATES, table, P, index, B, rate_row_rule);
 }
+extern "C" int mpc_set_agent_fields(mpc_handle *h, const double *table, int P, const int32_t *index, int B)
+{
+    return bind_agent_table(h, TAB_FIELDS, table, P, index, B, field_row_rule);
+}
 // The closed loops carry u_{-1} themselves: with a rate table bound they need a row per agent (P == B; index 0 .. B-1 is
 // the caller's to ensure, as with the traffic loop's disc table) ...
 static int check_rate_rows(const mpc_handle *h, int B, const std::string &who)
@@ -348,6 +386,20 @@ extern "C" int mpc_discs_from_plans(mpc_handle *h, int B, const double *X, const
     const size_t words = (size_t)B * h->cfg.N * MPC_NDISC;
     hipLaunchKernelGGL(discs_from_plans_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, h->cfg.N,
                        h->dc.nx, X, opp, radius, table);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
+// The risk fields of everybody's opponents from everybody's plans (fields_from_plans_kernel), asynchronous
+extern "C" int mpc_fields_from_plans(mpc_handle *h, int B, const double *X, const int32_t *opp, const double *shape,
+                                     double *table, void *stream)
+{
+    int rc = check_common(h, B, "mpc_fields_from_plans"); if (rc) return rc;
+    if (B == 0) return MPC_OK;
+    if (!X || !opp || !shape || !table) return fail(MPC_E_ARG, "mpc_fields_from_plans: null buffer");
+    const size_t words = (size_t)B * h->cfg.N * MPC_NFIELD;
+    hipLaunchKernelGGL(fields_from_plans_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, h->cfg.N,
+                       h->dc.nx, X, opp, shape, table);
     HIPCHK(hipGetLastError());
     return MPC_OK;
 }
@@ -444,7 +496,7 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     if (!x0 || !cl || !U || !psi) return fail(MPC_E_ARG, "mpc_eval_cost_grad: null buffer");
     const DevCfg &c = h->dc;
     if (c.m && (!y || !Sigma)) return fail(MPC_E_ARG, "mpc_eval_cost_grad: y and Sigma are required when m > 0");
-    rc = check_tables(h, B, "mpc_eval_cost_grad", READS_PARAMS | READS_CONSTR | READS_DISCS | READS_RATES, true); if (rc) return rc;
+    rc = check_tables(h, B, "mpc_eval_cost_grad", READS_PARAMS | READS_CONSTR | READS_DISCS | READS_RATES | READS_FIELDS, true); if (rc) return rc;
     rc = reserve(h, B); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     // direct mode: the kernel reads and writes the caller's agent-major buffers in place
@@ -458,6 +510,7 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     w.ctab = h->tab[TAB_CONSTR].table; w.cidx = h->tab[TAB_CONSTR].idx;
     w.dtab = h->tab[TAB_DISCS].table; w.didx = h->tab[TAB_DISCS].idx;
     w.rtab = h->tab[TAB_RATES].table; w.ridx = h->tab[TAB_RATES].idx;
+    w.ftab = h->tab[TAB_FIELDS].table; w.fidx = h->tab[TAB_FIELDS].idx;
     if (wave_path) launch_solo_eval(h, w, s, grad ? 1 : 0);
     else launch_eval(h, w, s, nullptr, nullptr, grad ? B : 0, grad ? 0 : B);
     HIPCHK(hipGetLastError());
@@ -534,6 +587,7 @@ static int solve_core(mpc_handle *h, int B, const double *x0, const double *cl, 
     w.ctab = h->tab[TAB_CONSTR].table; w.cidx = rows_of(TAB_CONSTR);
     w.dtab = h->tab[TAB_DISCS].table; w.didx = rows_of(TAB_DISCS);
     w.rtab = h->tab[TAB_RATES].table; w.ridx = rows_of(TAB_RATES);
+    w.ftab = h->tab[TAB_FIELDS].table; w.fidx = rows_of(TAB_FIELDS);
     w.xe = w.ws_xe; w.ge = w.ws_ge; w.yhe = w.ws_yhe; w.Sig = w.ws_Sig;
     rc = run_solver(h, s); if (rc) return rc;
     if (stats) hipLaunchKernelGGL(stats_kernel, grid_for(B, 256), dim3(256), 0, s, w, stats);
@@ -656,7 +710,7 @@ static int solve_active_impl(mpc_handle *h, int B, const int32_t *active, const 
     r.cl_index = cl_index; r.pidx = h->params().idx;
     r.xs = e.xs; r.Us = e.Us; r.lams = e.lams; r.stats_s = e.stats_s; r.cis = e.cis; r.pis = e.pis;
     hipLaunchKernelGGL(active_gather_kernel, grows, dim3(EV_BLK), 0, s, r);
-    const AgentIdx gathered = {{e.pis, e.bis, e.kis, e.dis, e.ris}};   // (the parameter rows ride in the gather above)
+    const AgentIdx gathered = {{e.pis, e.bis, e.kis, e.dis, e.ris, e.fis}};   // (the parameter rows ride in the gather above)
     for (int k = TAB_BOX; k < TAB_KINDS; k++)
         if (h->tab[k].table)
             hipLaunchKernelGGL(active_index_kernel, gblk, dim3(EV_BLK), 0, s, e.list, e.count, h->tab[k].idx, const_cast<int32_t *>(gathered.of[k]));
@@ -927,29 +981,27 @@ extern "C" int mpc_opponents_from_plans(mpc_handle *h, int B, int G, int Nst, co
 }
 
 // Traffic closed loop: per step everybody's plans (mpc_rollout), the nearest opponents of every agent on them, their
-// discs into the bound table (mpc_discs_from_plans), the solve, the plant step of mpc_closed_loop, and the clearance
-// realised on the new states.  Every step is what the public call of that name launches; control returns to the host
-// inside the solve alone.
-extern "C" int mpc_closed_loop_traffic(mpc_handle *h, int B, int T, int shift, int G, const double *radius, double reach,
-                                       double *x, const double *cl, const int32_t *cl_index, double *U, double *lambda,
-                                       double *table, double *traj_x, double *traj_u, int32_t *traj_opp, double *traj_clear,
-                                       int32_t *fail_count, double *stats, void *stream)
+// discs into the bound table (mpc_discs_from_plans) -- or their risk fields (mpc_fields_from_plans:
+// mpc_closed_loop_traffic_field) -- the solve, the plant step of mpc_closed_loop, and the clearance realised on the new
+// states.  Every step is what the public call of that name launches; control returns to the host inside the solve alone.
+// One body for the two loops: `kind` is the table the loop rewrites (TAB_DISCS or TAB_FIELDS), `gather` step 3.
+template <class Gather>
+static int closed_loop_traffic_impl(const std::string &who, TableKind kind, mpc_handle *h, int B, int T, int shift, int G, const double *radius,
+                                    double reach, double *x, const double *cl, const int32_t *cl_index, double *U, double *lambda,
+                                    double *table, double *traj_x, double *traj_u, int32_t *traj_opp, double *traj_clear,
+                                    int32_t *fail_count, double *stats, void *stream, Gather gather)
 {
-    const std::string who = "mpc_closed_loop_traffic";
-    int rc = check_scene_args(who, B, G, reach, radius); if (rc) return rc;
-    if (T < 0) return fail(MPC_E_ARG, who + ": negative T");
-    rc = check_common(h, B, who.c_str()); if (rc) return rc;
-    if (h->cfg.constr_mode != MPC_CONSTR_DISCS) return fail(MPC_E_ARG, who + ": the handle's constr_mode is not MPC_CONSTR_DISCS");
-    const BoundTable &dt = h->tab[TAB_DISCS];
-    rc = check_tables(h, B, who.c_str(), READS_ALL, true); if (rc) return rc;
+    const BoundTable &dt = h->tab[kind];
+    int rc = check_tables(h, B, who.c_str(), READS_ALL, true); if (rc) return rc;
     if (!table || table != dt.table)
-        return fail(MPC_E_ARG, who + ": table must be the disc table that is bound (mpc_set_agent_discs): the loop rewrites it in place");
+        return fail(MPC_E_ARG, who + ": table must be the " + k_tables[kind].noun + " table that is bound (" + k_tables[kind].setter +
+                               "): the loop rewrites it in place");
     if (dt.rows != B)
-        return fail(MPC_E_ARG, who + ": the bound disc table has " + std::to_string(dt.rows) + " rows, the loop needs one per agent (P == B = " +
-                               std::to_string(B) + ", index 0 .. B-1)");
+        return fail(MPC_E_ARG, who + ": the bound " + k_tables[kind].noun + " table has " + std::to_string(dt.rows) +
+                               " rows, the loop needs one per agent (P == B = " + std::to_string(B) + ", index 0 .. B-1)");
     rc = check_rate_rows(h, B, who); if (rc) return rc;
     if (B == 0 || T == 0) return MPC_OK;
-    if (!x || !cl || !U || !lambda) return fail(MPC_E_ARG, who + ": null buffer");
+    if (!x || !cl || !U || (h->dc.m && !lambda)) return fail(MPC_E_ARG, who + ": null buffer");
     rc = reserve_traffic(h, B); if (rc) return rc;
     const DevCfg &c = h->dc;
     mpc_handle::TrafficBufs &tr = h->tr;
@@ -963,7 +1015,7 @@ extern "C" int mpc_closed_loop_traffic(mpc_handle *h, int B, int T, int shift, i
         rc = mpc_rollout(h, B, c.N, x, U, tr.X, stream); if (rc) return rc;
         launch_opponents(h, s, B, G, c.N, tr.X, radius, reach, tr.opp, traj_opp ? traj_opp + (size_t)t * MPC_NDISC : nullptr,
                          (size_t)T * MPC_NDISC, nullptr, 0, 0);
-        rc = mpc_discs_from_plans(h, B, tr.X, tr.opp, radius, table, stream); if (rc) return rc;
+        rc = gather(tr.X, tr.opp); if (rc) return rc;
         rc = mpc_solve_batch(h, B, x, cl, cl_index, U, lambda, st, stream); if (rc) return rc;
         launch_rate_prev(h, s, B, U, nullptr, nullptr);
         with_model_table(h, h->plant_rows(), [&](auto MODEL, auto PA, auto... pt) {
@@ -975,6 +1027,40 @@ extern "C" int mpc_closed_loop_traffic(mpc_handle *h, int B, int T, int shift, i
     }
     HIPCHK(hipGetLastError());
     return bounded_sync(h, s, who.c_str());
+}
+
+extern "C" int mpc_closed_loop_traffic(mpc_handle *h, int B, int T, int shift, int G, const double *radius, double reach,
+                                       double *x, const double *cl, const int32_t *cl_index, double *U, double *lambda,
+                                       double *table, double *traj_x, double *traj_u, int32_t *traj_opp, double *traj_clear,
+                                       int32_t *fail_count, double *stats, void *stream)
+{
+    const std::string who = "mpc_closed_loop_traffic";
+    int rc = check_scene_args(who, B, G, reach, radius); if (rc) return rc;
+    if (T < 0) return fail(MPC_E_ARG, who + ": negative T");
+    rc = check_common(h, B, who.c_str()); if (rc) return rc;
+    if (h->cfg.constr_mode != MPC_CONSTR_DISCS) return fail(MPC_E_ARG, who + ": the handle's constr_mode is not MPC_CONSTR_DISCS");
+    return closed_loop_traffic_impl(who, TAB_DISCS, h, B, T, shift, G, radius, reach, x, cl, cl_index, U, lambda, table, traj_x, traj_u,
+                                    traj_opp, traj_clear, fail_count, stats, stream, [&](const double *X, const int32_t *opp) {
+                                        return mpc_discs_from_plans(h, B, X, opp, radius, table, stream);
+                                    });
+}
+
+extern "C" int mpc_closed_loop_traffic_field(mpc_handle *h, int B, int T, int shift, int G, const double *radius, const double *shape,
+                                             double reach, double *x, const double *cl, const int32_t *cl_index, double *U,
+                                             double *lambda, double *table, double *traj_x, double *traj_u, int32_t *traj_opp,
+                                             double *traj_clear, int32_t *fail_count, double *stats, void *stream)
+{
+    const std::string who = "mpc_closed_loop_traffic_field";
+    int rc = check_scene_args(who, B, G, reach, radius); if (rc) return rc;
+    if (T < 0) return fail(MPC_E_ARG, who + ": negative T");
+    if (!shape) return fail(MPC_E_ARG, who + ": null shape");
+    rc = check_common(h, B, who.c_str()); if (rc) return rc;
+    if (h->cfg.constr_mode == MPC_CONSTR_DISCS)
+        return fail(MPC_E_ARG, who + ": the handle's constr_mode is MPC_CONSTR_DISCS: there an obstacle is a disc (mpc_closed_loop_traffic)");
+    return closed_loop_traffic_impl(who, TAB_FIELDS, h, B, T, shift, G, radius, reach, x, cl, cl_index, U, lambda, table, traj_x, traj_u,
+                                    traj_opp, traj_clear, fail_count, stats, stream, [&](const double *X, const int32_t *opp) {
+                                        return mpc_fields_from_plans(h, B, X, opp, shape, table, stream);
+                                    });
 }
 
 extern "C" int mpc_last_speculation(mpc_handle *h, int64_t *issued, int64_t *used)

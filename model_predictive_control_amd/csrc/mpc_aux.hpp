@@ -238,7 +238,7 @@ __global__ void __launch_bounds__(64) plant_step_kernel(const DevCfg c_, int B, 
 }
 
 
-// device-math probe (test only): op 0 sin, 1 cos, 2 atan, 3 atan2(a, b), 4 tan
+// device-math probe (test only): op 0 sin, 1 cos, 2 atan, 3 atan2(a, b), 4 tan, 5 exp (the out-of-line one of field_term)
 __global__ void math_probe_kernel(int n, int op, const double *__restrict__ a, const double *__restrict__ b,
                                   double *__restrict__ out)
 {
@@ -250,6 +250,7 @@ __global__ void math_probe_kernel(int n, int op, const double *__restrict__ a, c
     case 1: r = m_sincos(a[i]).c; break;
     case 2: r = m_atan(a[i]); break;
     case 3: r = m_atan2(a[i], b[i]); break;
+    case 5: r = ocml_exp(a[i]); break;
     default: r = m_tan(a[i]); break;
     }
     out[i] = r;

@@ -174,6 +174,17 @@ MPC_DEV double rate_term(const StageRate &r, double d, double dl, bool is_g, dou
     return t0 * e0 + t1 * e1;
 }
 
+// mpc_set_agent_fields: a table [P][N][NFIELD][NFSRC] of soft obstacle potentials in device memory and one row index per
+// agent -- like the discs, data that varies with the stage.  One source is [cx, cy, c, s, A, kx, ky, alpha]: a skewed
+// anisotropic Gaussian of height A around (cx, cy) in the frame whose cosine and sine are (c, s), kx = 1 / (2 sigma_x^2)
+// along the frame and ky across it, alpha the skew along it.  Stage k's cost gets the sum of its NFIELD sources at the
+// state at the end of the stage (field_term, below the math section: it calls the device exp).  The sixteen doubles of a
+// stage never enter a DevCfg and are not passed by value either: the field forms of the kernels that evaluate the cost
+// (trailing FieldTab argument, behind the RateTab: mpc_solver.hpp) hand stage_record the address of the stage's entry,
+// and field_term loads a source's eight doubles where it evaluates it.
+constexpr int NFIELD = 2, NFSRC = 8;
+struct StageField { const double *src; };   // [NFIELD][NFSRC]: the entry of the agent's row for this stage
+
 // ---------------------------------------------------------------------------------- math
 // The OCML double-precision transcendentals are full-range (Payne-Hanek reduction, dozens of
 // 64-bit literals each) and dominate this kernel's instruction count.  The angles of this problem
@@ -187,7 +198,41 @@ __device__ __noinline__ SinCos ocml_sincos(double x) { SinCos r; ::sincos(x, &r.
 __device__ __noinline__ double m_tan(double x) { return ::tan(x); }
 __device__ __noinline__ double ocml_fmod(double a, double b) { return ::fmod(a, b); }
 __device__ __noinline__ double ocml_atan2(double y, double x) { return ::atan2(y, x); }
+__device__ __noinline__ double ocml_exp(double x) { return ::exp(x); }
 __device__ __noinline__ double ocml_remainder(double a, double b) { return ::remainder(a, b); }
+
+// The risk field of one stage: its NFIELD sources at (x, y), the position at the end of the stage, added to the stage cost
+// L one by one (j = 0, 1) and -- for a gradient request -- to the stage's state gradient (xb0, xb1) = dL/d(x, y); every
+// operation rounded on its own (one function for the four evaluation routes: the same request gets the same bits
+// whichever serves it; one out-of-line exp, full range):
+//     dx = x - cx,  dy = y - cy,  a = (c dx) + (s dy),  l = (c dy) - (s dx)
+//     E = ((kx a) a + (ky l) l) + alpha a,  V = A exp(-E),  L = L + V
+//     ga = -(V (2 (kx a) + alpha)),  gl = -(V (2 (ky l))),  xb0 = xb0 + ((c ga) - (s gl)),  xb1 = xb1 + ((s ga) + (c gl))
+// A source with A == 0 is skipped by a branch: it adds nothing, not even a signed zero ("no obstacle at this stage"), so
+// a table of zeros gives the bits of the rate form alone.  The eight doubles are loaded inside the loop, one source at a
+// time, after everything stage_cost needed is dead.
+MPC_DEV void field_term(const StageField &f, double x, double y, bool is_g, double &L, double &xb0, double &xb1)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int j = 0; j < NFIELD; j++) {
+        const double *__restrict__ p = f.src + j * NFSRC;
+        const double A = p[4];
+        if (A == 0.0) continue;
+        const double c = p[2], s = p[3], kx = p[5], ky = p[6], alpha = p[7];
+        const double dx = x - p[0], dy = y - p[1];
+        const double a = (c * dx) + (s * dy), l = (c * dy) - (s * dx);
+        const double ka = kx * a, kl = ky * l;
+        const double E = ((ka * a) + (kl * l)) + (alpha * a);
+        const double V = A * ocml_exp(-E);
+        L = L + V;
+        if (is_g) {
+            const double ga = -(V * ((2.0 * ka) + alpha)), gl = -(V * (2.0 * kl));
+            xb0 = xb0 + ((c * ga) - (s * gl));
+            xb1 = xb1 + ((s * ga) + (c * gl));
+        }
+    }
+}
 
 #ifdef MPC_ATAN_OUTLINE
 #define MPC_ATAN_FN __device__ __noinline__

@@ -247,4 +247,33 @@ __global__ void __launch_bounds__(256) discs_from_plans_kernel(int B, int N, int
     out[0] = cx; out[1] = cy; out[2] = r;
 }
 
+// mpc_fields_from_plans: table[b][k][j] = [cx, cy, c, s, A, kx, ky, alpha] for o = opp[b][j] -- the opponent's planned
+// position X[o][k][0..1], the device sincos of its planned heading X[o][k][2], its shape[o][0..2] as an obstacle, and the
+// skew shape[o][3] * (X[b][k][3] - X[o][k][3]) (the subtraction and the product each rounded on its own) -- eight zeros
+// where there is no such agent (o < 0 or o >= B).  One thread per (agent, stage, source).
+__global__ void __launch_bounds__(256) fields_from_plans_kernel(int B, int N, int nx, const double *__restrict__ X,
+                                                                const int *__restrict__ opp, const double *__restrict__ shape,
+                                                                double *__restrict__ table)
+{
+#pragma clang fp contract(off)
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)B * N * NFIELD) return;
+    const int j = (int)(t % NFIELD);
+    const size_t bk = t / NFIELD;
+    const int k = (int)(bk % N), b = (int)(bk / N);
+    const int o = opp[(size_t)b * NFIELD + j];
+    double v[NFSRC] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (o >= 0 && o < B) {
+        const double *__restrict__ xo = X + ((size_t)o * N + k) * nx;
+        const double *__restrict__ so = shape + (size_t)o * 4;
+        const SinCos sc = m_sincos(xo[2]);
+        const double dv = X[((size_t)b * N + k) * nx + 3] - xo[3];
+        v[0] = xo[0]; v[1] = xo[1]; v[2] = sc.c; v[3] = sc.s;
+        v[4] = so[0]; v[5] = so[1]; v[6] = so[2]; v[7] = so[3] * dv;
+    }
+    double *out = table + t * NFSRC;
+#pragma unroll
+    for (int i = 0; i < NFSRC; i++) out[i] = v[i];
+}
+
 } // namespace mpc

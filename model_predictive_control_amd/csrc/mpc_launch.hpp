@@ -6,8 +6,9 @@
 // the constraint forms exist beside the parameter form alone (K1b, the wave evaluation), beside the parameter and box
 // forms alone (the persistent kernel) and for constrained problems alone (the step kernel); the disc forms stand where
 // the constraint forms stand, except that the step kernel has none (it reads no discs); the rate forms (RateTab alone, and
-// DiscTab + RateTab) stand where the disc forms stand, never with the lookahead.  Where a form needs a table
-// the caller has not bound, with_own_params / with_own_box put the handle's own one-row table in its place.
+// DiscTab + RateTab) stand where the disc forms stand, never with the lookahead; the field forms are RateTab + FieldTab
+// alone, where the rate forms stand.  Where a form needs a table the caller has not bound, with_own_params /
+// with_own_box / with_own_rates put the handle's own one-row table in its place.
 #pragma once
 #include "mpc_handle.hpp"
 
@@ -42,6 +43,9 @@ static WorkspacePA with_own_params(const mpc_handle *h, const WorkspaceHost &w)
 // ... and the box as the constraint form of the persistent kernel takes it: it exists together with the box form alone,
 // so without a bounds table of the caller's it runs on the handle's own one-row box table (mpc_handle::own_btab)
 static BoxTab with_own_box(const mpc_handle *h, const WorkspaceHost &w) { return w.btab ? w.box() : BoxTab{h->own_btab, h->own_pidx}; }
+// ... and the rates as the field forms take them: they exist behind the rate form alone, so without a rate table of the
+// caller's they run on the handle's own one-row table of zeros (mpc_handle::own_rtab: zero weights change no bit)
+static RateTab with_own_rates(const mpc_handle *h, const WorkspaceHost &w) { return w.rtab ? w.rate() : RateTab{h->own_rtab, h->own_pidx}; }
 
 // How the step kernel and the persistent kernel read an agent's L-BFGS history -- f(int_c<NE>, int_c<MC>), the two
 // kernels' template arguments (results do not depend on the choice).  NE: elements per lane, 1 up to n = 64 and 2
@@ -108,6 +112,11 @@ static bool launch_eval_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
                     hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, ConTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
                                        with_own_params(h, w), counts, nG, nC, desc, w.con());
                 });
+            else if (w.ftab)     // a field table is bound: the field form of K1b, behind the rate form (here and below)
+                with_flag(shared, [&](auto SH) {
+                    hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, RateTab, FieldTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
+                                       with_own_params(h, w), counts, nG, nC, desc, with_own_rates(h, w), w.field());
+                });
             else if (w.rtab)     // a rate table is bound: the rate form of K1b, beside the disc form where discs are bound too (here and below)
                 with_flags(shared, w.dtab != nullptr, [&](auto SH, auto DA) {
                     if constexpr (DA())
@@ -138,6 +147,11 @@ static bool launch_eval_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
         with_flag(shared, [&](auto SH) {
             hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, ConTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
                                with_own_params(h, w), counts, nG, nC, nblk, w.con());
+        });
+    else if (w.ftab)
+        with_flag(shared, [&](auto SH) {
+            hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, RateTab, FieldTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
+                               with_own_params(h, w), counts, nG, nC, nblk, with_own_rates(h, w), w.field());
         });
     else if (w.rtab)
         with_flags(shared, w.dtab != nullptr, [&](auto SH, auto DA) {
@@ -176,6 +190,14 @@ static void launch_solo_eval(mpc_handle *h, const WorkspaceHost &w, hipStream_t 
             const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
             hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, ConTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
                                want_grad, w.con());
+        });
+        return;
+    }
+    if (w.ftab) {
+        with_model(c.model, [&](auto MODEL) {
+            const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
+            hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, RateTab, FieldTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
+                               want_grad, with_own_rates(h, w), w.field());
         });
         return;
     }
@@ -323,6 +345,12 @@ static void launch_solo_t(mpc_handle *h, const WorkspaceHost &v, hipStream_t s, 
     if (v.ctab) {
         hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, ConTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
                            with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), v.con());
+        return;
+    }
+    // v.ftab: a field table is bound, the field form, behind the rate form (the caller's rate table or the handle's zeros)
+    if (v.ftab) {
+        hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, RateTab, FieldTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
+                           with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), with_own_rates(h, v), v.field());
         return;
     }
     // v.rtab: a rate table is bound, the rate form, on the disc form's terms and beside it where discs are bound too

@@ -72,6 +72,7 @@ struct SoloClk { long long roll = 0, recs = 0, adj = 0; };
 // DS: empty, or the disc table (the disc forms: one trailing DiscTab) -- lane k loads the discs of its stage from the
 // agent's row, whose address is wave-uniform -- and / or the rate table (the rate forms: a trailing RateTab, last) -- lane k
 // takes u_{k-1} and u_{k+1} from the row it evaluates (`row`: xe, or xe2 on the speculative half), u_{-1} from the table
+// -- and, behind the RateTab, the field table (the field forms) -- lane k hands on the address of its stage's sources
 template <int MODEL, class... DS>
 __device__ __forceinline__ void solo_eval(const DevCfg &c, const Workspace &w, int a, int lane, int req,
                                           double *traj, double *rec SOLO_CLK_ARG, const DS &...ds)
@@ -136,8 +137,11 @@ __device__ __forceinline__ void solo_eval(const DevCfg &c, const Workspace &w, i
         if (is_g) stage_sens_record<MODEL>(c, xs, xe, d, dl, put);
         Geom g;
         stage_geom(c, w, clp, w.cl_index ? w.cl_index[a] : 0, xe[0], xe[1], g);
-        constexpr bool DA = has_tab<DiscTab, DS...>, RA = has_tab<RateTab, DS...>;
-        if constexpr (DA && RA)
+        constexpr bool DA = has_tab<DiscTab, DS...>, RA = has_tab<RateTab, DS...>, FA = has_tab<FieldTab, DS...>;
+        if constexpr (FA)
+            stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_rate_uniform(pack_get<RateTab>(ds...), a, hl, N, row),
+                                stage_field_uniform(pack_get<FieldTab>(ds...), a, hl, N));
+        else if constexpr (DA && RA)
             stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_discs_uniform(pack_get<DiscTab>(ds...), a, hl, N),
                                 stage_rate_uniform(pack_get<RateTab>(ds...), a, hl, N, row));
         else if constexpr (RA)
@@ -251,7 +255,7 @@ __global__ void __launch_bounds__(64, 1) solo_eval_kernel(const DevCfg c_, const
     // constraint row, the same way)
     DevCfg cm_;
     if constexpr (PA) { cm_ = c_; agent_cfg_uniform(cm_, w.ptab, w.pidx, blockIdx.x); }
-    // the disc and rate forms (CT = DiscTab, RateTab or both): the tables go on to the evaluation
+    // the disc, rate and field forms (CT = DiscTab, RateTab, both, or RateTab + FieldTab): the tables go on to the evaluation
     constexpr bool DA = has_tab<DiscTab, CT...> || has_tab<RateTab, CT...>;
     if constexpr (has_tab<ConTab, CT...>) agent_con_uniform(cm_, ct..., blockIdx.x);
     const DevCfg &c = PA ? cm_ : c_;
@@ -429,6 +433,8 @@ template <int MODEL> struct SoloOcc { static constexpr int WPS = MODEL == KIN ? 
 // BT = (BoxTab, RateTab) or (BoxTab, DiscTab, RateTab): the rate forms (mpc_set_agent_rates), on the disc form's terms --
 // the evaluations add the move penalty of the agent's row; the state machine is what it is without them.  Never with the
 // lookahead (results do not depend on it).
+// BT = (BoxTab, RateTab, FieldTab): the field form (mpc_set_agent_fields), on the rate form's terms -- the evaluations add
+// the risk field of the agent's row, stage by stage.
 template <int MODEL, int NE, int MC, bool LA = false, bool PA = false, class... BT>
 __global__ void __launch_bounds__(64 * SOLO_WAVES, SoloOcc<MODEL>::WPS)
 solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int *__restrict__ ctr,
@@ -438,6 +444,8 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
     static_assert(!BA || PA, "the box form of the persistent kernel exists in the per-agent-parameter form alone");
     static_assert((!CA && !DA) || !LA, "the lookahead is an unconstrained problem's: it has no constraint or disc form");
     static_assert(!RA || !LA, "the rate forms run without the lookahead");
+    constexpr bool FA = has_tab<FieldTab, BT...>;
+    static_assert(!FA || (RA && !DA && !CA), "the field forms are <..., BoxTab, RateTab, FieldTab> alone");
     using BOX = BoxOf<BA, LaneBox>;
     using CON = ConOf<CA, RowCon>;
     extern __shared__ double s_solo[];
@@ -504,14 +512,16 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
             if ((req & (REQ_GRAD | REQ_COST)) == 0) break;              // uniform: the agent is done
 #if MPC_DEV_STAMP == 5
             t_adv += __builtin_amdgcn_s_memrealtime() - ta;
-            if constexpr (DA && RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...));
+            if constexpr (FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...));
+            else if constexpr (DA && RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...));
             else if constexpr (RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk, pack_get<RateTab>(bt...));
             else if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk, pack_get<DiscTab>(bt...));
             else
             solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk);
             ntrip++;
 #else
-            if constexpr (DA && RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...));
+            if constexpr (FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...));
+            else if constexpr (DA && RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...));
             else if constexpr (RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, pack_get<RateTab>(bt...));
             else if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, pack_get<DiscTab>(bt...));
             else

@@ -179,6 +179,25 @@ __device__ __forceinline__ StageRate stage_rate_uniform(const RateTab &t, int a,
     return stage_rate_from(t.rtab + (size_t)ri * NRATE, k, N, [=](int i) { return row[2 * (k - 1) + i]; },
                            [=](int i) { return row[2 * (k + 1) + i]; });
 }
+// The field table of mpc_set_agent_fields, as the field forms of the kernels receive it: the LAST trailing argument, behind
+// the RateTab -- the field forms are <..., RateTab, FieldTab> alone (no cross product: without a rate table of the
+// caller's the host puts the handle's own one-row table of zero weights in its place, with_own_rates in mpc_launch.hpp,
+// and zero weights change no bit).  Never beside a DiscTab or a ConTab: the binder refuses both.
+struct FieldTab {
+    const double *ftab;                            // [P][N][NFIELD][NFSRC] caller's table
+    const int *fidx;                               // [B]                   caller's row index per agent
+};
+// the address of stage k's sources in agent a's row: a different agent in every lane ...
+__device__ __forceinline__ StageField stage_field(const FieldTab &t, int a, int k, int N)
+{
+    return StageField{t.ftab + ((size_t)t.fidx[a] * N + k) * (NFIELD * NFSRC)};
+}
+// ... one agent per wave: the row is wave-uniform, lane k takes its stage
+__device__ __forceinline__ StageField stage_field_uniform(const FieldTab &t, int a, int k, int N)
+{
+    const int row = __builtin_amdgcn_readfirstlane(t.fidx[a]);
+    return StageField{t.ftab + (size_t)row * N * (NFIELD * NFSRC) + (size_t)k * (NFIELD * NFSRC)};
+}
 // which table a kernel's trailing pack holds
 template <class A, class B> struct SameTab { static constexpr bool v = false; };
 template <class A> struct SameTab<A, A> { static constexpr bool v = true; };

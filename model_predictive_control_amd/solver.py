@@ -62,7 +62,8 @@ _AGENT_TABLES = {"params": _AgentTable(_lib.NPARAM, 0, "mpc_set_agent_params", T
                  "bounds": _AgentTable(_lib.NBOUND, 0, "mpc_set_agent_bounds", False),
                  "constraints": _AgentTable(_lib.NCONSTR, 0, "mpc_set_agent_constraints", False),
                  "discs": _AgentTable(0, 3 * _lib.NDISC, "mpc_set_agent_discs", False),
-                 "rates": _AgentTable(_lib.NRATE, 0, "mpc_set_agent_rates", False)}
+                 "rates": _AgentTable(_lib.NRATE, 0, "mpc_set_agent_rates", False),
+                 "fields": _AgentTable(0, _lib.NFIELD * _lib.NFSRC, "mpc_set_agent_fields", False)}
 
 
 class BatchedMPC:
@@ -299,6 +300,45 @@ class BatchedMPC:
                              f"needs one row per agent (P == B = {B}, index = arange(B))")
         if not torch.equal(index, torch.arange(B, dtype=torch.int32, device=index.device)):
             raise ValueError("the bound rate table's index is not arange(B): a closed loop writes the applied input into row b of agent b")
+
+    def set_agent_fields(self, table, index):
+        """Binds a per-agent table of risk fields (mpc_set_agent_fields; not on an engine of CONSTR_DISCS): table
+        [P, NFIELD * NFSRC * N] float64 (rows [N][NFIELD][NFSRC], sources [cx, cy, c, s, A, kx, ky, alpha], as
+        _lib.field_rows(...).reshape(P, -1) makes them; A = 0: no source), index [B] int32 = the row of agent b.  Bound,
+        every call that evaluates the horizon's cost (eval_cost_grad(_wave), solve, solve_async, solve_active, the closed
+        loops) adds the skewed Gaussians of agent b's row to its stage costs, stage k reading entry k, and serves batches
+        of exactly B agents.  A cost, not a constraint: it works beside the engine's own constraint data (a lane band),
+        the parameter, bounds and rate tables (together they are for the same B); not beside a constraint table.  The
+        tensors stay the caller's: the library reads them at every call, so rows may be rewritten in place between
+        calls; the engine keeps them alive until clear_agent_fields()."""
+        self._bind_agent_table("fields", table, index)
+
+    def clear_agent_fields(self):
+        """Unbinds the field table: the engine is what it was before set_agent_fields."""
+        self._clear_agent_table("fields")
+
+    @property
+    def agent_fields_bound(self):
+        return "fields" in self._keep
+
+    def fields_from_plans(self, X, opp, shape, out=None):
+        """mpc_fields_from_plans: the field table [B, NFIELD * NFSRC * N] in which agent b's sources are the plans of its
+        opponents -- X [B, N, nx] as rollout() returns it for the agents' current plans, opp [B, NFIELD] int32 (the
+        opponents of agent b, as opponents_from_plans returns them; < 0 or >= B: none, eight zeros), shape [B, 4] =
+        [A, kx, ky, gain] of agent b as an obstacle: the source sits at the opponent's planned position in the frame of
+        its planned heading, skewed by gain * (own speed - its speed).  A gather on the current stream; `out`: a table to
+        write in place (one that is bound, say), else a new one."""
+        self._free()
+        if not isinstance(X, torch.Tensor) or X.dim() != 3:
+            raise ValueError(f"X: expected [B, {self.N}, {self.nx}]")
+        B = X.shape[0]
+        self._chk(X, (B, self.N, self.nx), "X")
+        self._chk(opp, (B, _lib.NFIELD), "opp", torch.int32)
+        self._chk(shape, (B, 4), "shape")
+        width = _lib.field_row(self.N)
+        table = self._empty(B, width) if out is None else self._chk(out, (B, width), "out")
+        _lib.check(self.lib.mpc_fields_from_plans(self._h, B, _ptr(X), _ptr(opp), _ptr(shape), _ptr(table), self._stream()))
+        return table
 
     def discs_from_plans(self, X, opp, radius, out=None):
         """mpc_discs_from_plans: the disc table [B, 3 * NDISC * N] in which agent b's discs are the plans of its
@@ -544,6 +584,49 @@ class BatchedMPC:
             _ptr(table), _ptr(tx), _ptr(tu), _ptr(topp), _ptr(tclear), _ptr(fails), _ptr(stats), self._stream()))
         return TrafficLoopResult(x, U, lam, tx, tu, fails, stats, topp, tclear, table)
 
+    def closed_loop_traffic_field(self, x, centerline, U, T, G, radius, shape, reach=float("inf"), lam=None, cl_index=None,
+                                  shift=False, table=None):
+        """mpc_closed_loop_traffic_field (an engine of any constr_mode but CONSTR_DISCS): closed_loop_traffic with soft
+        obstacles -- at every step every agent's cost gets the risk fields of the current plans of the NFIELD nearest
+        agents of its scene (opponents_from_plans on rollout(x, U), then fields_from_plans into the bound table, then the
+        solve and the plant step).  radius [B] drives the selection and traj_clear, shape [B, 4] = [A, kx, ky, gain] is
+        agent b as an obstacle.  table: the bound field table [B, NFIELD NFSRC N] (set_agent_fields with index =
+        arange(B)), rewritten in place; None: a table of zeros is made, bound with arange(B) and left bound.  Returns a
+        TrafficLoopResult (x, U and lam are copies, lam None where the engine has no constraints; the table is the bound
+        one)."""
+        B, T = x.shape[0], int(T)
+        self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
+        self._check_rate_rows(B)
+        if T < 0:
+            raise ValueError("T must be >= 0")
+        G, reach = self._scene_args(B, G, radius, reach)
+        self._chk(shape, (B, 4), "shape")
+        if int(self.cfg.constr_mode) == _lib.CONSTR_DISCS:     # before a table is made and bound for the caller
+            raise ValueError("closed_loop_traffic_field: the engine's constr_mode is CONSTR_DISCS, where an obstacle is a disc "
+                             "(closed_loop_traffic)")
+        width = _lib.field_row(self.N)
+        if table is None:
+            table = torch.zeros(B, width, dtype=torch.float64, device=self.device)
+            self.set_agent_fields(table, torch.arange(B, dtype=torch.int32, device=self.device))
+        else:
+            self._chk(table, (B, width), "table")
+        cl = self._centerline(centerline, cl_index, B)
+        x, U = x.clone(), U.clone()
+        if self.m:
+            lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None else lam.clone()
+            self._chk(lam, (B, self.m), "lam")
+        else:
+            lam = None
+        tx, tu = self._empty(B, T, self.nx), self._empty(B, T, 2)
+        topp = torch.full((B, T, _lib.NFIELD), -1, dtype=torch.int32, device=self.device)
+        tclear = torch.full((B, T), float("inf"), dtype=torch.float64, device=self.device)
+        fails = torch.zeros(B, dtype=torch.int32, device=self.device)
+        stats = self._empty(B, _lib.NSTATS)
+        _lib.check(self.lib.mpc_closed_loop_traffic_field(
+            self._h, B, T, int(bool(shift)), G, _ptr(radius), _ptr(shape), reach, _ptr(x), _ptr(cl), _ptr(cl_index), _ptr(U),
+            _ptr(lam), _ptr(table), _ptr(tx), _ptr(tu), _ptr(topp), _ptr(tclear), _ptr(fails), _ptr(stats), self._stream()))
+        return TrafficLoopResult(x, U, lam, tx, tu, fails, stats, topp, tclear, table)
+
     # ------------------------------------------------------------------ masked solve, event-triggered loop
     def _weights(self, w):
         w = [float(v) for v in (w.tolist() if hasattr(w, "tolist") else w)]
@@ -758,7 +841,7 @@ class BatchedMPC:
         return out
 
     def math_probe(self, op, a, b=None):
-        """Device math used by the kernels (test aid): op 0 sin, 1 cos, 2 atan, 3 atan2(a, b), 4 tan."""
+        """Device math used by the kernels (test aid): op 0 sin, 1 cos, 2 atan, 3 atan2(a, b), 4 tan, 5 exp."""
         n = a.shape[0]
         self._chk(a, (n,), "a")
         if b is not None:
