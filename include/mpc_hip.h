@@ -499,6 +499,64 @@ int mpc_closed_loop_track(mpc_handle *h, int B, int T, int shift, const double *
                           uint8_t *solved, int32_t *solve_count, int32_t *fail_count, double *stats, void *stream,
                           const mpc_track *trk, int32_t *traj_row);
 
+/* Scripted moving obstacles: obstacle TRAJECTORIES per scene, the selection of the ones that matter to each agent, decided
+ * on the device, and the closed loop around it.  Scenes are the traffic loop's: contiguous blocks of G agents, agent b in
+ * scene b / G, 1 <= G <= MPC_SCENE_MAX and B % G == 0.  Every scene has K scripted obstacles, 1 <= K <= MPC_SCENE_MAX, each
+ * of Lt >= 1 samples, one per Ts of the handle, shared by the scene's G agents: obs [B / G][K][Lt][W], doubles in DEVICE
+ * memory of the caller.  W = 3 on a handle of MPC_CONSTR_DISCS, a sample being (cx, cy, r); W = MPC_NFSRC on every other
+ * handle, a sample being a whole risk source (cx, cy, c, s, A, kx, ky, alpha) -- the caller scripts frame and skew.  A
+ * sample is ABSENT iff r == 0 (discs) or A == 0 (fields): "not there yet", "gone".  The sample of time i >= 0, in
+ * integers: wrap ? i mod Lt : min(i, Lt - 1) -- a script that ends leaves its obstacle standing at the last sample, a
+ * periodic one serves an obstacle circling a closed track.  obs is device data and is not checked, as radius is not
+ * (the Python front end's obstacle_tracks applies the row rules of mpc_set_agent_discs / _fields).
+ * mpc_obstacles_select: X [B][Nst][nx] as mpc_rollout writes it (Nst = 1 with X = x: the states as they are); stage k is
+ * compared with sample ti + k of every obstacle o < K of b's scene.  The rule, every operation rounded on its own (a host
+ * loop in IEEE doubles gets the same bits), over the stages k < Nst whose sample is present:
+ *     dx = X[b][k][0] - cx, dy = X[b][k][1] - cy, g_k = (dx dx + dy dy) - r2,   c(b, o) = min_k g_k
+ * with r2 = r r for discs and 0 for fields -- the disc expression and the rule of mpc_opponents_from_plans, operand for
+ * operand.  A pair with a g_k that is not finite is out; an obstacle with no present sample in the window is no
+ * candidate; o is a candidate iff c(b, o) < reach reach (reach >= 0; +inf: all).  Selected are the MPC_NDISC candidates
+ * smallest in the lexicographic order (c, o), ties to the smaller o.  sel [B][MPC_NDISC] (int32, out) holds the obstacle's
+ * index WITHIN THE SCENE, an unused slot -1 with clear = +inf; clear [B][MPC_NDISC] (out) may be NULL.  No atomics.
+ * Asynchronous on `stream`.  MPC_E_ARG before any launch: G or K outside [1, MPC_SCENE_MAX], B % G != 0, Lt < 1, ti < 0,
+ * ti + Nst not an int32, Nst < 1, reach negative or NaN, NULL X, obs or sel, an asynchronous solve in flight, and, with
+ * tables bound, a B other than the bound one.
+ * mpc_discs_from_obstacles (only on a handle of MPC_CONSTR_DISCS) and mpc_fields_from_obstacles (on every other): the
+ * gather, asynchronous on `stream`.  table [B][MPC_DISC_ROW(N)] or [B][MPC_FIELD_ROW(N)] receives, for k < N,
+ *     table[b][k][j] = obs[b / G][sel[b][j]][sample(ti + k)]     (W words)
+ * and W zeros where sel[b][j] is outside [0, K) and where the sample is absent (its other words are never copied: junk
+ * behind r == 0 cannot reach a constraint).  Every word written is a copy of an input word or zero.  The refusals of the
+ * selection that apply (ti + N in place of ti + Nst), NULL sel or table, and the handle's constr_mode.
+ * mpc_closed_loop_obstacles: T closed-loop steps among the scripted obstacles, on a handle of any constr_mode.  Blocking;
+ * the arguments it shares with mpc_closed_loop_traffic mean what they mean there.  `table` must be the bound disc table
+ * (MPC_CONSTR_DISCS) or the bound field table (every other mode) with P == B rows, index 0 .. B-1 (MPC_E_ARG otherwise);
+ * with a rate table bound it needs one row per agent as in the other loops.  Step t, every numbered launch being the one
+ * the public call of that name makes:
+ *   0. only with trk != NULL: mpc_track_select(x, cl as win, active = NULL, cl_index) -- lap driving among moving
+ *      obstacles, everybody re-selecting its window at every step (mpc_closed_loop_track at thr = 0 does); with
+ *      trk == NULL cl_index is read only and may be NULL
+ *   1. X = mpc_rollout(x, U), N stages, into a buffer of the handle
+ *   2. sel = mpc_obstacles_select on X with ti = t0 + t + 1, Nst = N; traj_sel [B][T][MPC_NDISC] records it (NULL ok)
+ *   3. table = the gather of the handle's kind with the same ti
+ *   4. mpc_solve_batch; U and lambda are warm starts, lambda is NOT re-slotted when the selection changes
+ *   5. the rate table's u_prev write and the plant step of mpc_closed_loop, as the traffic loop launches them
+ *   6. traj_clear [B][T] (NULL ok) = slot 0 of `clear` of the selection on the NEW states (Nst = 1, ti = t0 + t + 1,
+ *      reach = +inf): the realised clearance at time t + 1; +inf when nothing is present
+ * t0 >= 0 lets a later call continue the script: two calls of T steps (the second with t0 + T and what the first
+ * returned) are one of 2 T.  Also MPC_E_ARG: T < 0, t0 < 0, t0 + T + N not an int32.  Nothing but the solve's own polls
+ * returns to the host. */
+int mpc_obstacles_select(mpc_handle *h, int B, int G, int K, int Lt, int wrap, int ti, int Nst, const double *X,
+                         const double *obs, double reach, int32_t *sel, double *clear, void *stream);
+int mpc_discs_from_obstacles(mpc_handle *h, int B, int G, int K, int Lt, int wrap, int ti, const double *obs,
+                             const int32_t *sel, double *table, void *stream);
+int mpc_fields_from_obstacles(mpc_handle *h, int B, int G, int K, int Lt, int wrap, int ti, const double *obs,
+                              const int32_t *sel, double *table, void *stream);
+int mpc_closed_loop_obstacles(mpc_handle *h, int B, int T, int shift, int G, int K, int Lt, int wrap, int t0,
+                              const double *obs, double reach, double *x, const double *cl, int32_t *cl_index,
+                              double *U, double *lambda, double *table, double *traj_x, double *traj_u,
+                              int32_t *traj_sel, double *traj_clear, int32_t *fail_count, double *stats, void *stream,
+                              const mpc_track *trk);
+
 /* profiling aid: rounds (eval launches) and kernel time of the last mpc_solve_batch */
 int mpc_last_solve_info(mpc_handle *h, int64_t *rounds, int64_t *evals_grad, int64_t *evals_cost,
                         double *eval_ms, double *step_ms);

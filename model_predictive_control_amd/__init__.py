@@ -6,8 +6,9 @@ from ._lib import (MODEL_KINEMATIC, MODEL_PACEJKA, WRAP_FLOOR, WRAP_FMOD, WRAP_I
                    CONSTR_STATE_SQ, CONSTR_LANE, CONSTR_DISCS, NDISC, SCENE_MAX, default_discs, disc_rows,
                    NRATE, default_rates, rate_rows, NFIELD, NFSRC, field_row, default_fields, field_rows,
                    NSTATS, NPARAM, MpcConfig, default_config, default_params, param_rows, NBOUND,
-                   default_bounds, bound_rows, NCONSTR, default_constraints, constraint_rows, MpcError)
-from .solver import BatchedMPC, Track, TrafficLoopResult
+                   default_bounds, bound_rows, NCONSTR, default_constraints, constraint_rows, MpcError,
+                   obstacle_tracks, obstacle_width)
+from .solver import BatchedMPC, Track, TrafficLoopResult, ObstacleLoopResult
 from .tracks import stadium_track, circle_track
 
 __all__ = ["BatchedMPC", "MpcConfig", "default_config", "MpcError", "MODEL_KINEMATIC", "MODEL_PACEJKA",
@@ -16,4 +17,4 @@ __all__ = ["BatchedMPC", "MpcConfig", "default_config", "MpcError", "MODEL_KINEM
            "rate_rows", "NFIELD", "NFSRC", "field_row", "default_fields", "field_rows", "NSTATS", "NPARAM",
            "default_params", "param_rows", "NBOUND", "default_bounds", "bound_rows", "NCONSTR",
            "default_constraints", "constraint_rows", "Track", "TrafficLoopResult", "stadium_track",
-           "circle_track"]
+           "circle_track", "ObstacleLoopResult", "obstacle_tracks", "obstacle_width"]

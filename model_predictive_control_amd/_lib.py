@@ -32,7 +32,7 @@ LIB_PATH = os.environ.get("MPC_LIB_PATH", os.path.join(_HERE, "libmpc_hip.so")) 
 _SRC = [os.path.join(_HERE, "csrc", f) for f in ("mpc_api.hip", "mpc_handle.hpp", "mpc_launch.hpp", "mpc_rounds.hpp",
                                                   "mpc_aux.hpp", "mpc_eval.hpp", "mpc_solver.hpp", "mpc_device.hpp",
                                                   "mpc_game.hpp", "mpc_solo.hpp", "mpc_event.hpp", "mpc_step_body.hpp",
-                                                  "mpc_track.hpp", "mpc_traffic.hpp")]
+                                                  "mpc_track.hpp", "mpc_obstacles.hpp", "mpc_traffic.hpp")]
 _HDR = os.path.join(os.path.dirname(_HERE), "include", "mpc_hip.h")
 
 MODEL_KINEMATIC, MODEL_PACEJKA = 0, 1
@@ -58,6 +58,7 @@ EXPORTS = [
     "mpc_default_rates", "mpc_set_agent_rates",
     "mpc_default_fields", "mpc_set_agent_fields", "mpc_fields_from_plans", "mpc_closed_loop_traffic_field",
     "mpc_opponents_from_plans", "mpc_closed_loop_traffic",
+    "mpc_obstacles_select", "mpc_discs_from_obstacles", "mpc_fields_from_obstacles", "mpc_closed_loop_obstacles",
     "mpc_track_init", "mpc_track_windows", "mpc_track_locate", "mpc_track_select", "mpc_closed_loop_track",
 ]
 NREC = 64
@@ -195,6 +196,11 @@ def load():
     L.mpc_closed_loop_traffic_field.argtypes = [vp, ci, ci, ci, ci, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mpc_opponents_from_plans.argtypes = [vp, ci, ci, ci, vp, vp, C.c_double, vp, vp, vp]
     L.mpc_closed_loop_traffic.argtypes = [vp, ci, ci, ci, ci, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mpc_obstacles_select.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, C.c_double, vp, vp, vp]
+    L.mpc_discs_from_obstacles.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp]
+    L.mpc_fields_from_obstacles.argtypes = L.mpc_discs_from_obstacles.argtypes
+    L.mpc_closed_loop_obstacles.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                            vp, vp, vp, tp]
     L.mpc_step_lds_plan.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     L.mpc_math_probe.argtypes = [vp, ci, ci, vp, vp, vp, vp]
     L.mpc_lane_payoff.argtypes = [vp, ci, ci, C.POINTER(C.c_double), vp, vp, vp, vp, vp]
@@ -437,6 +443,53 @@ def field_rows(centres, heading, A, sigma_x, sigma_y, alpha=0):
     tab[..., 2], tab[..., 3], tab[..., 4] = np.cos(hd), np.sin(hd), Av
     tab[..., 5], tab[..., 6], tab[..., 7] = 1.0 / (2.0 * sx * sx), 1.0 / (2.0 * sy * sy), al
     return tab
+
+
+def obstacle_width(cfg):
+    """W of a sample of the obstacle tracks of `cfg`: 3 = (cx, cy, r) on CONSTR_DISCS, NFSRC (a whole risk source) else."""
+    return 3 if int(cfg.constr_mode) == CONSTR_DISCS else NFSRC
+
+
+def obstacle_tracks(cfg, centres=None, radii=None, sources=None):
+    """The table of scripted obstacles for BatchedMPC.obstacles_select / closed_loop_obstacles, on the host: float64
+    [scenes, K, Lt, W], one sample per Ts.  On a cfg of CONSTR_DISCS (W = 3): `centres` [scenes, K, Lt, 2] and `radii`
+    [scenes, K, Lt] (or anything that broadcasts to it; r = 0: the obstacle is absent at that sample).  On every other cfg
+    (W = NFSRC): `sources` [scenes, K, Lt, NFSRC] = [cx, cy, c, s, A, kx, ky, alpha] (A = 0: absent).  Checked by the row
+    rules of mpc_set_agent_discs / mpc_set_agent_fields -- the library does not check the table: everything finite,
+    r >= 0; A, kx, ky >= 0 and a skew (alpha != 0) only with kx > 0; 1 <= K <= SCENE_MAX, Lt >= 1.  Pure host code."""
+    import numpy as np
+    who = "obstacle_tracks"
+    if obstacle_width(cfg) == 3:
+        if centres is None or radii is None or sources is not None:
+            raise ValueError(f"{who}: a configuration of CONSTR_DISCS takes centres and radii (an obstacle is a disc)")
+        c = np.asarray(centres, dtype=np.float64)
+        if c.ndim != 4 or c.shape[-1] != 2:
+            raise ValueError(f"{who}: centres must have shape (scenes, K, Lt, 2), got {c.shape}")
+        try:
+            r = np.broadcast_to(np.asarray(radii, dtype=np.float64), c.shape[:3])
+        except ValueError:
+            raise ValueError(f"{who}: radii must broadcast to {c.shape[:3]}, got {np.shape(radii)}") from None
+        tab = np.empty(c.shape[:3] + (3,), dtype=np.float64)
+        tab[..., :2], tab[..., 2] = c, r
+        if not np.all(np.isfinite(tab)):
+            raise ValueError(f"{who}: (cx, cy, r) must be finite")
+        if np.any(tab[..., 2] < 0.0):
+            raise ValueError(f"{who}: the radius must not be negative")
+    else:
+        if sources is None or centres is not None or radii is not None:
+            raise ValueError(f"{who}: a configuration without CONSTR_DISCS takes sources (an obstacle is a risk source)")
+        tab = np.array(sources, dtype=np.float64)
+        if tab.ndim != 4 or tab.shape[-1] != NFSRC:
+            raise ValueError(f"{who}: sources must have shape (scenes, K, Lt, {NFSRC}), got {tab.shape}")
+        if not np.all(np.isfinite(tab)):
+            raise ValueError(f"{who}: (cx, cy, c, s, A, kx, ky, alpha) must be finite")
+        if np.any(tab[..., 4:7] < 0.0):
+            raise ValueError(f"{who}: A, kx and ky must not be negative")
+        if np.any((tab[..., 7] != 0.0) & ~(tab[..., 5] > 0.0)):
+            raise ValueError(f"{who}: a skew (alpha != 0) needs kx > 0")
+    if tab.shape[0] < 1 or not 1 <= tab.shape[1] <= SCENE_MAX or tab.shape[2] < 1:
+        raise ValueError(f"{who}: need scenes >= 1, 1 <= K <= {SCENE_MAX} obstacles and Lt >= 1 samples, got {tab.shape[:3]}")
+    return np.ascontiguousarray(tab)
 
 
 def track_init(cfg, K, L, stride, lead, closed):

@@ -1,9 +1,11 @@
 // mpc_api.hip -- the C-ABI of libmpc_hip.so (see include/mpc_hip.h): the extern "C" entry points of the batched MPC
 // solve on one MI355X, one process / one handle per GPU.  The one translation unit of the library: the host side is in
 // mpc_handle.hpp (the handle and its per-agent tables), mpc_launch.hpp (which kernel instantiation a launch takes) and mpc_rounds.hpp (the
-// round loop of a solve), the kernels in the headers those include (and mpc_track.hpp: the kernels of lap driving).
+// round loop of a solve), the kernels in the headers those include (and mpc_track.hpp: the kernels of lap driving;
+// mpc_obstacles.hpp: the kernels of the scripted obstacles).
 #include "mpc_rounds.hpp"
 #include "mpc_track.hpp"
+#include "mpc_obstacles.hpp"
 
 extern "C" const char *mpc_last_error(void) { return g_err.c_str(); }
 #ifndef MPC_SOURCE_SHA256
@@ -1061,6 +1063,166 @@ extern "C" int mpc_closed_loop_traffic_field(mpc_handle *h, int B, int T, int sh
                                     traj_opp, traj_clear, fail_count, stats, stream, [&](const double *X, const int32_t *opp) {
                                         return mpc_fields_from_plans(h, B, X, opp, shape, table, stream);
                                     });
+}
+
+// ---------------------------------------------------------------------------------- scripted obstacles (mpc_obstacles.hpp)
+static_assert(MPC_NDISC == MPC_NFIELD, "one sel [B][2] of mpc_obstacles_select serves the disc and the field table");
+// what the four entry points ask of the scene and the tracks (checked without a device) ...
+static int check_obstacle_args(const std::string &who, int B, int G, int K, int Lt, int ti, const char *ti_name, const void *obs)
+{
+    if (G < 1 || G > MPC_SCENE_MAX) return fail(MPC_E_ARG, who + ": the scene size G must be in [1, " + std::to_string(MPC_SCENE_MAX) + "]");
+    if (K < 1 || K > MPC_SCENE_MAX) return fail(MPC_E_ARG, who + ": the number of obstacles K of a scene must be in [1, " + std::to_string(MPC_SCENE_MAX) + "]");
+    if (B < 0) return fail(MPC_E_ARG, who + ": negative batch");
+    if (B % G) return fail(MPC_E_ARG, who + ": the batch of " + std::to_string(B) + " agents is not a whole number of scenes of G = " +
+                                       std::to_string(G) + " (B % G != 0: pad the scenes)");
+    if (Lt < 1) return fail(MPC_E_ARG, who + ": Lt must be >= 1 samples per obstacle");
+    if (ti < 0) return fail(MPC_E_ARG, who + ": " + ti_name + " must be >= 0");
+    if (!obs) return fail(MPC_E_ARG, who + ": null obs");
+    return MPC_OK;
+}
+// ... and of the window of `stages` samples from `ti` on: the kernels index it with an int
+static int check_obstacle_window(const std::string &who, int ti, long long stages, const char *ti_name)
+{
+    if (ti + stages > 2147483647ll) return fail(MPC_E_ARG, who + ": " + ti_name + " plus the stages of the window does not fit an int32");
+    return MPC_OK;
+}
+// W of the handle's obstacle samples: a disc on a handle of MPC_CONSTR_DISCS, a whole risk source on every other
+static bool obstacle_discs(const mpc_handle *h) { return h->cfg.constr_mode == MPC_CONSTR_DISCS; }
+
+// the selection on plans X [B][Nst][nx] against the window from sample `ti` (see obstacles_kernel for the three outputs)
+static void launch_obstacles(mpc_handle *h, hipStream_t s, int B, int G, int K, int Lt, int wrap, int ti, int Nst, const double *X,
+                             const double *obs, double reach, int32_t *sel, int32_t *sel_rec, size_t rec_stride, double *clear,
+                             size_t clear_stride, int clear_slots)
+{
+    int Gp = 1, Kp = 1;
+    while (Gp < G) Gp <<= 1;
+    while (Kp < K) Kp <<= 1;
+    const int spw = 64 / std::max(Gp, Kp), scenes = B / G;
+    const dim3 grid((unsigned)((scenes + spw - 1) / spw));
+    if (obstacle_discs(h))
+        hipLaunchKernelGGL(obstacles_kernel<3>, grid, dim3(TR_BLK), 0, s, B, G, K, Kp, spw, Lt, wrap ? 1 : 0, ti, Nst, h->dc.nx, X, obs,
+                           reach * reach, sel, sel_rec, rec_stride, clear, clear_stride, clear_slots);
+    else
+        hipLaunchKernelGGL(obstacles_kernel<MPC_NFSRC>, grid, dim3(TR_BLK), 0, s, B, G, K, Kp, spw, Lt, wrap ? 1 : 0, ti, Nst, h->dc.nx, X,
+                           obs, reach * reach, sel, sel_rec, rec_stride, clear, clear_stride, clear_slots);
+}
+
+extern "C" int mpc_obstacles_select(mpc_handle *h, int B, int G, int K, int Lt, int wrap, int ti, int Nst, const double *X,
+                                    const double *obs, double reach, int32_t *sel, double *clear, void *stream)
+{
+    const std::string who = "mpc_obstacles_select";
+    if (Nst < 1) return fail(MPC_E_ARG, who + ": Nst must be >= 1 stages");
+    int rc = check_obstacle_args(who, B, G, K, Lt, ti, "ti", obs); if (rc) return rc;
+    rc = check_obstacle_window(who, ti, Nst, "ti"); if (rc) return rc;
+    if (!(reach >= 0.0)) return fail(MPC_E_ARG, who + ": reach must be >= 0 (+inf: every obstacle of the scene)");
+    if (!X || !sel) return fail(MPC_E_ARG, who + ": null X or sel");
+    rc = check_common(h, B, who.c_str()); if (rc) return rc;
+    rc = check_tables(h, B, who.c_str(), READS_ALL); if (rc) return rc;
+    if (B == 0) return MPC_OK;
+    launch_obstacles(h, (hipStream_t)stream, B, G, K, Lt, wrap, ti, Nst, X, obs, reach, sel, nullptr, 0, clear, MPC_NDISC, MPC_NDISC);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
+// the gather of the window of the selected tracks from sample `ti` into table [B][N][MPC_NDISC][W] (rows_from_obstacles_kernel)
+static void launch_rows(mpc_handle *h, hipStream_t s, int B, int G, int K, int Lt, int wrap, int ti, const double *obs,
+                        const int32_t *sel, double *table)
+{
+    const size_t words = (size_t)B * h->cfg.N * MPC_NDISC;
+    const dim3 grid((unsigned)((words + 255) / 256));
+    if (obstacle_discs(h))
+        hipLaunchKernelGGL(rows_from_obstacles_kernel<3>, grid, dim3(256), 0, s, B, h->cfg.N, G, K, Lt, wrap ? 1 : 0, ti, obs, sel, table);
+    else
+        hipLaunchKernelGGL(rows_from_obstacles_kernel<MPC_NFSRC>, grid, dim3(256), 0, s, B, h->cfg.N, G, K, Lt, wrap ? 1 : 0, ti, obs, sel,
+                           table);
+}
+// what the two public gathers check (`discs`: the disc form), asynchronous
+static int rows_from_obstacles(const std::string &who, bool discs, mpc_handle *h, int B, int G, int K, int Lt, int wrap, int ti,
+                               const double *obs, const int32_t *sel, double *table, void *stream)
+{
+    int rc = check_obstacle_args(who, B, G, K, Lt, ti, "ti", obs); if (rc) return rc;
+    if (!sel || !table) return fail(MPC_E_ARG, who + ": null sel or table");
+    rc = check_common(h, B, who.c_str()); if (rc) return rc;
+    rc = check_obstacle_window(who, ti, h->cfg.N, "ti"); if (rc) return rc;
+    if (discs && !obstacle_discs(h)) return fail(MPC_E_ARG, who + ": the handle's constr_mode is not MPC_CONSTR_DISCS");
+    if (!discs && obstacle_discs(h))
+        return fail(MPC_E_ARG, who + ": the handle's constraints are keep-out discs (constr_mode MPC_CONSTR_DISCS): there an obstacle is a disc "
+                               "(mpc_set_agent_discs)");
+    rc = check_tables(h, B, who.c_str(), READS_ALL); if (rc) return rc;
+    if (B == 0) return MPC_OK;
+    launch_rows(h, (hipStream_t)stream, B, G, K, Lt, wrap, ti, obs, sel, table);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+extern "C" int mpc_discs_from_obstacles(mpc_handle *h, int B, int G, int K, int Lt, int wrap, int ti, const double *obs,
+                                        const int32_t *sel, double *table, void *stream)
+{
+    return rows_from_obstacles("mpc_discs_from_obstacles", true, h, B, G, K, Lt, wrap, ti, obs, sel, table, stream);
+}
+extern "C" int mpc_fields_from_obstacles(mpc_handle *h, int B, int G, int K, int Lt, int wrap, int ti, const double *obs,
+                                         const int32_t *sel, double *table, void *stream)
+{
+    return rows_from_obstacles("mpc_fields_from_obstacles", false, h, B, G, K, Lt, wrap, ti, obs, sel, table, stream);
+}
+
+// Closed loop among scripted obstacles: per step (with a track) everybody's window of the track, everybody's plans
+// (mpc_rollout), the nearest obstacle tracks of every agent's scene on them at the script's time t0 + t + 1, their window
+// into the bound disc or field table, the solve, the plant step of mpc_closed_loop, and the clearance realised on the new
+// states.  Every step is what the public call of that name launches; control returns to the host inside the solve alone.
+// The traffic loops' body is not shared: they stay launch for launch what they are.
+extern "C" int mpc_closed_loop_obstacles(mpc_handle *h, int B, int T, int shift, int G, int K, int Lt, int wrap, int t0,
+                                         const double *obs, double reach, double *x, const double *cl, int32_t *cl_index,
+                                         double *U, double *lambda, double *table, double *traj_x, double *traj_u,
+                                         int32_t *traj_sel, double *traj_clear, int32_t *fail_count, double *stats, void *stream,
+                                         const mpc_track *trk)
+{
+    const std::string who = "mpc_closed_loop_obstacles";
+    if (T < 0) return fail(MPC_E_ARG, who + ": negative T");
+    int rc = check_obstacle_args(who, B, G, K, Lt, t0, "t0", obs); if (rc) return rc;
+    if (!(reach >= 0.0)) return fail(MPC_E_ARG, who + ": reach must be >= 0 (+inf: every obstacle of the scene)");
+    rc = check_common(h, B, who.c_str()); if (rc) return rc;
+    rc = check_obstacle_window(who, t0, (long long)T + h->cfg.N, "t0"); if (rc) return rc;   // up to the last step's window
+    if (trk) { rc = check_track(h, trk, who.c_str()); if (rc) return rc; }
+    const bool discs = obstacle_discs(h);
+    const TableKind kind = discs ? TAB_DISCS : TAB_FIELDS;
+    const BoundTable &dt = h->tab[kind];
+    rc = check_tables(h, B, who.c_str(), READS_ALL, true); if (rc) return rc;
+    if (!table || table != dt.table)
+        return fail(MPC_E_ARG, who + ": table must be the " + k_tables[kind].noun + " table that is bound (" + k_tables[kind].setter +
+                               "): the loop rewrites it in place");
+    if (dt.rows != B)
+        return fail(MPC_E_ARG, who + ": the bound " + k_tables[kind].noun + " table has " + std::to_string(dt.rows) +
+                               " rows, the loop needs one per agent (P == B = " + std::to_string(B) + ", index 0 .. B-1)");
+    rc = check_rate_rows(h, B, who); if (rc) return rc;
+    if (B == 0 || T == 0) return MPC_OK;
+    if (!x || !cl || !U || (h->dc.m && !lambda) || (trk && !cl_index)) return fail(MPC_E_ARG, who + ": null buffer");
+    rc = reserve_traffic(h, B); if (rc) return rc;
+    const DevCfg &c = h->dc;
+    mpc_handle::TrafficBufs &tr = h->tr;
+    hipStream_t s = (hipStream_t)stream;
+    double *st = stats;
+    if (!st) {
+        rc = reserve_stage(h, sizeof(double) * 8 * (size_t)B); if (rc) return rc;
+        st = h->stage;
+    }
+    for (int t = 0; t < T; t++) {
+        const int ti = t0 + t + 1;
+        if (trk) { rc = mpc_track_select(h, trk, B, x, cl, nullptr, cl_index, nullptr, stream); if (rc) return rc; }
+        rc = mpc_rollout(h, B, c.N, x, U, tr.X, stream); if (rc) return rc;
+        launch_obstacles(h, s, B, G, K, Lt, wrap, ti, c.N, tr.X, obs, reach, tr.opp, traj_sel ? traj_sel + (size_t)t * MPC_NDISC : nullptr,
+                         (size_t)T * MPC_NDISC, nullptr, 0, 0);
+        launch_rows(h, s, B, G, K, Lt, wrap, ti, obs, tr.opp, table);
+        rc = mpc_solve_batch(h, B, x, cl, cl_index, U, lambda, st, stream); if (rc) return rc;
+        launch_rate_prev(h, s, B, U, nullptr, nullptr);
+        with_model_table(h, h->plant_rows(), [&](auto MODEL, auto PA, auto... pt) {
+            hipLaunchKernelGGL((plant_step_kernel<MODEL(), PA(), decltype(pt)...>), grid_for(B, 64), dim3(64), 0,
+                               s, c, B, t, T, shift, x, U, traj_x, traj_u, st, fail_count, pt...);
+        });
+        if (traj_clear)
+            launch_obstacles(h, s, B, G, K, Lt, wrap, ti, 1, x, obs, INFINITY, nullptr, nullptr, 0, traj_clear + t, (size_t)T, 1);
+    }
+    HIPCHK(hipGetLastError());
+    return bounded_sync(h, s, who.c_str());
 }
 
 extern "C" int mpc_last_speculation(mpc_handle *h, int64_t *issued, int64_t *used)

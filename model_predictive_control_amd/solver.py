@@ -34,6 +34,14 @@ TrackLoopResult = collections.namedtuple(
 TrafficLoopResult = collections.namedtuple(
     "TrafficLoopResult", "x U lam traj_x traj_u failures stats traj_opp traj_clear table")
 
+# what BatchedMPC.closed_loop_obstacles returns: what closed_loop returns -- x, U, lam, traj_x [B, T, nx], traj_u [B, T, 2],
+# failures [B], stats [B, 8] of the last solve --, then traj_sel [B, T, NDISC] int32 (the obstacles of its scene every agent
+# avoided at every step, -1: none), traj_clear [B, T] (the clearance to the nearest present obstacle after every step), the
+# disc or field table as the last step left it (bound to the engine) and cl_index [B] int32 (with a track: every agent's
+# row of the window table on return; else what was passed)
+ObstacleLoopResult = collections.namedtuple(
+    "ObstacleLoopResult", "x U lam traj_x traj_u failures stats traj_sel traj_clear table cl_index")
+
 
 class Track:
     """A table of track windows (BatchedMPC.track_windows): `win` [K * R, 2S], the window tensor -- an ordinary
@@ -823,6 +831,132 @@ class BatchedMPC:
             _ptr(lam), _ptr(held), _ptr(disturbance), _ptr(tx), _ptr(tu), _ptr(solved), _ptr(count), _ptr(fails),
             _ptr(stats), self._stream(), C.byref(trk._c), _ptr(rows)))
         return TrackLoopResult(x, U, lam, held, tx, tu, solved, count, fails, stats, ci, rows)
+
+    # ------------------------------------------------------------------ scripted obstacles
+    def _obstacle_args(self, B, G, obs, wrap, ti, Nst, reach=0.0):
+        """(G, K, Lt, wrap, ti, reach) of a call on the obstacle tracks obs [B / G, K, Lt, W]"""
+        G, ti, reach = int(G), int(ti), float(reach)
+        if not 1 <= G <= _lib.SCENE_MAX:
+            raise ValueError(f"G: a scene holds 1 .. {_lib.SCENE_MAX} agents")
+        if B % G:
+            raise ValueError(f"the batch of {B} agents is not a whole number of scenes of {G} (pad the scenes)")
+        W = _lib.obstacle_width(self.cfg)
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 4 or obs.shape[3] != W:
+            raise ValueError(f"obs: expected a tensor [B / G, K, Lt, {W}]")
+        K, Lt = int(obs.shape[1]), int(obs.shape[2])
+        if not 1 <= K <= _lib.SCENE_MAX or Lt < 1:
+            raise ValueError(f"obs: a scene has 1 .. {_lib.SCENE_MAX} obstacles of Lt >= 1 samples, got K = {K}, Lt = {Lt}")
+        self._chk(obs, (B // G, K, Lt, W), "obs")
+        if ti < 0 or ti + int(Nst) > 2 ** 31 - 1:
+            raise ValueError("the window of samples must start at a time >= 0 and end within an int32")
+        if not reach >= 0.0:
+            raise ValueError("reach must be >= 0 (inf: every obstacle of the scene)")
+        return G, K, Lt, int(bool(wrap)), ti, reach
+
+    def obstacles_select(self, X, G, obs, ti=0, reach=float("inf"), wrap=False):
+        """mpc_obstacles_select: (sel [B, NDISC] int32, clear [B, NDISC]) -- for every agent the NDISC scripted obstacles of
+        its scene (obs [B / G, K, Lt, W], _lib.obstacle_tracks) that come closest along the plans X [B, Nst, nx] (rollout();
+        [B, nx]: the states as they are now), stage k against sample ti + k (wrap: i mod Lt, else the last sample stands):
+        c(b, o) = min over the present samples of (dx dx + dy dy) - r^2 (fields: r = 0), candidates c < reach^2 with every
+        stage finite, the smallest in the order (c, o) first.  sel holds indices within the scene, -1 for an unused slot
+        (clear +inf): what discs_from_obstacles / fields_from_obstacles take.  On the current stream."""
+        self._free()
+        if isinstance(X, torch.Tensor) and X.dim() == 2:
+            X = X.unsqueeze(1)
+        if not isinstance(X, torch.Tensor) or X.dim() != 3 or X.shape[1] < 1:
+            raise ValueError(f"X: expected [B, Nst >= 1, {self.nx}]")
+        B, Nst = int(X.shape[0]), int(X.shape[1])
+        self._chk(X, (B, Nst, self.nx), "X")
+        G, K, Lt, wrap, ti, reach = self._obstacle_args(B, G, obs, wrap, ti, Nst, reach)
+        sel = torch.full((B, _lib.NDISC), -1, dtype=torch.int32, device=self.device)
+        clear = torch.full((B, _lib.NDISC), float("inf"), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.mpc_obstacles_select(self._h, B, G, K, Lt, wrap, ti, Nst, _ptr(X), _ptr(obs), reach, _ptr(sel),
+                                                 _ptr(clear), self._stream()))
+        return sel, clear
+
+    def _rows_from_obstacles(self, fn, width, sel, G, obs, ti, wrap, out):
+        self._free()
+        if not isinstance(sel, torch.Tensor) or sel.dim() != 2:
+            raise ValueError(f"sel: expected [B, {_lib.NDISC}] int32")
+        B = int(sel.shape[0])
+        self._chk(sel, (B, _lib.NDISC), "sel", torch.int32)
+        G, K, Lt, wrap, ti, _ = self._obstacle_args(B, G, obs, wrap, ti, self.N)
+        table = self._empty(B, width) if out is None else self._chk(out, (B, width), "out")
+        _lib.check(fn(self._h, B, G, K, Lt, wrap, ti, _ptr(obs), _ptr(sel), _ptr(table), self._stream()))
+        return table
+
+    def discs_from_obstacles(self, sel, G, obs, ti=0, wrap=False, out=None):
+        """mpc_discs_from_obstacles (an engine of CONSTR_DISCS): the disc table [B, 3 NDISC N] whose entry (k, j) of agent b
+        is sample ti + k of obstacle sel[b, j] of b's scene, zeros where sel is -1 (or outside [0, K)) or the sample is
+        absent (r == 0).  A gather on the current stream; `out`: a table to write in place, else a new one."""
+        if int(self.cfg.constr_mode) != _lib.CONSTR_DISCS:
+            raise _lib.MpcError("libmpc_hip error -1: mpc_discs_from_obstacles: the handle's constr_mode is not MPC_CONSTR_DISCS")
+        return self._rows_from_obstacles(self.lib.mpc_discs_from_obstacles, 3 * _lib.NDISC * self.N, sel, G, obs, ti, wrap, out)
+
+    def fields_from_obstacles(self, sel, G, obs, ti=0, wrap=False, out=None):
+        """mpc_fields_from_obstacles (an engine of any constr_mode but CONSTR_DISCS): the field table [B, NFIELD NFSRC N]
+        whose entry (k, j) of agent b is sample ti + k of obstacle sel[b, j] of b's scene, zeros where sel is -1 (or
+        outside [0, K)) or the sample is absent (A == 0).  `out`: a table to write in place, else a new one."""
+        if int(self.cfg.constr_mode) == _lib.CONSTR_DISCS:
+            raise _lib.MpcError("libmpc_hip error -1: mpc_fields_from_obstacles: the handle's constraints are keep-out discs "
+                                "(constr_mode MPC_CONSTR_DISCS): there an obstacle is a disc (mpc_set_agent_discs)")
+        return self._rows_from_obstacles(self.lib.mpc_fields_from_obstacles, _lib.field_row(self.N), sel, G, obs, ti, wrap, out)
+
+    def closed_loop_obstacles(self, x, centerline, U, T, G, obs, reach=float("inf"), t0=0, wrap=False, lam=None, cl_index=None,
+                              shift=False, table=None, track_obj=None):
+        """mpc_closed_loop_obstacles: closed_loop among scripted moving obstacles -- at every step every agent avoids the
+        NDISC obstacles of its scene (obs [B / G, K, Lt, W], _lib.obstacle_tracks) that come closest to its current plan,
+        stage k of the re-plan of step t reading sample t0 + t + 1 + k of their scripts (obstacles_select on rollout(x, U),
+        then discs_from_obstacles -- an engine of CONSTR_DISCS -- or fields_from_obstacles into the bound table, then the
+        solve and the plant step).  table: the bound disc / field table with index = arange(B), rewritten in place; None:
+        a table of zeros is made, bound with arange(B) and left bound.  track_obj: a Track (track_windows) -- the
+        centerline is its window table (pass centerline=None) and every agent re-selects its row cl_index [B] (required:
+        track_locate) from its state before every step.  t0: the script's time at the call (a second call with t0 + T,
+        and x, U, lam, cl_index of the first's result, continues it).  Returns an ObstacleLoopResult (copies; the table is
+        the bound one)."""
+        B, T, t0 = x.shape[0], int(T), int(t0)
+        self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
+        self._check_rate_rows(B)
+        if T < 0:
+            raise ValueError("T must be >= 0")
+        G, K, Lt, wrap, t0, reach = self._obstacle_args(B, G, obs, wrap, t0, T + self.N, reach)
+        discs = int(self.cfg.constr_mode) == _lib.CONSTR_DISCS
+        kind, width = ("discs", 3 * _lib.NDISC * self.N) if discs else ("fields", _lib.field_row(self.N))
+        if table is None:
+            table = torch.zeros(B, width, dtype=torch.float64, device=self.device)
+            arange = torch.arange(B, dtype=torch.int32, device=self.device)
+            self.set_agent_discs(table, arange) if discs else self.set_agent_fields(table, arange)
+        else:
+            self._chk(table, (B, width), "table")
+            if kind in self._keep and self._keep[kind][0] is table and \
+                    not torch.equal(self._keep[kind][1], torch.arange(B, dtype=torch.int32, device=self.device)):
+                raise ValueError(f"the bound {kind[:-1]} table's index is not arange(B): the loop writes row b for agent b")
+        trk = None
+        if track_obj is not None:
+            trk = self._track(track_obj)
+            if centerline is not None and centerline is not trk.win:
+                raise ValueError("with track_obj the centerline table is track_obj.win (pass centerline=None)")
+            if cl_index is None:
+                raise ValueError("cl_index: the rows to start from are required with track_obj (track_locate)")
+            centerline = trk.win
+        cl = self._centerline(centerline, cl_index, B)
+        x, U = x.clone(), U.clone()
+        ci = None if cl_index is None else cl_index.clone()
+        if self.m:
+            lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None else lam.clone()
+            self._chk(lam, (B, self.m), "lam")
+        else:
+            lam = None
+        tx, tu = self._empty(B, T, self.nx), self._empty(B, T, 2)
+        tsel = torch.full((B, T, _lib.NDISC), -1, dtype=torch.int32, device=self.device)
+        tclear = torch.full((B, T), float("inf"), dtype=torch.float64, device=self.device)
+        fails = torch.zeros(B, dtype=torch.int32, device=self.device)
+        stats = self._empty(B, _lib.NSTATS)
+        _lib.check(self.lib.mpc_closed_loop_obstacles(
+            self._h, B, T, int(bool(shift)), G, K, Lt, wrap, t0, _ptr(obs), reach, _ptr(x), _ptr(cl), _ptr(ci), _ptr(U), _ptr(lam),
+            _ptr(table), _ptr(tx), _ptr(tu), _ptr(tsel), _ptr(tclear), _ptr(fails), _ptr(stats), self._stream(),
+            C.byref(trk._c) if trk is not None else None))
+        return ObstacleLoopResult(x, U, lam, tx, tu, fails, stats, tsel, tclear, table, ci)
 
     def lane_payoff(self, ego, cars, ncars, params):
         """f-3: out[B, 2, 4] = target lane 1, 2 -> [total, safety, velocity, comfort] (game_theory.py:115-244)."""
