@@ -367,6 +367,14 @@ int mpc_eval_cost_grad_wave(mpc_handle *h, int B, const double *x0, const double
                             const int32_t *cl_index, const double *U, const double *y,
                             const double *Sigma, double *psi, double *grad, double *yhat, void *stream);
 
+/* two points of every agent in one trip of that code: the evaluation at U (psi; grad, NULL: cost only; yhat) on one
+ * half of the wavefront and the gradient at U2 (grad2[B][2N]) on the other, as a trip of the persistent kernel that
+ * carries a speculative gradient runs them -- bit-identical to two calls of mpc_eval_cost_grad.  Kinematic model,
+ * nfe = 4, N <= 32. */
+int mpc_eval_cost_grad_wave2(mpc_handle *h, int B, const double *x0, const double *cl,
+                             const int32_t *cl_index, const double *U, const double *U2, const double *y,
+                             const double *Sigma, double *psi, double *grad, double *grad2, double *yhat, void *stream);
+
 /* a-10, kernel K2: forward-backward step. p = clamp(-gamma*grad, lb-x, ub-x), xhat = x+p;
  * out[B][2] = [||p||^2, grad'p].  gamma[B]. */
 int mpc_prox_step(mpc_handle *h, int B, const double *x, const double *grad, const double *gamma,

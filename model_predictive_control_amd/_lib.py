@@ -47,7 +47,7 @@ EXPORTS = [
     "mpc_lbfgs_apply", "mpc_solve_batch", "mpc_solve_batch_async", "mpc_solve_wait", "mpc_closed_loop", "mpc_last_solve_info",
     "mpc_last_solve_info2", "mpc_math_probe", "mpc_set_groups", "mpc_last_kernel_ms", "mpc_lane_payoff",
     "mpc_set_profile", "mpc_last_speculation", "mpc_last_kernel_profile", "mpc_set_solo_max",
-    "mpc_eval_cost_grad_wave", "mpc_centerline_blocks", "mpc_set_nearest_blocks", "mpc_set_memo",
+    "mpc_eval_cost_grad_wave", "mpc_eval_cost_grad_wave2", "mpc_centerline_blocks", "mpc_set_nearest_blocks", "mpc_set_memo",
     "mpc_set_round_limit", "mpc_stream_concurrency", "mpc_last_solo_ms",
     "mpc_set_poll_timeout", "mpc_debug_spin", "mpc_debug_records", "mpc_debug_record_names", "mpc_source_hash",
     "mpc_last_lookahead", "mpc_step_lds_plan", "mpc_default_params", "mpc_set_agent_params",
@@ -157,6 +157,7 @@ def load():
     L.mpc_stage_cost.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
     L.mpc_eval_cost_grad.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mpc_eval_cost_grad_wave.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mpc_eval_cost_grad_wave2.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mpc_prox_step.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.mpc_lbfgs_apply.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mpc_solve_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]

@@ -491,7 +491,7 @@ extern "C" int mpc_stage_cost(mpc_handle *h, int B, const double *x, const doubl
 
 static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *cl, const int32_t *cl_index,
                           const double *U, const double *y, const double *Sigma, double *psi, double *grad,
-                          double *yhat, void *stream, bool wave_path)
+                          double *yhat, void *stream, bool wave_path, const double *U2 = nullptr, double *grad2 = nullptr)
 {
     int rc = check_common(h, B, "mpc_eval_cost_grad"); if (rc) return rc;
     if (B == 0) return MPC_OK;
@@ -508,12 +508,13 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     w.y = const_cast<double *>(y); w.Sig = c.m ? const_cast<double *>(Sigma) : h->ws.ws_Sig;
     w.yhe = (yhat && c.m) ? yhat : h->ws.ws_yhe;
     w.psi_direct = psi;
+    if (U2) { w.xe2 = const_cast<double *>(U2); w.ge2 = grad2; }
     w.ptab = h->params().table; w.pidx = h->params().idx;
     w.ctab = h->tab[TAB_CONSTR].table; w.cidx = h->tab[TAB_CONSTR].idx;
     w.dtab = h->tab[TAB_DISCS].table; w.didx = h->tab[TAB_DISCS].idx;
     w.rtab = h->tab[TAB_RATES].table; w.ridx = h->tab[TAB_RATES].idx;
     w.ftab = h->tab[TAB_FIELDS].table; w.fidx = h->tab[TAB_FIELDS].idx;
-    if (wave_path) launch_solo_eval(h, w, s, grad ? 1 : 0);
+    if (wave_path) launch_solo_eval(h, w, s, (grad ? 1 : 0) | (U2 ? 2 : 0));
     else launch_eval(h, w, s, nullptr, nullptr, grad ? B : 0, grad ? 0 : B);
     HIPCHK(hipGetLastError());
     return MPC_OK;
@@ -527,6 +528,21 @@ extern "C" int mpc_eval_cost_grad_wave(mpc_handle *h, int B, const double *x0, c
                                        const double *y, const double *Sigma, double *psi, double *grad, double *yhat, void *stream)
 {
     return eval_cost_grad(h, B, x0, cl, cl_index, U, y, Sigma, psi, grad, yhat, stream, true);
+}
+
+// Two points, one trip: the evaluation at U (cost, and gradient when grad is given) and the gradient at U2 side by side
+// in one wave, as a trip of the kinematic persistent kernel that carries a speculative gradient runs them (solo_halves:
+// nfe = 4, horizons of at most half a wave).
+extern "C" int mpc_eval_cost_grad_wave2(mpc_handle *h, int B, const double *x0, const double *cl, const int32_t *cl_index, const double *U,
+                                        const double *U2, const double *y, const double *Sigma, double *psi, double *grad, double *grad2,
+                                        double *yhat, void *stream)
+{
+    int rc = check_common(h, B, "mpc_eval_cost_grad_wave2"); if (rc) return rc;
+    if (B == 0) return MPC_OK;
+    if (!U2 || !grad2) return fail(MPC_E_ARG, "mpc_eval_cost_grad_wave2: null buffer");
+    if (!solo_halves(h->dc.model, h->dc.nfe, h->dc.N))
+        return fail(MPC_E_ARG, "mpc_eval_cost_grad_wave2: the kinematic model with nfe = 4 and N <= 32 (the half-wave form of the wide rollout)");
+    return eval_cost_grad(h, B, x0, cl, cl_index, U, y, Sigma, psi, grad, yhat, stream, true, U2, grad2);
 }
 
 extern "C" int mpc_prox_step(mpc_handle *h, int B, const double *x, const double *grad, const double *gamma,

@@ -427,6 +427,111 @@ __device__ __forceinline__ void kin_wide_rollout(const DevCfg &c, const double (
     if (stage_lane) { put(lane + 1, 0, epx); put(lane + 1, 1, epy); put(lane + 1, 2, eph); put(lane + 1, 3, ev); }
 }
 
+// The half-wave form: TWO requests of one agent side by side, request h on lanes 32 h .. 32 h + 31 (the persistent
+// kernel's evaluation and its speculative gradient, mpc_solo.hpp).  N <= 32.  The serial recursion of phase A is issued
+// once and each lane walks its own half's request; phase B takes ceil(4 N / 32) passes of one RK4 step per lane of the
+// half; phase C sums each half's increments in step order.  readlane is wave-uniform and cannot serve two halves: the
+// per-stage inputs and the increments go through the half's exchange area in LDS, `xch` (11 N doubles: inputs [N][3],
+// increments [4 N][2]), and the loads of the next stage are issued before the current stage's chain.  The fast-range
+// test is per half: both in range -- the common case -- is the one-request kernel's fast branch; otherwise each half
+// takes, lane by lane, the form the one-request kernel would choose for it.  Same helper functions, same order of every
+// sum: a request gets the bits kin_wide_rollout gives it.  d / dl are the inputs of stage `lane & 31` of the lane's own
+// half (lanes >= N of a half: zeros); `tj` is the half's trajectory [(N + 1)][4].  All 64 lanes must be active.
+__device__ __forceinline__ void kin_wide_rollout2(const DevCfg &c, const double (&x0)[4], double d, double dl, int lane,
+                                                  double *xch, double *tj)
+{
+    const int N = c.N, hl = lane & 31;
+    const bool stage_lane = hl < N, hi = lane >= 32;
+    StageInput<KIN> u;
+    prep_input(c, d, dl, u);
+    double *const uin = xch, *const inc = xch + 3 * N;
+    if (stage_lane) { uin[3 * hl] = u.ad; uin[3 * hl + 1] = u.beta; uin[3 * hl + 2] = u.sb_lr; }
+    if (hl == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) tj[i] = x0[i];
+    }
+    __builtin_amdgcn_wave_barrier();                     // LDS is in order within a wave
+    // ---- phase A: lane s & 31 of a half keeps the (heading, speed) at the start of RK4 step s, lane k the state at the
+    // end of stage k; pass p: stages 8 p .. 8 p + 7 = RK4 steps 32 p .. 32 p + 31
+    double ph = x0[2], v = x0[3];
+    constexpr int PASS = 4;
+    double cph[PASS] = {0.0, 0.0, 0.0, 0.0}, cv[PASS] = {0.0, 0.0, 0.0, 0.0}, eph = 0.0, ev = 0.0;
+    int gen = 0;                                         // bit p: this lane's step of pass p belongs to a stage outside the fast range
+    bool anygen = false;                                 // uniform: some stage of either half is outside
+    double n_ad = uin[0], n_beta = uin[1], n_sb = uin[2];
+#pragma unroll
+    for (int p = 0; p < PASS; p++) {
+        const int k1 = N < 8 * (p + 1) ? N : 8 * (p + 1);
+        for (int k = 8 * p; k < k1; k++) {
+            StageInput<KIN> uk;
+            uk.ad = n_ad; uk.beta = n_beta; uk.sb_lr = n_sb;
+            const int kn = k + 1 < N ? k + 1 : k;
+            n_ad = uin[3 * kn]; n_beta = uin[3 * kn + 1]; n_sb = uin[3 * kn + 2];
+            const double xs[4] = {0.0, 0.0, ph, v};
+            const unsigned long long bad = __ballot(!kin4_in_range(c, uk, xs));   // (every lane of a half holds the same values)
+            const bool inr = (hi ? bad >> 32 : bad & 0xffffffffull) == 0ull;      // this half's stage is inside
+            anygen = anygen || bad != 0ull;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (hl == ((4 * k + j) & 31)) { cph[p] = ph; cv[p] = v; gen |= inr ? 0 : 1 << p; }
+                KinRK kr;
+                if (__builtin_expect(bad == 0ull, 1)) { kin_rk(c, uk, v, kr); kin_next(c, kr, ph, v); }
+                else {                                   // (uniform; rare) both forms, each lane keeps its half's
+                    double pha = ph, va = v;
+                    kin_rk(c, uk, v, kr); kin_next(c, kr, pha, va);
+                    kin_gen_rk(c, uk, v, kr); kin_gen_next(c, kr, ph, v);
+                    ph = inr ? pha : ph; v = inr ? va : v;
+                }
+            }
+            if (hl == k) { eph = ph; ev = v; }
+        }
+    }
+    // ---- phase B: position increment of RK4 step s = 32 p + hl of the lane's half
+#pragma unroll
+    for (int p = 0; p < PASS; p++) {
+        const int s = 32 * p + hl;
+        if (32 * p >= 4 * N) break;                      // uniform
+        const bool on = (s >> 2) < N;                    // lanes past the horizon compute a copy, unused
+        const int k = on ? (s >> 2) : N - 1;
+        StageInput<KIN> uk;
+        uk.ad = uin[3 * k]; uk.beta = uin[3 * k + 1]; uk.sb_lr = uin[3 * k + 2];
+        const bool g = ((gen >> p) & 1) != 0 && on;
+        KinRK kr;
+        double dx, dy;
+        kin_rk(c, uk, cv[p], kr);
+        kin_increment(c, uk, cph[p], kr, !g, dx, dy);
+        if (anygen) {                                    // uniform; rare
+            double gx, gy;
+            kin_gen_rk(c, uk, g ? cv[p] : 0.0, kr);
+            kin_gen_increment(c, uk, g ? cph[p] : 0.0, g ? cv[p] : 0.0, kr, gx, gy);
+            dx = g ? gx : dx; dy = g ? gy : dy;
+        }
+        if (on) { inc[2 * s] = dx; inc[2 * s + 1] = dy; }
+    }
+    __builtin_amdgcn_wave_barrier();
+    // ---- phase C: positions, summed in step order; lane k of a half keeps the position at the end of stage k
+    double px = x0[0], py = x0[1], epx = 0.0, epy = 0.0;
+    double nx[4], ny[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) { nx[j] = inc[2 * j]; ny[j] = inc[2 * j + 1]; }
+    for (int k = 0; k < N; k++) {
+#pragma clang fp contract(off)
+        double ix[4], iy[4];
+        const int kn = k + 1 < N ? k + 1 : k;
+#pragma unroll
+        for (int j = 0; j < 4; j++) { ix[j] = nx[j]; iy[j] = ny[j]; }
+#pragma unroll
+        for (int j = 0; j < 4; j++) { nx[j] = inc[2 * (4 * kn + j)]; ny[j] = inc[2 * (4 * kn + j) + 1]; }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            px = px + ix[j];
+            py = py + iy[j];
+        }
+        if (hl == k) { epx = px; epy = py; }
+    }
+    if (stage_lane) { tj[(hl + 1) * 4] = epx; tj[(hl + 1) * 4 + 1] = epy; tj[(hl + 1) * 4 + 2] = eph; tj[(hl + 1) * 4 + 3] = ev; }
+}
+
 template <bool PA = false>
 __global__ void __launch_bounds__(256)
 rollout_wide_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ lists,

@@ -15,10 +15,12 @@
 // thread-per-agent stage_forward on one lane otherwise; stage k of the horizon on lane k
 // (stage_record); the adjoint recursion on one lane (adjoint_rec) -- so an agent gets the
 // same bits whichever path serves it, and the host may switch on the live request counts.
-// Speculative gradients: with the lane-serial rollout (Pacejka model) the speculative request of a
-// round is evaluated beside the regular one, on the other half of the wave (solo_dual); with the
-// wave-per-request rollout (kinematic model) two evaluations would run one after the other, so none is
-// issued -- one that is pending when the agent arrives is consumed either way.
+// Speculative gradients: the speculative request of a round is evaluated beside the regular one, on the
+// other half of the wave -- with the lane-serial rollout (Pacejka model) always (solo_dual); with the
+// wave-per-request rollout (kinematic model) on the trips that carry one (solo_halves): those trips run the
+// half-wave form of the rollout (kin_wide_rollout2), whose serial recursion serves both halves in the same
+// instructions, and every other trip keeps the 64-lane form.  Horizons beyond half a wave issue none -- one
+// that is pending when the agent arrives is consumed either way.
 #pragma once
 #include "mpc_eval.hpp"
 
@@ -33,8 +35,16 @@ constexpr int SOLO_WAVES = 1; // one wave per workgroup: nothing is shared betwe
 // instructions.
 __host__ __device__ inline bool solo_wide(int model, int nfe) { return model == KIN && nfe == 4; }
 __host__ __device__ inline bool solo_dual(int model, int nfe, int N) { return !solo_wide(model, nfe) && N <= 32; }
+// The same for the wave-per-request rollout, trip by trip: a trip that carries a speculative gradient runs the half-wave
+// form of the rollout (kin_wide_rollout2: the request on lanes 0 .. 31, the speculative gradient on lanes 32 .. 63), a
+// trip that carries one request keeps all 64 lanes.  The iteration that consumes the gradient saves a dependent trip.
+__host__ __device__ inline bool solo_halves(int model, int nfe, int N) { return solo_wide(model, nfe) && N <= 32; }
 
 // doubles of LDS one wave needs: history copy (MC < 0), trajectory, stage records (twice when dual)
+// (solo_halves: the second trajectory and record block lie ON the history copy where that is large enough -- the state
+// machine fills and reads the copy inside one step, between two evaluations it holds nothing (advance_agent with
+// hist_ready = false: hist_dma and hist_wait in PH_LS_INIT), and LDS is what bounds this kernel's waves per CU at the
+// headline's shapes; solo_second_on_hist)
 // Lookahead (Pacejka model, N <= 16, no constraints): FOUR evaluations side by side, 16 lanes each -- the one the state
 // machine asked for, its speculative gradient, and candidates the state machine is going to ask for if the test it is
 // about to make fails (the next line-search trial points; the prox points of the next descent-lemma doublings),
@@ -53,11 +63,21 @@ struct LaSlot { const double *in; double *grad; double *psi; int live, is_g; }; 
 // doubles of LDS the cache and the slot descriptors take
 __host__ __device__ inline size_t la_lds_doubles(int n) { return (size_t)LA_ENTRIES * (2 * n + 2) + LA_SLOTS * 4 + 8; }
 
+// The persistent kernel hands advance_agent a history copy that is NOT filled ahead of the step (hist_ready): the copy is
+// filled, waited for and read inside PH_LS_INIT of one step, so between two steps -- during an evaluation -- it is free.
+// The overlay below is sound on that condition alone; a kernel that prefetches the history across an evaluation (as
+// mpc_step_body.hpp does) sets this to true and gets the second half's LDS behind the first half's instead.
+constexpr bool SOLO_HIST_PREFETCH = false;
+template <int MODEL> __host__ __device__ inline bool solo_second_on_hist(int N, int n, int M, bool hist)
+{
+    return !SOLO_HIST_PREFETCH && hist && (size_t)2 * M * n >= (size_t)(N + 1) * ModelDim<MODEL>::NX + (size_t)(JacRec<MODEL>::SIZE + 1) * N;
+}
 template <int MODEL> __host__ __device__ inline size_t solo_lds_doubles(int nfe, int N, int n, int M, bool hist, bool la = false)
 {
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE;
     const size_t per = (size_t)(N + 1) * NX + (size_t)(JS + 1) * N;
-    return (hist ? (size_t)2 * M * n : 0) + (la ? LA_SLOTS : solo_dual(MODEL, nfe, N) ? 2 : 1) * per + (la ? la_lds_doubles(n) : 0);
+    const bool second = solo_halves(MODEL, nfe, N) && !solo_second_on_hist<MODEL>(N, n, M, hist);
+    return (hist ? (size_t)2 * M * n : 0) + (la ? LA_SLOTS : solo_dual(MODEL, nfe, N) || second ? 2 : 1) * per + (la ? la_lds_doubles(n) : 0);
 }
 
 // the evaluation(s) agent `a` asked for (req: REQ_GRAD or REQ_COST, plus REQ_SPEC) by its whole wave
@@ -73,16 +93,19 @@ struct SoloClk { long long roll = 0, recs = 0, adj = 0; };
 // agent's row, whose address is wave-uniform -- and / or the rate table (the rate forms: a trailing RateTab, last) -- lane k
 // takes u_{k-1} and u_{k+1} from the row it evaluates (`row`: xe, or xe2 on the speculative half), u_{-1} from the table
 // -- and, behind the RateTab, the field table (the field forms) -- lane k hands on the address of its stage's sources
+// alt: where the second half's trajectory and record block lie (solo_halves); nullptr: behind the first half's (solo_dual)
 template <int MODEL, class... DS>
 __device__ __forceinline__ void solo_eval(const DevCfg &c, const Workspace &w, int a, int lane, int req,
-                                          double *traj, double *rec SOLO_CLK_ARG, const DS &...ds)
+                                          double *traj, double *rec, double *alt SOLO_CLK_ARG, const DS &...ds)
 {
 #if MPC_DEV_STAMP == 5
     long long tclk = __builtin_amdgcn_s_memrealtime();
 #endif
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE;
     const int N = c.N, n = c.n;
-    const bool wide = solo_wide(MODEL, c.nfe), dual = solo_dual(MODEL, c.nfe, N);   // uniform
+    const bool wide = solo_wide(MODEL, c.nfe);                                      // uniform
+    const bool halves = solo_halves(MODEL, c.nfe, N) && (req & REQ_SPEC) != 0;      // uniform: this trip carries two requests
+    const bool dual = solo_dual(MODEL, c.nfe, N) || halves;
     const int half = dual ? lane >> 5 : 0, hl = dual ? lane & 31 : lane;
     const bool ch2 = half == 1;                                     // the speculative channel: xe2 -> ge2 only
     const bool live = !ch2 || (req & REQ_SPEC) != 0;
@@ -90,13 +113,22 @@ __device__ __forceinline__ void solo_eval(const DevCfg &c, const Workspace &w, i
     const double *__restrict__ row = (ch2 ? w.xe2 : w.xe) + (size_t)a * n;
     const bool stage_lane = live && hl < N;
     const double d = stage_lane ? row[2 * hl] : 0.0, dl = stage_lane ? row[2 * hl + 1] : 0.0;
-    double *const tj = traj + (size_t)half * ((size_t)(N + 1) * NX);
-    double *const rc = rec + (size_t)half * ((size_t)(JS + 1) * N);
+    double *const tj = half && alt ? alt : traj + (size_t)half * ((size_t)(N + 1) * NX);
+    double *const rc = half && alt ? alt + (size_t)(N + 1) * NX : rec + (size_t)half * ((size_t)(JS + 1) * N);
     double x0[NX];
 #pragma unroll
     for (int i = 0; i < NX; i++) x0[i] = w.x0[(size_t)a * NX + i];
     if constexpr (MODEL == KIN) {
-        if (wide) kin_wide_rollout(c, x0, d, dl, lane, [=](int k, int i, double v) { tj[k * 4 + i] = v; });
+        // (the half-wave form's exchange area: the half's record block, which is written after the rollout)
+        static_assert(11 <= JS + 1, "kin_wide_rollout2's exchange area fits a record block");
+        // The scalars the serial recursion reads at every step, as registers of their own: the DevCfg arrives in sixteen-
+        // register tuples, this kernel spills scalar registers by the hundred, and a tuple that is live for the sake of
+        // one field was reloaded whole, three times per stage, inside phase A (4 340 lane reads in the kernel against
+        // 2 564 with the copies; profiles/r19_solo_dual.txt).  The values are the DevCfg's: same bits.
+        DevCfg cr = c;
+        asm volatile("" : "+s"(cr.h), "+s"(cr.friction), "+s"(cr.N), "+s"(cr.lf), "+s"(cr.lr));
+        if (halves) kin_wide_rollout2(cr, x0, d, dl, lane, rc, tj);
+        else if (wide) kin_wide_rollout(cr, x0, d, dl, lane, [=](int k, int i, double v) { tj[k * 4 + i] = v; });
     }
     if constexpr (MODEL == PAC) {
         if (hl < 4 && live) {                              // the serial recurrence on a quad of lanes (rhs_quad)
@@ -155,7 +187,7 @@ __device__ __forceinline__ void solo_eval(const DevCfg &c, const Workspace &w, i
     if constexpr (MODEL == KIN) {
         // (the kinematic adjoint by a quad of lanes: mpc_eval.hpp adjoint_rec_quad_kin -- same bits, a third of the chain)
         if (hl < 4 && live) {
-            double *psi_out = w.psi_direct ? w.psi_direct + a : !ch2 ? w.rec + (size_t)a * REC + R_PSIE : nullptr;
+            double *psi_out = ch2 ? nullptr : w.psi_direct ? w.psi_direct + a : w.rec + (size_t)a * REC + R_PSIE;   // (the speculative half: the gradient alone)
             adjoint_rec_quad_kin(c, is_g, hl, [=](int k, int f) { return rc[f * N + k]; }, psi_out,
                                  (ch2 ? w.ge2 : w.ge) + (size_t)a * n);
         }
@@ -246,6 +278,8 @@ __global__ void __launch_bounds__(256) solo_list_kernel(const Workspace w, int *
 }
 
 // K1 alone through the wave-per-agent evaluation (standalone entry point, parity tests): agent = block
+// (want_grad bit 1: "two points, one trip" -- the speculative gradient xe2 -> ge2 rides beside the request, as on a trip
+// of the persistent kernel that carries REQ_SPEC; the host asks for it where solo_halves holds)
 template <int MODEL, bool PA = false, class... CT>
 __global__ void __launch_bounds__(64, 1) solo_eval_kernel(const DevCfg c_, const WsArg<PA> w, int want_grad, CT... ct)
 {
@@ -261,15 +295,18 @@ __global__ void __launch_bounds__(64, 1) solo_eval_kernel(const DevCfg c_, const
     const DevCfg &c = PA ? cm_ : c_;
     double *traj = s_solo;
     double *rec = traj + (size_t)(c.N + 1) * ModelDim<MODEL>::NX;
+    double *alt = nullptr;
+    if (solo_halves(MODEL, c.nfe, c.N)) alt = rec + (size_t)(JacRec<MODEL>::SIZE + 1) * c.N;
+    const int ereq = ((want_grad & 1) ? REQ_GRAD : REQ_COST) | ((want_grad & 2) ? REQ_SPEC : 0);
 #if MPC_DEV_STAMP == 5
     SoloClk clk;
-    if constexpr (DA) solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, want_grad ? REQ_GRAD : REQ_COST, traj, rec, clk, ct...);
+    if constexpr (DA) solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, ereq, traj, rec, alt, clk, ct...);
     else
-    solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, want_grad ? REQ_GRAD : REQ_COST, traj, rec, clk);
+    solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, ereq, traj, rec, alt, clk);
 #else
-    if constexpr (DA) solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, want_grad ? REQ_GRAD : REQ_COST, traj, rec, ct...);
+    if constexpr (DA) solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, ereq, traj, rec, alt, ct...);
     else
-    solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, want_grad ? REQ_GRAD : REQ_COST, traj, rec);
+    solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, ereq, traj, rec, alt);
 #endif
 }
 
@@ -451,10 +488,15 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
     extern __shared__ double s_solo[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const size_t per_wave = solo_lds_doubles<MODEL>(c.nfe, c.N, c.n, c.M, MC < 0);
-    const bool spec = solo_dual(MODEL, c.nfe, c.N);      // speculative gradients only where they ride along
+    const bool spec = solo_dual(MODEL, c.nfe, c.N) || solo_halves(MODEL, c.nfe, c.N);   // speculative gradients only where they ride along
     double *hist = s_solo + (size_t)wv * per_wave;
     double *traj = hist + (MC < 0 ? (size_t)2 * c.M * c.n : 0);
     double *rec = traj + (size_t)(c.N + 1) * ModelDim<MODEL>::NX;
+    // the second half's trajectory and records (solo_halves): on the history copy, idle between two steps of the state
+    // machine, where it is large enough (solo_second_on_hist), else behind the first half's
+    double *alt = nullptr;
+    if (solo_halves(MODEL, c.nfe, c.N))
+        alt = solo_second_on_hist<MODEL>(c.N, c.n, c.M, MC < 0) ? hist : rec + (size_t)(JacRec<MODEL>::SIZE + 1) * c.N;
     const int total = list ? ctr[1] : w.B;
     if constexpr (LA) {
         // (one element per lane, one wave per workgroup; four trajectories, then four record blocks, then the cache)
@@ -500,7 +542,7 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
         }
 #if MPC_DEV_STAMP == 5
         const long long st0 = __builtin_amdgcn_s_memrealtime();
-        long long ntrip = 0, t_adv = 0;
+        long long ntrip = 0, t_adv = 0, nhess = 0;   // nhess: trips that are the Hessian-vector gradient of PH_AFTER_DL alone
         SoloClk clk;
 #endif
         for (long long trip = 0; trip < max_trips; trip++) {
@@ -508,31 +550,32 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
             const long long ta = __builtin_amdgcn_s_memrealtime();
 #endif
             const AgentIn<NE> in = load_agent<NE>(c, w, a, lane);
-            const int req = advance_agent<NE, MC, true, false, BOX, CON, /*PRED=*/false>(c, w, a, lane, in, hist, false, /*allow_spec=*/spec, false, 1 << 30, bx, cn);
+            const int req = advance_agent<NE, MC, true, false, BOX, CON, /*PRED=*/false>(c, w, a, lane, in, hist, /*hist_ready=*/SOLO_HIST_PREFETCH, /*allow_spec=*/spec, false, 1 << 30, bx, cn);
             if ((req & (REQ_GRAD | REQ_COST)) == 0) break;              // uniform: the agent is done
 #if MPC_DEV_STAMP == 5
             t_adv += __builtin_amdgcn_s_memrealtime() - ta;
-            if constexpr (FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...));
-            else if constexpr (DA && RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...));
-            else if constexpr (RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk, pack_get<RateTab>(bt...));
-            else if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk, pack_get<DiscTab>(bt...));
+            if ((req & (REQ_GRAD | REQ_COST | REQ_SPEC)) == REQ_GRAD && (rec_int_of(w.rec[(size_t)a * REC + R_PHASE]) & PH_MASK) == PH_W_HESS) nhess++;
+            if constexpr (FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...));
+            else if constexpr (DA && RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...));
+            else if constexpr (RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<RateTab>(bt...));
+            else if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<DiscTab>(bt...));
             else
-            solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, clk);
+            solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk);
             ntrip++;
 #else
-            if constexpr (FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...));
-            else if constexpr (DA && RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...));
-            else if constexpr (RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, pack_get<RateTab>(bt...));
-            else if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, pack_get<DiscTab>(bt...));
+            if constexpr (FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...));
+            else if constexpr (DA && RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...));
+            else if constexpr (RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<RateTab>(bt...));
+            else if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<DiscTab>(bt...));
             else
-            solo_eval<MODEL>(cm, w, a, lane, req, traj, rec);
+            solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt);
 #endif
         }
 #if MPC_DEV_STAMP == 5
         if (lane == 0 && i < DEV_STAMPS) {   // (one buffer for all groups: the claim index of the group whose kernel ran last wins)
             g_dev_stamps[4 * i] = st0; g_dev_stamps[4 * i + 1] = __builtin_amdgcn_s_memrealtime();
             g_dev_stamps[4 * i + 2] = ntrip | (t_adv << 20); g_dev_stamps[4 * i + 3] = a | (clk.roll << 20);
-            if (i + 32768 < DEV_STAMPS) { g_dev_stamps[4 * (i + 32768)] = clk.recs; g_dev_stamps[4 * (i + 32768) + 1] = clk.adj; }
+            if (i + 32768 < DEV_STAMPS) { g_dev_stamps[4 * (i + 32768)] = clk.recs; g_dev_stamps[4 * (i + 32768) + 1] = clk.adj; g_dev_stamps[4 * (i + 32768) + 2] = nhess; }
         }
 #endif
     }

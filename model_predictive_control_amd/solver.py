@@ -464,6 +464,25 @@ class BatchedMPC:
                       _ptr(grad), _ptr(yhat), self._stream()))
         return psi, grad, yhat
 
+    def eval_cost_grad_pair(self, x0, centerline, U, U2, y=None, Sigma=None, cl_index=None, want_grad=True):
+        """K1 at two points of every agent in one trip of the wave-per-agent evaluation: psi[B], grad[B, 2N] (or None)
+        and yhat[B, m] (or None) at U, and grad2[B, 2N] at U2 -- the request and the speculative gradient of a trip of
+        the kinematic persistent kernel (nfe = 4, N <= 32).  Same bits as two calls of eval_cost_grad."""
+        B = x0.shape[0]
+        self._chk(x0, (B, self.nx), "x0"); self._chk(U, (B, self.n), "U"); self._chk(U2, (B, self.n), "U2")
+        cl = self._centerline(centerline, cl_index, B)
+        if self.m:
+            if y is None or Sigma is None:
+                raise ValueError("y and Sigma are required when the problem has constraints")
+            self._chk(y, (B, self.m), "y"); self._chk(Sigma, (B, self.m), "Sigma")
+        psi = self._empty(B)
+        grad = self._empty(B, self.n) if want_grad else None
+        grad2 = self._empty(B, self.n)
+        yhat = self._empty(B, self.m) if self.m else None
+        _lib.check(self.lib.mpc_eval_cost_grad_wave2(self._h, B, _ptr(x0), _ptr(cl), _ptr(cl_index), _ptr(U), _ptr(U2), _ptr(y),
+                                                     _ptr(Sigma), _ptr(psi), _ptr(grad), _ptr(grad2), _ptr(yhat), self._stream()))
+        return psi, grad, grad2, yhat
+
     # ------------------------------------------------------------------ solver pieces
     def prox_step(self, x, grad, gamma):
         """K2: xhat, p, [||p||^2, grad'p]."""

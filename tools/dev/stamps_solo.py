@@ -39,6 +39,17 @@ for i in order:
 i = order[0]
 print("the longest agent, per trip: load + step of the state machine %.1f us, rollout %.1f us, stage records %.1f us, adjoint %.1f us (of %.1f us)"
       % (t_adv[i] / 100.0 / trips[i], t_roll[i] / 100.0 / trips[i], t_recs[i] / 100.0 / trips[i], t_adj[i] / 100.0 / trips[i], dur[i] / trips[i]))
+# trips that are the Hessian-vector gradient of PH_AFTER_DL alone (a plain REQ_GRAD that leaves the agent in PH_W_HESS):
+# what a speculative gradient riding beside the cost request saves (solo_halves).  The counter is written by a library
+# built from mpc_solo.hpp as of solo_halves or later: an older -DMPC_DEV_STAMP=5 build leaves that column as it found
+# it, and the line below then means nothing.
+nhess = full[32768:32768 + n, 2]
+top = np.argsort(-dur)[:64]
+print("Hessian-vector trips: the longest agent %d of %d trips (%.1f %%); the 64 longest agents %d of %d (%.1f %%, per agent min %.1f %% max %.1f %%); all agents %d of %d (%.1f %%)"
+      % (nhess[i], trips[i], 100.0 * nhess[i] / max(1, trips[i]), nhess[top].sum(), trips[top].sum(), 100.0 * nhess[top].sum() / max(1, trips[top].sum()),
+         (100.0 * nhess[top] / np.maximum(1, trips[top])).min(), (100.0 * nhess[top] / np.maximum(1, trips[top])).max(),
+         nhess.sum(), trips.sum(), 100.0 * nhess.sum() / max(1, trips.sum())))
+print("second-longest agent done after %.2f ms; spec issued %d used %d" % (np.sort(dur)[-2] / 1e3, info["spec_issued"], info["spec_used"]))
 late = (t0 - base) / 100.0 > 50.0
 print("agents claimed later than 50 us after the start: %d; the latest claim at %.2f ms; work claimed late: %.1f ms of %.1f ms of wave time"
       % (late.sum(), (t0.max() - base) / 1e5, dur[late].sum() / 1e3, dur.sum() / 1e3))
