@@ -325,6 +325,66 @@ int mpc_closed_loop_traffic_field(mpc_handle *h, int B, int T, int shift, int G,
                                   double *lambda, double *table, double *traj_x, double *traj_u, int32_t *traj_opp,
                                   double *traj_clear, int32_t *fail_count, double *stats, void *stream);
 
+/* Road cost: a per-stage lane target, soft road edges and a per-stage speed target -- a seventh table of P rows in device
+ * memory and one row index per agent; like the disc and field tables its data varies with the stage.  One row, all
+ * doubles: [N][MPC_NROAD], MPC_ROAD_ROW(N) of them.  A stage's entry is [off, w_off, lo, w_lo, hi, w_hi, v_tgt, w_v]:
+ * the target-lane well w_off (e - off)^2 and the road boundary w_lo (e - lo)^2 below lo, w_hi (e - hi)^2 above hi, 0
+ * between (the road part of the reference's driving potential, restated in this project's frame), and w_v (sp - v_tgt)^2
+ * on the speed.  e is the signed lateral offset from the centerline, exactly the lane band's expression
+ * (MPC_CONSTR_LANE): POSITIVE TO THE RIGHT of the direction of travel -- on a line y = 0.5 driven towards +x,
+ * e = -(y - 0.5).  With (nx, ny) the nearest centerline point of the position at the end of stage k, (qx, qy) its
+ * successor and x the state at the end of the stage (x_{k+1}, where every stage term is taken), stage k's cost -- behind
+ * the risk field (on a handle of MPC_CONSTR_DISCS: behind the move penalty) and before the ALM terms -- gets, every
+ * operation rounded on its own and in this order:
+ *     wx = qx - nx,  wy = qy - ny,  nrm = sqrt(wx wx + wy wy),  e = ((x[0] - nx) wy - (x[1] - ny) wx) / nrm,  de = 0
+ *     w_off != 0:                  t = e - off,  a = w_off t,  L_k = L_k + a t,  de = de + 2 a
+ *     w_lo != 0 and q = e - lo < 0:              a = w_lo q,   L_k = L_k + a q,  de = de + 2 a
+ *     w_hi != 0 and p = e - hi > 0:              a = w_hi p,   L_k = L_k + a p,  de = de + 2 a
+ *     gradient request, any of the three weights != 0:
+ *         dL/dx_k[0] = dL/dx_k[0] + (de wy) / nrm,   dL/dx_k[1] = dL/dx_k[1] - (de wx) / nrm
+ *     w_v != 0:  ev = sp - v_tgt (sp as in the stage cost: x[3], or sqrt(x[3] x[3] + x[4] x[4]) on the Pacejka model),
+ *                a = w_v ev,  L_k = L_k + a ev
+ *                gradient request: kinematic  dL/dx_k[3] = dL/dx_k[3] + 2 a;
+ *                                  Pacejka    dL/dx_k[3] = dL/dx_k[3] + ((2 a) x[3]) / sp,  dL/dx_k[4] likewise with x[4]
+ * psi stays the sum of the stage costs in stage order; the adjoint recursion carries the state gradient like any other.
+ * A part whose weight is 0 is skipped by a branch: it adds nothing, not even a signed zero, so a table of zero weights
+ * gives the bits of the call without a table, whatever its other words are; with no lateral weight set e and nrm are not
+ * computed.  Where two neighbouring centerline points coincide (nrm == 0) the term is what the lane band is there today:
+ * e = 0 / 0 is not a number, and so is the cost of every stage that lands there with a lateral weight set; a centerline
+ * without repeated points never gets there.  Likewise on the Pacejka model at sp == 0 with w_v != 0: the speed gradient
+ * divides by sp and is 0 / 0 there, as the stage cost's own speed term is.  One device function (road_term) serves the four evaluation routes (K1b,
+ * the fused K1b + K1c kernel, the wave evaluation, the persistent kernel): a request gets the same bits whichever serves
+ * it.  It is a cost, not a constraint: no multiplier; the step kernel, the prox and the constraint bounds do not know it.
+ * So it is allowed on handles of EVERY constr_mode -- on a handle of MPC_CONSTR_DISCS "keep out of these discs and stay
+ * on the road" is one solve -- beside the parameter, bounds, rate and field tables and beside the disc table; the terms
+ * add up.  The table is read by mpc_eval_cost_grad(_wave), mpc_solve_batch(_async), mpc_solve_active and the closed loops
+ * (which read it as it is bound: stage k of every re-plan reads entry k of the agent's row); mpc_stage_cost, mpc_rhs,
+ * mpc_rollout and mpc_prox_step do not read it.
+ * mpc_default_roads (host only): a row of zeros, MPC_ROAD_ROW(cfg->N) doubles.
+ * mpc_set_agent_roads: the semantics of the other tables.  table == NULL unbinds; bound, the calls above use row index[b]
+ * for agent b and return MPC_E_ARG for a batch size other than B; bound beside other tables it is for the same B.  table
+ * [P][MPC_ROAD_ROW(N)] and index [B] are DEVICE memory of the caller, read at every call: rows may be rewritten in place
+ * between calls.  The P rows are checked once, at bind time: every value finite, no weight negative, and lo <= hi on
+ * every stage where w_lo and w_hi are both non-zero; index ranges are the caller's to check (the Python front end does).
+ * Refused (MPC_E_ARG) while an asynchronous solve is in flight, and while a constraint table is bound -- as
+ * mpc_set_agent_constraints is while a road table is bound (the kernels have no form that takes both).
+ * mpc_roads_from_script: rows that move in time, asynchronous on `stream`.  script [Ps][Lt][MPC_NROAD] holds one sample
+ * per Ts, sidx [B] (int32, 0 <= sidx[b] < Ps: the caller's to check) one script row per agent; row b of table
+ * [B][MPC_ROAD_ROW(N)] receives, for k < N, sample min(ti + k, Lt - 1) of script row sidx[b] -- or sample (ti + k) mod Lt
+ * with wrap != 0: the time rule of mpc_discs_from_obstacles.  A plain copy; the samples are not checked (the binder
+ * checked the table's rows once, the script's are the caller's to keep valid).  Although the copy reads no bound table,
+ * B must be the B of whatever tables are bound (MPC_E_ARG otherwise), as for mpc_discs_from_obstacles.  table may be the bound road table: a host
+ * loop of mpc_roads_from_script, mpc_solve_batch and mpc_rollout (or of mpc_roads_from_script and mpc_closed_loop with
+ * T = 1) advances a lane change or a speed profile through a closed loop without uploading B x N x 8 doubles per step.
+ * All three are device memory.  No closed loop performs this gather itself, and profiles are indexed by time, not by
+ * track position. */
+#define MPC_NROAD 8
+#define MPC_ROAD_ROW(N) (MPC_NROAD * (N))
+int mpc_default_roads(const mpc_config *cfg, double *row);
+int mpc_set_agent_roads(mpc_handle *h, const double *table, int P, const int32_t *index, int B);
+int mpc_roads_from_script(mpc_handle *h, int B, int Lt, int wrap, int ti, const double *script, const int32_t *sidx,
+                          double *table, void *stream);
+
 /* a-1(car_dynamics.py:93-132 / dynamics.py:67-119,:144-173): dx[B][nx] = f(x[B][nx], u[B][2]) */
 int mpc_rhs(mpc_handle *h, int B, const double *x, const double *u, double *dx, void *stream);
 

@@ -57,6 +57,7 @@ EXPORTS = [
     "mpc_default_discs", "mpc_set_agent_discs", "mpc_discs_from_plans",
     "mpc_default_rates", "mpc_set_agent_rates",
     "mpc_default_fields", "mpc_set_agent_fields", "mpc_fields_from_plans", "mpc_closed_loop_traffic_field",
+    "mpc_default_roads", "mpc_set_agent_roads", "mpc_roads_from_script",
     "mpc_opponents_from_plans", "mpc_closed_loop_traffic",
     "mpc_obstacles_select", "mpc_discs_from_obstacles", "mpc_fields_from_obstacles", "mpc_closed_loop_obstacles",
     "mpc_track_init", "mpc_track_windows", "mpc_track_locate", "mpc_track_select", "mpc_closed_loop_track",
@@ -69,6 +70,7 @@ NCONSTR = 19    # MPC_NCONSTR: doubles per row of the per-agent constraint table
 NRATE = 4       # MPC_NRATE: doubles per row of the per-agent rate table, [w_d, w_delta, d_prev, delta_prev]
 NFIELD = 2      # MPC_NFIELD: sources of the risk field per stage (== NDISC: one opp [B, 2] serves both)
 NFSRC = 8       # MPC_NFSRC: doubles per source, [cx, cy, c, s, A, kx, ky, alpha]; a row of the field table is [N][NFIELD][NFSRC]
+NROAD = 8       # MPC_NROAD: doubles per stage of the road table, [off, w_off, lo, w_lo, hi, w_hi, v_tgt, w_v]; a row is [N][NROAD]
 NDISC = 2       # MPC_NDISC: keep-out discs per stage; a row of the disc table is [N][NDISC][3] = (cx, cy, r)
 SCENE_MAX = 64  # MPC_SCENE_MAX: agents per scene at most (mpc_opponents_from_plans, mpc_closed_loop_traffic)
 # columns of a constraint row, by field name (include/mpc_hip.h: mpc_set_agent_constraints)
@@ -195,6 +197,9 @@ def load():
     L.mpc_set_agent_fields.argtypes = [vp, vp, ci, vp, ci]
     L.mpc_fields_from_plans.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.mpc_closed_loop_traffic_field.argtypes = [vp, ci, ci, ci, ci, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mpc_default_roads.argtypes = [cp, C.POINTER(C.c_double)]
+    L.mpc_set_agent_roads.argtypes = [vp, vp, ci, vp, ci]
+    L.mpc_roads_from_script.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp]
     L.mpc_opponents_from_plans.argtypes = [vp, ci, ci, ci, vp, vp, C.c_double, vp, vp, vp]
     L.mpc_closed_loop_traffic.argtypes = [vp, ci, ci, ci, ci, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mpc_obstacles_select.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, C.c_double, vp, vp, vp]
@@ -491,6 +496,44 @@ def obstacle_tracks(cfg, centres=None, radii=None, sources=None):
     if tab.shape[0] < 1 or not 1 <= tab.shape[1] <= SCENE_MAX or tab.shape[2] < 1:
         raise ValueError(f"{who}: need scenes >= 1, 1 <= K <= {SCENE_MAX} obstacles and Lt >= 1 samples, got {tab.shape[:3]}")
     return np.ascontiguousarray(tab)
+
+
+def default_roads(cfg):
+    """mpc_default_roads: the row of the road table in which no part is on at any stage, float64 [NROAD * N] of zeros."""
+    return _default_row("mpc_default_roads", NROAD * int(cfg.N), cfg)
+
+
+def road_rows(N, offset=0.0, w_offset=0.0, lo=0.0, w_lo=0.0, hi=0.0, w_hi=0.0, v_target=0.0, w_speed=0.0):
+    """A road table for BatchedMPC.set_agent_roads, on the host: float64 [P, N, NROAD], stage entries
+    [offset, w_offset, lo, w_lo, hi, w_hi, v_target, w_speed] (reshape(P, -1) is the table).  Every argument is a scalar
+    or an array that broadcasts to [P, N] ([N]: the same profile for every row; [P, 1]: one value per row).  offset, lo
+    and hi are values of the signed lateral offset e from the centerline, POSITIVE TO THE RIGHT of the direction of
+    travel; a weight of 0 switches its part off.  Everything finite, weights >= 0, lo <= hi wherever both edge weights
+    are non-zero.  Pure host code: usable without a GPU."""
+    import numpy as np
+    N = int(N)
+    if N < 1:
+        raise ValueError("road_rows: N must be >= 1")
+    names = ("offset", "w_offset", "lo", "w_lo", "hi", "w_hi", "v_target", "w_speed")
+    vals = [np.asarray(v, dtype=np.float64) for v in (offset, w_offset, lo, w_lo, hi, w_hi, v_target, w_speed)]
+    if any(v.ndim > 2 for v in vals):
+        raise ValueError("road_rows: the arguments must broadcast to (P, N)")
+    try:
+        shape = np.broadcast_shapes((1, N), *(v.shape for v in vals))
+    except ValueError:
+        raise ValueError("road_rows: the arguments do not broadcast to one (P, N)") from None
+    if shape[1] != N:
+        raise ValueError(f"road_rows: {N} stages per row, got {shape[1]}")
+    tab = np.empty(shape + (NROAD,), dtype=np.float64)
+    for i, (name, v) in enumerate(zip(names, vals)):
+        if not np.all(np.isfinite(v)):
+            raise ValueError(f"road_rows: {name} must be finite")
+        if name.startswith("w_") and np.any(v < 0.0):
+            raise ValueError(f"road_rows: {name} must be >= 0")
+        tab[..., i] = np.broadcast_to(v, shape)
+    if np.any((tab[..., 3] != 0.0) & (tab[..., 5] != 0.0) & (tab[..., 2] > tab[..., 4])):
+        raise ValueError("road_rows: lo must not exceed hi where both edge weights are non-zero")
+    return tab
 
 
 def track_init(cfg, K, L, stride, lead, closed):

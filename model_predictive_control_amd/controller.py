@@ -106,8 +106,8 @@ class MPCController:
 
     # ------------------------------------------------------------------ batched entry points
     def solve(self, Y0, centerline, U0=None, lam0=None, cl_index=None, params=None, param_index=None,
-              bounds=None, bound_index=None, constraints=None, constraint_index=None, fields=None, field_index=None,
-              discs=None, disc_index=None, rates=None, rate_index=None):
+              bounds=None, bound_index=None, constraints=None, constraint_index=None, roads=None, road_index=None,
+              fields=None, field_index=None, discs=None, disc_index=None, rates=None, rate_index=None):
         """Batched solve: Y0 [B, nx], centerline [2S] or [C, 2S] (+ cl_index[B]) -> (U [B, 2N], stats).
         params [P, 31] (rows as _lib.param_rows makes them) + param_index [B] (None: agent b uses row b % P): this
         solve runs agent b on its own vehicle and cost parameters (BatchedMPC.set_agent_params).
@@ -124,8 +124,11 @@ class MPCController:
         fields [P', N, NFIELD, NFSRC] or [P', 16 N] (as _lib.field_rows makes them) + field_index [B] (None: agent b uses
         row b % P'): this solve adds the risk field of its own row to agent b's cost, stage by stage
         (BatchedMPC.set_agent_fields; not together with constraints= or discs=).
-        Pass the tables by keyword: fields= and field_index= stand in front of discs=, so the positional slots of discs,
-        disc_index, rates and rate_index are two further back than they were before the field table existed."""
+        roads [P', N, NROAD] or [P', 8 N] (as _lib.road_rows makes them) + road_index [B] (None: agent b uses row b % P'):
+        this solve adds the lane target, the soft road edges and the speed target of its own row to agent b's cost, stage
+        by stage (BatchedMPC.set_agent_roads; beside discs= too, not together with constraints=).
+        Pass the tables by keyword: roads=, road_index=, fields= and field_index= stand in front of discs=, so the
+        positional slots behind constraint_index have moved with every table added there."""
         dev = self.device
         Y0 = torch.as_tensor(Y0, dtype=torch.float64, device=dev).contiguous()
         B = Y0.shape[0]
@@ -144,13 +147,14 @@ class MPCController:
                                          ("constraints", constraints, constraint_index, "constraint_index"),
                                          ("discs", discs, disc_index, "disc_index"),
                                          ("rates", rates, rate_index, "rate_index"),
-                                         ("fields", fields, field_index, "field_index")):
+                                         ("fields", fields, field_index, "field_index"),
+                                         ("roads", roads, road_index, "road_index")):
             if table is None:
                 if index is not None:
                     raise ValueError(f"{name} needs {kind}")
                 continue
             table = torch.as_tensor(table, dtype=torch.float64, device=dev).contiguous()
-            if kind == "fields" and table.dim() == 4:
+            if (kind == "fields" and table.dim() == 4) or (kind == "roads" and table.dim() == 3):
                 table = table.reshape(table.shape[0], -1)
             if index is None:
                 index = torch.arange(B, device=dev) % table.shape[0]
@@ -168,11 +172,12 @@ class MPCController:
         return U, stats
 
     def step(self, Y0, centerline, U0=None, lam0=None, cl_index=None, params=None, param_index=None,
-             bounds=None, bound_index=None, constraints=None, constraint_index=None, fields=None, field_index=None,
-             discs=None, disc_index=None, rates=None, rate_index=None):
+             bounds=None, bound_index=None, constraints=None, constraint_index=None, roads=None, road_index=None,
+             fields=None, field_index=None, discs=None, disc_index=None, rates=None, rate_index=None):
         """First control of every agent, u0 [B, 2] (main.py:141 input_to_matrix(U)[:, 0])."""
         U, _ = self.solve(Y0, centerline, U0, lam0, cl_index, params, param_index, bounds, bound_index,
-                          constraints, constraint_index, fields, field_index, discs, disc_index, rates, rate_index)
+                          constraints, constraint_index, roads, road_index, fields, field_index, discs, disc_index, rates,
+                          rate_index)
         return U[:, :2].contiguous()
 
 

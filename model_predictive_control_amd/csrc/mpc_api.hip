@@ -109,6 +109,15 @@ extern "C" int mpc_default_fields(const mpc_config *c, double *row)
     return MPC_OK;
 }
 
+static_assert(MPC_NROAD == mpc::NROAD, "row layout: include/mpc_hip.h and mpc_device.hpp");
+extern "C" int mpc_default_roads(const mpc_config *c, double *row)
+{
+    if (!c || !row) return fail(MPC_E_ARG, "mpc_default_roads: null argument");
+    if (c->N < 1 || c->N > MPC_MAX_N) return fail(MPC_E_ARG, "mpc_default_roads: horizon N out of range [1, 64]");
+    for (int i = 0; i < MPC_ROAD_ROW(c->N); i++) row[i] = 0.0;   // every weight 0: no part is on at any stage
+    return MPC_OK;
+}
+
 extern "C" int mpc_create(const mpc_config *cfg, int device, mpc_handle **out)
 {
     if (!cfg || !out) return fail(MPC_E_ARG, "mpc_create: null argument");
@@ -200,23 +209,27 @@ extern "C" int mpc_centerline_blocks(mpc_handle *h, const double *cl, int C, voi
     return MPC_OK;
 }
 
-// the handle's own one-row parameter, box and rate tables and an index of B zeros (see mpc_handle::own_ptab)
+// the handle's own one-row parameter, box, rate and field tables and an index of B zeros (see mpc_handle::own_ptab)
 static int reserve_own_tables(mpc_handle *h, int B, const char *who)
 {
     if (B <= h->own_cap) return MPC_OK;
-    if (h->own_ptab) { HIPCHK(hipFree(h->own_ptab)); h->own_ptab = h->own_btab = h->own_rtab = nullptr; h->own_pidx = nullptr; h->own_cap = 0; }
+    if (h->own_ptab) { HIPCHK(hipFree(h->own_ptab)); h->own_ptab = h->own_btab = h->own_rtab = h->own_ftab = nullptr; h->own_pidx = nullptr; h->own_cap = 0; }
     const size_t cap = ((size_t)B + 63) & ~(size_t)63;
-    constexpr int ND = MPC_NPARAM + 1 + MPC_NBOUND + MPC_NRATE;
+    constexpr int NS = MPC_NPARAM + 1 + MPC_NBOUND + MPC_NRATE;   // the three of fixed width, then the field row of the handle's horizon
+    const size_t ND = (size_t)NS + MPC_FIELD_ROW(h->cfg.N);
     char *base = nullptr;
     if (hipMalloc((void **)&base, sizeof(double) * ND + sizeof(int32_t) * cap) != hipSuccess)
         return fail(MPC_E_ALLOC, std::string(who) + ": hipMalloc failed");
-    double own[ND] = {0};
+    std::vector<double> ownv(ND, 0.0);
+    double *own = ownv.data();
     (void)mpc_default_params(&h->cfg, own);
     (void)mpc_default_bounds(&h->cfg, own + MPC_NPARAM + 1);
     (void)mpc_default_rates(&h->cfg, own + MPC_NPARAM + 1 + MPC_NBOUND);
+    (void)mpc_default_fields(&h->cfg, own + NS);
     h->own_ptab = (double *)base; h->own_btab = h->own_ptab + MPC_NPARAM + 1; h->own_rtab = h->own_btab + MPC_NBOUND;
+    h->own_ftab = h->own_ptab + NS;
     h->own_pidx = (int32_t *)(base + sizeof(double) * ND); h->own_cap = (int)cap;
-    HIPCHK(hipMemcpy(base, own, sizeof own, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(base, own, sizeof(double) * ND, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(h->own_pidx, 0, sizeof(int32_t) * cap));
     return MPC_OK;
 }
@@ -286,6 +299,21 @@ static int field_row_rule(const mpc_handle *h, const double *r, const std::strin
     return MPC_OK;
 }
 
+// road data: every value finite, no negative weight, and the two edges in order where both are on
+static int road_row_rule(const mpc_handle *h, const double *r, const std::string &where)
+{
+    for (int k = 0; k < h->cfg.N; k++) {
+        const double *q = r + (size_t)MPC_NROAD * k;
+        const std::string which = ", stage " + std::to_string(k);
+        for (int f = 0; f < MPC_NROAD; f++)
+            if (!std::isfinite(q[f])) return fail(MPC_E_ARG, where + which + ": (off, w_off, lo, w_lo, hi, w_hi, v_tgt, w_v) must be finite");
+        if (!(q[1] >= 0.0) || !(q[3] >= 0.0) || !(q[5] >= 0.0) || !(q[7] >= 0.0))
+            return fail(MPC_E_ARG, where + which + ": the weights must not be negative");
+        if (q[3] != 0.0 && q[5] != 0.0 && q[2] > q[4]) return fail(MPC_E_ARG, where + which + ": lo must not exceed hi where both edges are on");
+    }
+    return MPC_OK;
+}
+
 // Binds (table != NULL) or unbinds the per-agent table of one kind.  The rows are checked once, here, through a
 // synchronous copy (binding is not on the hot path; rows rewritten in place later are the caller's to keep valid).
 // Nothing else is done: the kernels read the caller's memory at every call.  The box and constraint forms of some
@@ -312,6 +340,11 @@ static int bind_agent_table(mpc_handle *h, TableKind kind, const double *table, 
         if ((kind == TAB_FIELDS || kind == TAB_CONSTR) && kind != other && h->tab[other].table)
             return fail(MPC_E_ARG, std::string(who) + ": a " + k_tables[other].noun + " table is bound (" + k_tables[other].setter +
                                    "): a field table and a constraint table cannot be bound together");
+    // ... and a road table and a constraint table
+    for (const TableKind other : {TAB_CONSTR, TAB_ROADS})
+        if ((kind == TAB_ROADS || kind == TAB_CONSTR) && kind != other && h->tab[other].table)
+            return fail(MPC_E_ARG, std::string(who) + ": a " + k_tables[other].noun + " table is bound (" + k_tables[other].setter +
+                                   "): a road table and a constraint table cannot be bound together");
     // ... and so would a rate table and a constraint table
     if ((kind == TAB_RATES && h->tab[TAB_CONSTR].table) || (kind == TAB_CONSTR && h->tab[TAB_RATES].table))
         return fail(MPC_E_ARG, std::string(who) + ": a " + k_tables[kind == TAB_RATES ? TAB_CONSTR : TAB_RATES].noun + " table is bound (" +
@@ -359,6 +392,10 @@ extern "C" int mpc_set_agent_rates(mpc_handle *h, const double *table, int P, co
 extern "C" int mpc_set_agent_fields(mpc_handle *h, const double *table, int P, const int32_t *index, int B)
 {
     return bind_agent_table(h, TAB_FIELDS, table, P, index, B, field_row_rule);
+}
+extern "C" int mpc_set_agent_roads(mpc_handle *h, const double *table, int P, const int32_t *index, int B)
+{
+    return bind_agent_table(h, TAB_ROADS, table, P, index, B, road_row_rule);
 }
 // The closed loops carry u_{-1} themselves: with a rate table bound they need a row per agent (P == B; index 0 .. B-1 is
 // the caller's to ensure, as with the traffic loop's disc table) ...
@@ -498,7 +535,7 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     if (!x0 || !cl || !U || !psi) return fail(MPC_E_ARG, "mpc_eval_cost_grad: null buffer");
     const DevCfg &c = h->dc;
     if (c.m && (!y || !Sigma)) return fail(MPC_E_ARG, "mpc_eval_cost_grad: y and Sigma are required when m > 0");
-    rc = check_tables(h, B, "mpc_eval_cost_grad", READS_PARAMS | READS_CONSTR | READS_DISCS | READS_RATES | READS_FIELDS, true); if (rc) return rc;
+    rc = check_tables(h, B, "mpc_eval_cost_grad", READS_PARAMS | READS_CONSTR | READS_DISCS | READS_RATES | READS_FIELDS | READS_ROADS, true); if (rc) return rc;
     rc = reserve(h, B); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     // direct mode: the kernel reads and writes the caller's agent-major buffers in place
@@ -514,6 +551,7 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     w.dtab = h->tab[TAB_DISCS].table; w.didx = h->tab[TAB_DISCS].idx;
     w.rtab = h->tab[TAB_RATES].table; w.ridx = h->tab[TAB_RATES].idx;
     w.ftab = h->tab[TAB_FIELDS].table; w.fidx = h->tab[TAB_FIELDS].idx;
+    w.wtab = h->tab[TAB_ROADS].table; w.widx = h->tab[TAB_ROADS].idx;
     if (wave_path) launch_solo_eval(h, w, s, (grad ? 1 : 0) | (U2 ? 2 : 0));
     else launch_eval(h, w, s, nullptr, nullptr, grad ? B : 0, grad ? 0 : B);
     HIPCHK(hipGetLastError());
@@ -606,6 +644,7 @@ static int solve_core(mpc_handle *h, int B, const double *x0, const double *cl, 
     w.dtab = h->tab[TAB_DISCS].table; w.didx = rows_of(TAB_DISCS);
     w.rtab = h->tab[TAB_RATES].table; w.ridx = rows_of(TAB_RATES);
     w.ftab = h->tab[TAB_FIELDS].table; w.fidx = rows_of(TAB_FIELDS);
+    w.wtab = h->tab[TAB_ROADS].table; w.widx = rows_of(TAB_ROADS);
     w.xe = w.ws_xe; w.ge = w.ws_ge; w.yhe = w.ws_yhe; w.Sig = w.ws_Sig;
     rc = run_solver(h, s); if (rc) return rc;
     if (stats) hipLaunchKernelGGL(stats_kernel, grid_for(B, 256), dim3(256), 0, s, w, stats);
@@ -728,7 +767,7 @@ static int solve_active_impl(mpc_handle *h, int B, const int32_t *active, const 
     r.cl_index = cl_index; r.pidx = h->params().idx;
     r.xs = e.xs; r.Us = e.Us; r.lams = e.lams; r.stats_s = e.stats_s; r.cis = e.cis; r.pis = e.pis;
     hipLaunchKernelGGL(active_gather_kernel, grows, dim3(EV_BLK), 0, s, r);
-    const AgentIdx gathered = {{e.pis, e.bis, e.kis, e.dis, e.ris, e.fis}};   // (the parameter rows ride in the gather above)
+    const AgentIdx gathered = {{e.pis, e.bis, e.kis, e.dis, e.ris, e.fis, e.wis}};   // (the parameter rows ride in the gather above)
     for (int k = TAB_BOX; k < TAB_KINDS; k++)
         if (h->tab[k].table)
             hipLaunchKernelGGL(active_index_kernel, gblk, dim3(EV_BLK), 0, s, e.list, e.count, h->tab[k].idx, const_cast<int32_t *>(gathered.of[k]));
@@ -1179,6 +1218,27 @@ extern "C" int mpc_fields_from_obstacles(mpc_handle *h, int B, int G, int K, int
                                          const int32_t *sel, double *table, void *stream)
 {
     return rows_from_obstacles("mpc_fields_from_obstacles", false, h, B, G, K, Lt, wrap, ti, obs, sel, table, stream);
+}
+
+// Road rows in time: row b of table [B][N][MPC_NROAD] = the window of N samples from `ti` of script row sidx[b]
+// (roads_from_script_kernel), asynchronous.  The bound road table may be the target.
+extern "C" int mpc_roads_from_script(mpc_handle *h, int B, int Lt, int wrap, int ti, const double *script, const int32_t *sidx,
+                                     double *table, void *stream)
+{
+    const std::string who = "mpc_roads_from_script";
+    if (B < 0) return fail(MPC_E_ARG, who + ": negative batch");
+    if (Lt < 1) return fail(MPC_E_ARG, who + ": Lt must be >= 1 samples per script row");
+    if (ti < 0) return fail(MPC_E_ARG, who + ": ti must be >= 0");
+    if (!script || !sidx || !table) return fail(MPC_E_ARG, who + ": null script, sidx or table");
+    int rc = check_common(h, B, who.c_str()); if (rc) return rc;
+    rc = check_obstacle_window(who, ti, h->cfg.N, "ti"); if (rc) return rc;
+    rc = check_tables(h, B, who.c_str(), READS_ALL); if (rc) return rc;
+    if (B == 0) return MPC_OK;
+    const size_t words = (size_t)B * h->cfg.N;
+    hipLaunchKernelGGL(roads_from_script_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, h->cfg.N, Lt,
+                       wrap ? 1 : 0, ti, script, sidx, table);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
 }
 
 // Closed loop among scripted obstacles: per step (with a track) everybody's window of the track, everybody's plans

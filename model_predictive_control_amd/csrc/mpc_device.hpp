@@ -185,6 +185,16 @@ MPC_DEV double rate_term(const StageRate &r, double d, double dl, bool is_g, dou
 constexpr int NFIELD = 2, NFSRC = 8;
 struct StageField { const double *src; };   // [NFIELD][NFSRC]: the entry of the agent's row for this stage
 
+// mpc_set_agent_roads: a table [P][N][NROAD] of road data in device memory and one row index per agent -- per-stage
+// references and soft road edges.  A stage's entry is [off, w_off, lo, w_lo, hi, w_hi, v_tgt, w_v]: a target for the signed
+// lateral offset e from the centerline (the lane band's expression: stage_constraint), a quadratic wall below lo and one
+// above hi, and a target for the speed, each with its own weight (0: the part is off).  Like the field sources the eight
+// doubles never enter a DevCfg and are not passed by value: the road forms of the kernels that evaluate the cost (trailing
+// RoadTab argument, last: mpc_solver.hpp) hand stage_record the address of the stage's entry, and road_term (at the end
+// of this file: it needs the stage's Geom) loads them where it uses them.
+constexpr int NROAD = 8;
+struct StageRoad { const double *src; };    // [NROAD]: the entry of the agent's row for this stage
+
 // ---------------------------------------------------------------------------------- math
 // The OCML double-precision transcendentals are full-range (Payne-Hanek reduction, dozens of
 // 64-bit literals each) and dominate this kernel's instruction count.  The angles of this problem
@@ -1330,6 +1340,79 @@ MPC_DEV void stage_constraint_adjoint(const DevCfg &c, const Geom &g,
     const double nrm = sqrt(wx * wx + wy * wy);
     xb[0] += yh * wy / nrm;
     xb[1] += -yh * wx / nrm;
+}
+
+// The road cost of one stage at x, the state at the end of the stage, added to the stage cost L and -- for a gradient
+// request -- to the stage's state gradient xb; every operation rounded on its own (one function for the four evaluation
+// routes: the same request gets the same bits whichever serves it).  r = [off, w_off, lo, w_lo, hi, w_hi, v_tgt, w_v]:
+//     wx = qx - nx,  wy = qy - ny,  nrm = sqrt(wx wx + wy wy),  e = ((x0 - nx) wy - (x1 - ny) wx) / nrm     (the lane band's)
+//     de = 0
+//     w_off != 0:               t = e - off,  a = w_off t,  L = L + a t,  de = de + 2 a
+//     w_lo != 0, q = e - lo < 0:              a = w_lo q,   L = L + a q,  de = de + 2 a
+//     w_hi != 0, p = e - hi > 0:              a = w_hi p,   L = L + a p,  de = de + 2 a
+//     gradient, any of the three != 0:        xb0 = xb0 + (de wy) / nrm,  xb1 = xb1 - (de wx) / nrm
+//     w_v != 0:  ev = sp - v_tgt (sp as in stage_cost),  a = w_v ev,  L = L + a ev
+//                gradient: kinematic xb3 = xb3 + 2 a;  Pacejka xb3 = xb3 + ((2 a) x3) / sp,  xb4 = xb4 + ((2 a) x4) / sp
+// A part whose weight is 0 is skipped by a branch: it adds nothing, not even a signed zero, so a table of zero weights
+// gives the bits of the call without one; with no lateral weight set e and nrm are not computed.  nrm == 0 (two equal
+// neighbouring centerline points) gives what stage_constraint gives there: 0 / 0.  The doubles are loaded where they are
+// used, after everything stage_cost and field_term needed is dead.
+template <int MODEL>
+MPC_DEV void road_term(const StageRoad &rd, const Geom &g, const double (&x)[ModelDim<MODEL>::NX], bool is_g, double &L,
+                       double (&xb)[ModelDim<MODEL>::NX])
+{
+#pragma clang fp contract(off)
+    const double *__restrict__ r = rd.src;
+    const double w_off = r[1], w_lo = r[3], w_hi = r[5];
+    if (w_off != 0.0 || w_lo != 0.0 || w_hi != 0.0) {
+        const double wx = g.qx_ - g.nx_, wy = g.qy_ - g.ny_;
+        const double nrm = sqrt(wx * wx + wy * wy);
+        const double pe = (x[0] - g.nx_) * wy - (x[1] - g.ny_) * wx;
+        const double e = pe / nrm;
+        double de = 0.0;
+        if (w_off != 0.0) {
+            const double t = e - r[0], a = w_off * t;
+            L = L + a * t;
+            de = de + 2.0 * a;
+        }
+        if (w_lo != 0.0) {
+            const double q = e - r[2];
+            if (q < 0.0) {
+                const double a = w_lo * q;
+                L = L + a * q;
+                de = de + 2.0 * a;
+            }
+        }
+        if (w_hi != 0.0) {
+            const double p = e - r[4];
+            if (p > 0.0) {
+                const double a = w_hi * p;
+                L = L + a * p;
+                de = de + 2.0 * a;
+            }
+        }
+        if (is_g) {
+            xb[0] = xb[0] + (de * wy) / nrm;
+            xb[1] = xb[1] - (de * wx) / nrm;
+        }
+    }
+    const double w_v = r[7];
+    if (w_v != 0.0) {
+        double sp;
+        if (MODEL == PAC) sp = sqrt(x[3] * x[3] + x[4] * x[4]);
+        else sp = x[3];
+        const double ev = sp - r[6], a = w_v * ev;
+        L = L + a * ev;
+        if (is_g) {
+            const double ta = 2.0 * a;
+            if (MODEL == PAC) {
+                xb[3] = xb[3] + (ta * x[3]) / sp;
+                xb[4] = xb[4] + (ta * x[4]) / sp;
+            } else {
+                xb[3] = xb[3] + ta;
+            }
+        }
+    }
 }
 
 MPC_DEV void constraint_bounds(const DevCfg &c, int i, double &lb, double &ub)

@@ -594,7 +594,10 @@ __device__ __forceinline__ void stage_geom(const DevCfg &c, const Workspace &w, 
 // and to its direct input gradient right behind stage_cost, before the ALM terms, so psi stays the stage-order sum --
 // and, behind the StageRate, the stage's risk field (one trailing StageField, last: the field forms): field_term adds the
 // sources to the stage cost and to its state gradient xb[0], xb[1] behind rate_term and before the ALM terms; the adjoint
-// recursion carries that like any other stage gradient.
+// recursion carries that like any other stage gradient --
+// and, last of all, the stage's road data (one trailing StageRoad: the road forms, <rate, field, road> and <discs, rate,
+// road>): road_term adds the lane target, the road edges and the speed target to the stage cost and to its state gradient
+// behind field_term (on a disc handle: behind rate_term) and before the ALM terms.
 template <int MODEL, class Put, class... DS>
 __device__ __forceinline__ void stage_record(const DevCfg &c, const Workspace &w, int a, bool ch2, bool is_g,
                                              int k, const double (&xs)[ModelDim<MODEL>::NX],
@@ -603,8 +606,11 @@ __device__ __forceinline__ void stage_record(const DevCfg &c, const Workspace &w
 {
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE;
     constexpr bool DD = has_tab<StageDiscs, DS...>, RR = has_tab<StageRate, DS...>, FF = has_tab<StageField, DS...>;
-    static_assert(sizeof...(DS) == (DD ? 1 : 0) + (RR ? 1 : 0) + (FF ? 1 : 0), "at most the stage's discs, its move penalty and its risk field");
+    constexpr bool WW = has_tab<StageRoad, DS...>;
+    static_assert(sizeof...(DS) == (DD ? 1 : 0) + (RR ? 1 : 0) + (FF ? 1 : 0) + (WW ? 1 : 0),
+                  "at most the stage's discs, its move penalty, its risk field and its road data");
     static_assert(!FF || (RR && !DD), "the field forms stand behind the rate forms alone, never beside the discs");
+    static_assert(!WW || (RR && FF != DD), "the road forms are <rate, field, road> and <discs, rate, road> alone");
     double xb[NX], ub[2] = {0.0, 0.0};
 #pragma unroll
     for (int i = 0; i < NX; i++) xb[i] = 0.0;
@@ -615,6 +621,7 @@ __device__ __forceinline__ void stage_record(const DevCfg &c, const Workspace &w
         L = L + rate_term(pack_get<StageRate>(ds...), d, dl, is_g, ub);
     }
     if constexpr (FF) field_term(pack_get<StageField>(ds...), xe[0], xe[1], is_g, L, xb[0], xb[1]);
+    if constexpr (WW) road_term<MODEL>(pack_get<StageRoad>(ds...), g, xe, is_g, L, xb);
     if constexpr (DD) {
 #pragma clang fp contract(off)
         const StageDiscs dz[1] = {pack_get<StageDiscs>(ds...)};
@@ -825,6 +832,8 @@ __device__ __forceinline__ void adjoint_rec_quad_kin(const DevCfg &c, bool is_g,
 // slot (u_{-1} from the row at stage 0, nothing past stage N - 1) -- and stage_record adds the move penalty.
 // ... or the rate table and the field table behind it (RateTab, FieldTab: mpc_set_agent_fields): the thread also hands
 // stage_record the address of its (agent, stage)'s sources, which field_term loads one at a time.
+// ... or the road table last of all (RateTab, FieldTab, RoadTab or DiscTab, RateTab, RoadTab: mpc_set_agent_roads): the
+// thread hands stage_record the address of its (agent, stage)'s eight doubles as well, which road_term loads.
 template <int MODEL, bool SHARED_CL, bool PA = false, class... CT>
 __global__ void __launch_bounds__(64, (MODEL == KIN ? MPC_K1B_WAVES : MPC_K1B_WAVES_PAC))
 stage_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, int nG_imm, int nC_imm,
@@ -835,6 +844,8 @@ stage_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, 
     constexpr bool RA = has_tab<RateTab, CT...>;   // the rate form: CT = RateTab or DiscTab, RateTab
     constexpr bool FA = has_tab<FieldTab, CT...>;  // the field form: CT = RateTab, FieldTab
     static_assert(!FA || (RA && !DA), "the field forms are <..., RateTab, FieldTab> alone");
+    constexpr bool WA = has_tab<RoadTab, CT...>;   // the road forms: CT = RateTab, FieldTab, RoadTab or DiscTab, RateTab, RoadTab
+    static_assert(!WA || (RA && FA != DA), "the road forms are <..., RateTab, FieldTab, RoadTab> and <..., DiscTab, RateTab, RoadTab> alone");
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE;
 #if MPC_DEV_STAMP == 6
     DevStamp stamp(blockIdx.x);
@@ -881,7 +892,13 @@ stage_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, 
     } else {
         stage_geom(c, w, clp, SHARED_CL ? 0 : w.cl_index[a], xe[0], xe[1], g);
     }
-    if constexpr (FA)
+    if constexpr (WA && FA)
+        stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_rate(pack_get<RateTab>(ct...), a, k, c.N, w.useq + uslot, St),
+                            stage_field(pack_get<FieldTab>(ct...), a, k, c.N), stage_road(pack_get<RoadTab>(ct...), a, k, c.N));
+    else if constexpr (WA)
+        stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(pack_get<DiscTab>(ct...), a, k, c.N),
+                            stage_rate(pack_get<RateTab>(ct...), a, k, c.N, w.useq + uslot, St), stage_road(pack_get<RoadTab>(ct...), a, k, c.N));
+    else if constexpr (FA)
         stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_rate(pack_get<RateTab>(ct...), a, k, c.N, w.useq + uslot, St),
                             stage_field(pack_get<FieldTab>(ct...), a, k, c.N));
     else if constexpr (DA && RA)
@@ -942,6 +959,8 @@ stage_adjoint_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ 
     constexpr bool RA = has_tab<RateTab, CT...>;   // the rate form: CT = RateTab or DiscTab, RateTab
     constexpr bool FA = has_tab<FieldTab, CT...>;  // the field form: CT = RateTab, FieldTab
     static_assert(!FA || (RA && !DA), "the field forms are <..., RateTab, FieldTab> alone");
+    constexpr bool WA = has_tab<RoadTab, CT...>;   // the road forms: CT = RateTab, FieldTab, RoadTab or DiscTab, RateTab, RoadTab
+    static_assert(!WA || (RA && FA != DA), "the road forms are <..., RateTab, FieldTab, RoadTab> and <..., DiscTab, RateTab, RoadTab> alone");
     static_assert(MODEL == KIN, "the fused K1b + K1c kernel is the kinematic model's");
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE, BLK = FUSED_BLK;
     extern __shared__ double s_rec[];                    // [JS + 1][N][SPB]; row JS = stage cost
@@ -980,7 +999,13 @@ stage_adjoint_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ 
             if (is_g) stage_sens_record<MODEL>(cm, xs, xe, d, dl, put);
             Geom g;
             stage_geom(c, w, clp, SHARED_CL ? 0 : w.cl_index[a], xe[0], xe[1], g);
-            if constexpr (FA)
+            if constexpr (WA && FA)
+                stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_rate(pack_get<RateTab>(ct...), a, k, N, w.useq + uslot, St),
+                                    stage_field(pack_get<FieldTab>(ct...), a, k, N), stage_road(pack_get<RoadTab>(ct...), a, k, N));
+            else if constexpr (WA)
+                stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(pack_get<DiscTab>(ct...), a, k, N),
+                                    stage_rate(pack_get<RateTab>(ct...), a, k, N, w.useq + uslot, St), stage_road(pack_get<RoadTab>(ct...), a, k, N));
+            else if constexpr (FA)
                 stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_rate(pack_get<RateTab>(ct...), a, k, N, w.useq + uslot, St),
                                     stage_field(pack_get<FieldTab>(ct...), a, k, N));
             else if constexpr (DA && RA)

@@ -39,11 +39,11 @@ static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
 // The per-agent tables a caller can bind beside the handle's shared values: parameters (mpc_set_agent_params), input
 // boxes (mpc_set_agent_bounds), constraint data (mpc_set_agent_constraints), keep-out discs (mpc_set_agent_discs) and move
-// penalties (mpc_set_agent_rates) and risk fields (mpc_set_agent_fields).  The kinds are walked in this order wherever they are checked; an entry point names the kinds it reads as a mask of READS_*
+// penalties (mpc_set_agent_rates), risk fields (mpc_set_agent_fields) and road data (mpc_set_agent_roads).  The kinds are walked in this order wherever they are checked; an entry point names the kinds it reads as a mask of READS_*
 // (check_tables).
-enum TableKind { TAB_PARAMS, TAB_BOX, TAB_CONSTR, TAB_DISCS, TAB_RATES, TAB_FIELDS, TAB_KINDS };
+enum TableKind { TAB_PARAMS, TAB_BOX, TAB_CONSTR, TAB_DISCS, TAB_RATES, TAB_FIELDS, TAB_ROADS, TAB_KINDS };
 enum : unsigned { READS_PARAMS = 1u << TAB_PARAMS, READS_BOX = 1u << TAB_BOX, READS_CONSTR = 1u << TAB_CONSTR, READS_DISCS = 1u << TAB_DISCS,
-                  READS_RATES = 1u << TAB_RATES, READS_FIELDS = 1u << TAB_FIELDS, READS_ALL = (1u << TAB_KINDS) - 1 };
+                  READS_RATES = 1u << TAB_RATES, READS_FIELDS = 1u << TAB_FIELDS, READS_ROADS = 1u << TAB_ROADS, READS_ALL = (1u << TAB_KINDS) - 1 };
 // messages, doubles per row (width_per_N: per stage of the handle's horizon -- table_width)
 static constexpr struct { const char *noun, *setter; int width, width_per_N; } k_tables[TAB_KINDS] = {
     {"parameter", "mpc_set_agent_params", MPC_NPARAM, 0},
@@ -51,7 +51,8 @@ static constexpr struct { const char *noun, *setter; int width, width_per_N; } k
     {"constraint", "mpc_set_agent_constraints", MPC_NCONSTR, 0},
     {"disc", "mpc_set_agent_discs", 0, 3 * MPC_NDISC},
     {"rate", "mpc_set_agent_rates", MPC_NRATE, 0},
-    {"field", "mpc_set_agent_fields", 0, MPC_NFIELD * MPC_NFSRC}};
+    {"field", "mpc_set_agent_fields", 0, MPC_NFIELD * MPC_NFSRC},
+    {"road", "mpc_set_agent_roads", 0, MPC_NROAD}};
 struct BoundTable {
     const double *table = nullptr;         // [rows][k_tables[kind].width], null: none bound
     const int32_t *idx = nullptr;          // [B] the row per agent
@@ -65,7 +66,8 @@ struct AgentIdx { const int32_t *of[TAB_KINDS]; };
 // kernels as an argument of its own (BoxTab) and no other kernel at all; the constraint table of
 // mpc_set_agent_constraints likewise (ConTab, the constraint forms alone), and the disc table of mpc_set_agent_discs
 // (DiscTab, the disc forms alone), and the rate table of mpc_set_agent_rates (RateTab, the rate forms alone), and the field
-// table of mpc_set_agent_fields (FieldTab, the field forms alone).
+// table of mpc_set_agent_fields (FieldTab, the field forms alone), and the road table of mpc_set_agent_roads (RoadTab, the
+// road forms alone).
 struct WorkspaceHost : WorkspacePA {
     const double *btab;                            // [P][MPC_NBOUND] caller's table
     const int *bidx;                               // [B]             caller's row index per agent
@@ -82,6 +84,9 @@ struct WorkspaceHost : WorkspacePA {
     const double *ftab;                            // [P][MPC_FIELD_ROW(N)] caller's table
     const int *fidx;                               // [B]              caller's row index per agent
     FieldTab field() const { return FieldTab{ftab, fidx}; }
+    const double *wtab;                            // [P][MPC_ROAD_ROW(N)] caller's table
+    const int *widx;                               // [B]              caller's row index per agent
+    RoadTab road() const { return RoadTab{wtab, widx}; }
 };
 
 struct mpc_handle {
@@ -170,21 +175,22 @@ struct mpc_handle {
     bool spin = false;             // the round loop busy-waits instead of napping (MPC_SPIN)
     bool host_timing = false;      // the round loop prints its host-side times to stderr (MPC_HOST_TIMING)
     std::string host_trace;        // file the round loop appends one line per polled window to (MPC_HOST_TRACE; empty: none)
-    // The caller's per-agent tables, one per kind (mpc_set_agent_params / _bounds / _constraints / _discs / _rates / _fields; device memory, read at
+    // The caller's per-agent tables, one per kind (mpc_set_agent_params / _bounds / _constraints / _discs / _rates / _fields / _roads; device memory, read at
     // every call).  A kind with none bound runs the handle's values through the kernels that have always run.
     BoundTable tab[TAB_KINDS];
     const int32_t *pidx_plant = nullptr;   // parameters alone: [B] the plant's row per agent (mpc_closed_loop), null: the controller's
     const BoundTable &params() const { return tab[TAB_PARAMS]; }
     const int32_t *plant_rows() const { return pidx_plant ? pidx_plant : params().idx; }
-    AgentIdx bound_rows() const { return AgentIdx{{tab[TAB_PARAMS].idx, tab[TAB_BOX].idx, tab[TAB_CONSTR].idx, tab[TAB_DISCS].idx, tab[TAB_RATES].idx, tab[TAB_FIELDS].idx}}; }
+    AgentIdx bound_rows() const { return AgentIdx{{tab[TAB_PARAMS].idx, tab[TAB_BOX].idx, tab[TAB_CONSTR].idx, tab[TAB_DISCS].idx, tab[TAB_RATES].idx, tab[TAB_FIELDS].idx, tab[TAB_ROADS].idx}}; }
     size_t table_width(int kind) const { return (size_t)k_tables[kind].width + (size_t)k_tables[kind].width_per_N * (size_t)cfg.N; }
     // The persistent kernel has its box form together with the parameter form alone, and its constraint form -- as the
     // K1 kernels have theirs -- together with both.  With a table bound but not the ones its kernels come with, they run
     // on these one-row tables of the handle's own values (bit for bit the shared path: tests/test_gpu_agent_params.py,
     // tests/test_gpu_agent_bounds.py) and an index of zeros; made at the first such bind, one allocation.
-    double *own_ptab = nullptr;            // [MPC_NPARAM], a pad, then own_btab, own_rtab and the zeros
+    double *own_ptab = nullptr;            // [MPC_NPARAM], a pad, then own_btab, own_rtab, own_ftab and the zeros
     double *own_btab = nullptr;            // [MPC_NBOUND]
     double *own_rtab = nullptr;            // [MPC_NRATE] zeros: no move penalty (the field forms stand behind the rate forms alone)
+    double *own_ftab = nullptr;            // [MPC_FIELD_ROW(N)] zeros: no source (the road forms of a handle without discs stand behind the field forms alone)
     int32_t *own_pidx = nullptr;           // [own_cap] zeros
     int own_cap = 0;
     // staging buffers for the standalone entry points
@@ -196,7 +202,7 @@ struct mpc_handle {
     struct EventBufs {
         char *base = nullptr;
         int cap = 0;                                   // agents the arena holds
-        int *list = nullptr, *blk = nullptr, *count = nullptr, *fire = nullptr, *cis = nullptr, *pis = nullptr, *bis = nullptr, *kis = nullptr, *dis = nullptr, *ris = nullptr, *fis = nullptr;
+        int *list = nullptr, *blk = nullptr, *count = nullptr, *fire = nullptr, *cis = nullptr, *pis = nullptr, *bis = nullptr, *kis = nullptr, *dis = nullptr, *ris = nullptr, *fis = nullptr, *wis = nullptr;
         double *xs = nullptr, *Us = nullptr, *lams = nullptr, *stats_s = nullptr, *stats_own = nullptr;
         double *xhat = nullptr;                        // [xhat_B][nx]
         int xhat_B = 0;
@@ -448,7 +454,7 @@ static int reserve_event(mpc_handle *h, int B)
     const DevCfg &c = h->dc;
     const size_t Bp = ((size_t)B + 63) & ~(size_t)63, m = c.m ? c.m : 1, nblk = (Bp + EV_BLK - 1) / EV_BLK;
     const size_t nd = (size_t)c.nx + c.n + m + 8 + 8;            // doubles per agent: xs, Us, lams, stats_s, stats_own
-    const size_t bytes = nd * 8 * Bp + 4 * (9 * Bp + nblk + 64);  // ints: list, fire, cis, pis, bis, kis, dis, ris, fis [Bp], blk [nblk], count
+    const size_t bytes = nd * 8 * Bp + 4 * (10 * Bp + nblk + 64);  // ints: list, fire, cis, pis, bis, kis, dis, ris, fis, wis [Bp], blk [nblk], count
     char *base = nullptr;
     if (hipMalloc((void **)&base, bytes) != hipSuccess) return fail(MPC_E_ALLOC, "masked-solve staging hipMalloc failed");
     e.base = base; e.cap = (int)Bp;
@@ -457,7 +463,7 @@ static int reserve_event(mpc_handle *h, int B)
     e.xs = takeD(c.nx); e.Us = takeD(c.n); e.lams = takeD(m); e.stats_s = takeD(8); e.stats_own = takeD(8);
     int *ip = (int *)dp;
     auto takeI = [&](size_t cnt) { int *r = ip; ip += cnt; return r; };
-    e.list = takeI(Bp); e.fire = takeI(Bp); e.cis = takeI(Bp); e.pis = takeI(Bp); e.bis = takeI(Bp); e.kis = takeI(Bp); e.dis = takeI(Bp); e.ris = takeI(Bp); e.fis = takeI(Bp); e.blk = takeI(nblk); e.count = takeI(64);
+    e.list = takeI(Bp); e.fire = takeI(Bp); e.cis = takeI(Bp); e.pis = takeI(Bp); e.bis = takeI(Bp); e.kis = takeI(Bp); e.dis = takeI(Bp); e.ris = takeI(Bp); e.fis = takeI(Bp); e.wis = takeI(Bp); e.blk = takeI(nblk); e.count = takeI(64);
     HIPCHK(hipMemset(base, 0, bytes));
     return MPC_OK;
 }
@@ -494,7 +500,7 @@ static int reserve_xhat(mpc_handle *h, int B, bool *fresh)
 }
 
 // A handle with a table bound serves the batch size the table's indices were bound for, and no other, in the calls
-// that read that kind of table (`kinds`: a mask of READS_*).  Parameters, box, constraints, discs, rates, fields: the first mismatch wins.
+// that read that kind of table (`kinds`: a mask of READS_*).  Parameters, box, constraints, discs, rates, fields, roads: the first mismatch wins.
 // The discs have no shared values to fall back on: a call that evaluates constraints (`needs_discs`) on a handle of
 // MPC_CONSTR_DISCS with no disc table bound is refused.
 static int check_tables(const mpc_handle *h, int B, const char *who, unsigned kinds, bool needs_discs = false)

@@ -46,6 +46,10 @@ static BoxTab with_own_box(const mpc_handle *h, const WorkspaceHost &w) { return
 // ... and the rates as the field forms take them: they exist behind the rate form alone, so without a rate table of the
 // caller's they run on the handle's own one-row table of zeros (mpc_handle::own_rtab: zero weights change no bit)
 static RateTab with_own_rates(const mpc_handle *h, const WorkspaceHost &w) { return w.rtab ? w.rate() : RateTab{h->own_rtab, h->own_pidx}; }
+// ... and the fields as the road forms of a handle without discs take them: <..., RateTab, FieldTab, RoadTab> alone, so
+// without a field table of the caller's they run on the handle's own one-row table of zeros (mpc_handle::own_ftab: A == 0
+// is skipped by a branch and changes no bit)
+static FieldTab with_own_fields(const mpc_handle *h, const WorkspaceHost &w) { return w.ftab ? w.field() : FieldTab{h->own_ftab, h->own_pidx}; }
 
 // How the step kernel and the persistent kernel read an agent's L-BFGS history -- f(int_c<NE>, int_c<MC>), the two
 // kernels' template arguments (results do not depend on the choice).  NE: elements per lane, 1 up to n = 64 and 2
@@ -107,7 +111,16 @@ static bool launch_eval_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
             const int spb = FUSED_BLK / c.N;
             const int gb = (nblk * 64 + spb - 1) / spb;
             const size_t flds = sizeof(double) * (size_t)(JS + 1) * c.N * spb;
-            if (w.ctab)     // a constraint table is bound: the constraint form of K1b (here and below)
+            if (w.wtab)     // a road table is bound: the road forms of K1b, <rate, field, road> or on a disc handle <discs, rate, road> (here and below)
+                with_flags(shared, w.dtab != nullptr, [&](auto SH, auto DA) {
+                    if constexpr (DA())
+                        hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, DiscTab, RateTab, RoadTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
+                                           with_own_params(h, w), counts, nG, nC, desc, w.disc(), with_own_rates(h, w), w.road());
+                    else
+                        hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, RateTab, FieldTab, RoadTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
+                                           with_own_params(h, w), counts, nG, nC, desc, with_own_rates(h, w), with_own_fields(h, w), w.road());
+                });
+            else if (w.ctab)     // a constraint table is bound: the constraint form of K1b (here and below)
                 with_flag(shared, [&](auto SH) {
                     hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, ConTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
                                        with_own_params(h, w), counts, nG, nC, desc, w.con());
@@ -143,7 +156,16 @@ static bool launch_eval_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
     // block on XCD sb % 8 so that K1c could read records from the L2 they were written to -- no change: the 13 MB
     // of records per XCD and launch pass through a 4 MB L2 long before K1c starts)
     const size_t xy_lds = (shared && w.near.gmeta && c.S <= GRID_LDS_MAX_S) ? sizeof(double) * 2 * (size_t)c.S : 0;
-    if (w.ctab)
+    if (w.wtab)
+        with_flags(shared, w.dtab != nullptr, [&](auto SH, auto DA) {
+            if constexpr (DA())
+                hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, DiscTab, RateTab, RoadTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
+                                   with_own_params(h, w), counts, nG, nC, nblk, w.disc(), with_own_rates(h, w), w.road());
+            else
+                hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, RateTab, FieldTab, RoadTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
+                                   with_own_params(h, w), counts, nG, nC, nblk, with_own_rates(h, w), with_own_fields(h, w), w.road());
+        });
+    else if (w.ctab)
         with_flag(shared, [&](auto SH) {
             hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, ConTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
                                with_own_params(h, w), counts, nG, nC, nblk, w.con());
@@ -185,6 +207,18 @@ static bool launch_eval(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, co
 static void launch_solo_eval(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, int want_grad)
 {
     const DevCfg &c = h->dc;
+    if (w.wtab) {
+        with_model(c.model, [&](auto MODEL) {
+            const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
+            if (w.dtab)
+                hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, DiscTab, RateTab, RoadTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
+                                   want_grad, w.disc(), with_own_rates(h, w), w.road());
+            else
+                hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, RateTab, FieldTab, RoadTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
+                                   want_grad, with_own_rates(h, w), with_own_fields(h, w), w.road());
+        });
+        return;
+    }
     if (w.ctab) {
         with_model(c.model, [&](auto MODEL) {
             const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
@@ -342,6 +376,17 @@ static void launch_solo_t(mpc_handle *h, const WorkspaceHost &v, hipStream_t s, 
     // v.btab: a bounds table is bound, the box form, which exists together with the parameter form alone (with_own_params)
     // v.ctab: a constraint table is bound, the constraint form, which exists together with the box form alone
     // (with_own_box; never with the lookahead: m > 0)
+    // v.wtab: a road table is bound, the road forms -- behind the disc and rate forms on a disc handle, behind the rate and
+    // field forms elsewhere (the caller's tables or the handle's zeros); never with the lookahead, like the rate forms
+    if (v.wtab) {
+        if (v.dtab)
+            hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, DiscTab, RateTab, RoadTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
+                               with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), v.disc(), with_own_rates(h, v), v.road());
+        else
+            hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, RateTab, FieldTab, RoadTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
+                               with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), with_own_rates(h, v), with_own_fields(h, v), v.road());
+        return;
+    }
     if (v.ctab) {
         hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, ConTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
                            with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), v.con());

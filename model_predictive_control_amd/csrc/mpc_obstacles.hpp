@@ -147,4 +147,19 @@ __global__ void __launch_bounds__(256) rows_from_obstacles_kernel(int B, int N, 
     for (int i = 0; i < W; i++) out[i] = p ? p[i] : 0.0;
 }
 
+// mpc_roads_from_script: table[b][k] = the NROAD words of sample (ti + k) of script row sidx[b] -- clamped to the last
+// sample or wrapped, the time rule of the obstacles.  One thread per (agent, stage); a plain copy.  (The range of
+// sidx is the caller's to check, as every table's row index is; the Python front end does.)
+__global__ void __launch_bounds__(256) roads_from_script_kernel(int B, int N, int Lt, int wrap, int ti, const double *__restrict__ script,
+                                                                const int *__restrict__ sidx, double *__restrict__ table)
+{
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)B * N) return;
+    const int k = (int)(t % N), b = (int)(t / N);
+    const double *__restrict__ p = script + ((size_t)sidx[b] * (size_t)Lt + (size_t)obstacle_sample(ti + k, Lt, wrap)) * NROAD;
+    double *out = table + t * NROAD;
+#pragma unroll
+    for (int i = 0; i < NROAD; i++) out[i] = p[i];
+}
+
 } // namespace mpc

@@ -93,6 +93,7 @@ struct SoloClk { long long roll = 0, recs = 0, adj = 0; };
 // agent's row, whose address is wave-uniform -- and / or the rate table (the rate forms: a trailing RateTab, last) -- lane k
 // takes u_{k-1} and u_{k+1} from the row it evaluates (`row`: xe, or xe2 on the speculative half), u_{-1} from the table
 // -- and, behind the RateTab, the field table (the field forms) -- lane k hands on the address of its stage's sources
+// -- and, last, the road table (the road forms: RateTab, FieldTab, RoadTab or DiscTab, RateTab, RoadTab) -- likewise
 // alt: where the second half's trajectory and record block lie (solo_halves); nullptr: behind the first half's (solo_dual)
 template <int MODEL, class... DS>
 __device__ __forceinline__ void solo_eval(const DevCfg &c, const Workspace &w, int a, int lane, int req,
@@ -169,8 +170,14 @@ __device__ __forceinline__ void solo_eval(const DevCfg &c, const Workspace &w, i
         if (is_g) stage_sens_record<MODEL>(c, xs, xe, d, dl, put);
         Geom g;
         stage_geom(c, w, clp, w.cl_index ? w.cl_index[a] : 0, xe[0], xe[1], g);
-        constexpr bool DA = has_tab<DiscTab, DS...>, RA = has_tab<RateTab, DS...>, FA = has_tab<FieldTab, DS...>;
-        if constexpr (FA)
+        constexpr bool DA = has_tab<DiscTab, DS...>, RA = has_tab<RateTab, DS...>, FA = has_tab<FieldTab, DS...>, WA = has_tab<RoadTab, DS...>;
+        if constexpr (WA && FA)
+            stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_rate_uniform(pack_get<RateTab>(ds...), a, hl, N, row),
+                                stage_field_uniform(pack_get<FieldTab>(ds...), a, hl, N), stage_road_uniform(pack_get<RoadTab>(ds...), a, hl, N));
+        else if constexpr (WA)
+            stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_discs_uniform(pack_get<DiscTab>(ds...), a, hl, N),
+                                stage_rate_uniform(pack_get<RateTab>(ds...), a, hl, N, row), stage_road_uniform(pack_get<RoadTab>(ds...), a, hl, N));
+        else if constexpr (FA)
             stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_rate_uniform(pack_get<RateTab>(ds...), a, hl, N, row),
                                 stage_field_uniform(pack_get<FieldTab>(ds...), a, hl, N));
         else if constexpr (DA && RA)
@@ -472,6 +479,8 @@ template <int MODEL> struct SoloOcc { static constexpr int WPS = MODEL == KIN ? 
 // lookahead (results do not depend on it).
 // BT = (BoxTab, RateTab, FieldTab): the field form (mpc_set_agent_fields), on the rate form's terms -- the evaluations add
 // the risk field of the agent's row, stage by stage.
+// BT = (BoxTab, RateTab, FieldTab, RoadTab) or (BoxTab, DiscTab, RateTab, RoadTab): the road forms (mpc_set_agent_roads),
+// on the same terms -- the evaluations add the lane target, road edges and speed target of the agent's row, stage by stage.
 template <int MODEL, int NE, int MC, bool LA = false, bool PA = false, class... BT>
 __global__ void __launch_bounds__(64 * SOLO_WAVES, SoloOcc<MODEL>::WPS)
 solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int *__restrict__ ctr,
@@ -482,7 +491,10 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
     static_assert((!CA && !DA) || !LA, "the lookahead is an unconstrained problem's: it has no constraint or disc form");
     static_assert(!RA || !LA, "the rate forms run without the lookahead");
     constexpr bool FA = has_tab<FieldTab, BT...>;
-    static_assert(!FA || (RA && !DA && !CA), "the field forms are <..., BoxTab, RateTab, FieldTab> alone");
+    constexpr bool WA = has_tab<RoadTab, BT...>;
+    static_assert(!FA || (RA && !DA && !CA && sizeof...(BT) == (WA ? 4 : 3)), "the field forms are <..., BoxTab, RateTab, FieldTab> and <..., BoxTab, RateTab, FieldTab, RoadTab> alone");
+    static_assert(!WA || (RA && !CA && FA != DA && sizeof...(BT) == 4),
+                  "the road forms are <..., BoxTab, RateTab, FieldTab, RoadTab> and <..., BoxTab, DiscTab, RateTab, RoadTab> alone");
     using BOX = BoxOf<BA, LaneBox>;
     using CON = ConOf<CA, RowCon>;
     extern __shared__ double s_solo[];
@@ -555,7 +567,9 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
 #if MPC_DEV_STAMP == 5
             t_adv += __builtin_amdgcn_s_memrealtime() - ta;
             if ((req & (REQ_GRAD | REQ_COST | REQ_SPEC)) == REQ_GRAD && (rec_int_of(w.rec[(size_t)a * REC + R_PHASE]) & PH_MASK) == PH_W_HESS) nhess++;
-            if constexpr (FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...));
+            if constexpr (WA && FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...), pack_get<RoadTab>(bt...));
+            else if constexpr (WA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...), pack_get<RoadTab>(bt...));
+            else if constexpr (FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...));
             else if constexpr (DA && RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...));
             else if constexpr (RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<RateTab>(bt...));
             else if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<DiscTab>(bt...));
@@ -563,7 +577,9 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
             solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk);
             ntrip++;
 #else
-            if constexpr (FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...));
+            if constexpr (WA && FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...), pack_get<RoadTab>(bt...));
+            else if constexpr (WA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...), pack_get<RoadTab>(bt...));
+            else if constexpr (FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...));
             else if constexpr (DA && RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...));
             else if constexpr (RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<RateTab>(bt...));
             else if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<DiscTab>(bt...));

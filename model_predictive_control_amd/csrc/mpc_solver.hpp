@@ -198,6 +198,26 @@ __device__ __forceinline__ StageField stage_field_uniform(const FieldTab &t, int
     const int row = __builtin_amdgcn_readfirstlane(t.fidx[a]);
     return StageField{t.ftab + (size_t)row * N * (NFIELD * NFSRC) + (size_t)k * (NFIELD * NFSRC)};
 }
+// The road table of mpc_set_agent_roads, as the road forms of the kernels receive it: the LAST trailing argument.  Two
+// families and no cross product beyond them: <..., RateTab, FieldTab, RoadTab> on every handle that is not a disc handle
+// (a missing rate table is the handle's own one-row table of zero weights, a missing field table the handle's own one-row
+// table of zeros: with_own_rates, with_own_fields in mpc_launch.hpp -- neither changes a bit), and <..., DiscTab, RateTab,
+// RoadTab> on disc handles.  Never beside a ConTab: the binder refuses it.
+struct RoadTab {
+    const double *wtab;                            // [P][N][NROAD] caller's table
+    const int *widx;                               // [B]           caller's row index per agent
+};
+// the address of stage k's entry in agent a's row: a different agent in every lane ...
+__device__ __forceinline__ StageRoad stage_road(const RoadTab &t, int a, int k, int N)
+{
+    return StageRoad{t.wtab + ((size_t)t.widx[a] * N + k) * NROAD};
+}
+// ... one agent per wave: the row is wave-uniform, lane k takes its stage
+__device__ __forceinline__ StageRoad stage_road_uniform(const RoadTab &t, int a, int k, int N)
+{
+    const int row = __builtin_amdgcn_readfirstlane(t.widx[a]);
+    return StageRoad{t.wtab + (size_t)row * N * NROAD + (size_t)k * NROAD};
+}
 // which table a kernel's trailing pack holds
 template <class A, class B> struct SameTab { static constexpr bool v = false; };
 template <class A> struct SameTab<A, A> { static constexpr bool v = true; };

@@ -71,7 +71,8 @@ _AGENT_TABLES = {"params": _AgentTable(_lib.NPARAM, 0, "mpc_set_agent_params", T
                  "constraints": _AgentTable(_lib.NCONSTR, 0, "mpc_set_agent_constraints", False),
                  "discs": _AgentTable(0, 3 * _lib.NDISC, "mpc_set_agent_discs", False),
                  "rates": _AgentTable(_lib.NRATE, 0, "mpc_set_agent_rates", False),
-                 "fields": _AgentTable(0, _lib.NFIELD * _lib.NFSRC, "mpc_set_agent_fields", False)}
+                 "fields": _AgentTable(0, _lib.NFIELD * _lib.NFSRC, "mpc_set_agent_fields", False),
+                 "roads": _AgentTable(0, _lib.NROAD, "mpc_set_agent_roads", False)}
 
 
 class BatchedMPC:
@@ -328,6 +329,54 @@ class BatchedMPC:
     @property
     def agent_fields_bound(self):
         return "fields" in self._keep
+
+    def set_agent_roads(self, table, index):
+        """Binds a per-agent table of road data (mpc_set_agent_roads; an engine of any constr_mode, CONSTR_DISCS included):
+        table [P, NROAD * N] float64 (rows [N][NROAD], stage entries [off, w_off, lo, w_lo, hi, w_hi, v_tgt, w_v], as
+        _lib.road_rows(...).reshape(P, -1) makes them; a weight of 0: that part is off), index [B] int32 = the row of
+        agent b.  Bound, every call that evaluates the horizon's cost (eval_cost_grad(_wave), solve, solve_async,
+        solve_active, the closed loops) adds the lane target, the soft road edges and the speed target of agent b's row to
+        its stage costs, stage k reading entry k, and serves batches of exactly B agents.  The lateral offset e is the
+        lane band's, positive to the right of the direction of travel.  A cost, not a constraint: it works beside the
+        engine's own constraint data, the disc table of an engine of CONSTR_DISCS, and the parameter, bounds, rate and
+        field tables (together they are for the same B); not beside a constraint table.  The tensors stay the caller's:
+        the library reads them at every call, so rows may be rewritten in place between calls (roads_from_script does);
+        the engine keeps them alive until clear_agent_roads()."""
+        self._bind_agent_table("roads", table, index)
+
+    def clear_agent_roads(self):
+        """Unbinds the road table: the engine is what it was before set_agent_roads."""
+        self._clear_agent_table("roads")
+
+    @property
+    def agent_roads_bound(self):
+        return "roads" in self._keep
+
+    def roads_from_script(self, script, index, ti, wrap=False, out=None):
+        """mpc_roads_from_script: the road table [B, NROAD * N] whose row b is the window of N samples from sample `ti`
+        of script row index[b] -- script [Ps, Lt, NROAD] float64 (one sample per Ts, entries as _lib.road_rows makes
+        them), index [B] int32 in [0, Ps).  Stage k gets sample min(ti + k, Lt - 1), or (ti + k) % Lt with wrap.  A copy
+        on the current stream; `out`: a table to write in place (the bound one, say), else a new one.  The samples are
+        not checked: the script is the caller's to keep valid."""
+        self._free()
+        if not isinstance(script, torch.Tensor) or script.dim() != 3 or script.shape[0] < 1 or script.shape[1] < 1:
+            raise ValueError(f"script: expected [Ps >= 1, Lt >= 1, {_lib.NROAD}]")
+        Ps, Lt = int(script.shape[0]), int(script.shape[1])
+        self._chk(script, (Ps, Lt, _lib.NROAD), "script")
+        if not isinstance(index, torch.Tensor) or index.dim() != 1:
+            raise ValueError("index: expected a tensor [B]")
+        B = int(index.shape[0])
+        self._chk(index, (B,), "index", torch.int32)
+        if B and (int(index.min()) < 0 or int(index.max()) >= Ps):
+            raise ValueError("index out of range")
+        ti = int(ti)
+        if ti < 0:
+            raise ValueError("ti must be >= 0")
+        width = _lib.NROAD * self.N
+        table = self._empty(B, width) if out is None else self._chk(out, (B, width), "out")
+        _lib.check(self.lib.mpc_roads_from_script(self._h, B, Lt, int(bool(wrap)), ti, _ptr(script), _ptr(index), _ptr(table),
+                                                  self._stream()))
+        return table
 
     def fields_from_plans(self, X, opp, shape, out=None):
         """mpc_fields_from_plans: the field table [B, NFIELD * NFSRC * N] in which agent b's sources are the plans of its
