@@ -90,7 +90,7 @@ def test_config_is_validated_before_the_device_is_touched(L):
     kernels divide by Sigma), inverted Lipschitz or box bounds, non-positive Ts."""
     bad = [dict(max_total_inner=-5), dict(max_iter=0), dict(max_outer=0), dict(Sigma0=0.0), dict(Sigma0=-1.0),
            dict(L_min=1.0, L_max=0.5), dict(Ts=0.0), dict(Ts=float("nan")), dict(tau_min=0.0), dict(max_total_evals=-1),
-           dict(u_lb=[1.0, 0.0], u_ub=[-1.0, 0.3]), dict(S=2), dict(nfe=0), dict(lbfgs_memory=0), dict(alm_eps=0.0)]
+           dict(u_lb=[1.0, 0.0], u_ub=[-1.0, 0.3]), dict(S=2), dict(nfe=0), dict(nfe=17), dict(lbfgs_memory=0), dict(alm_eps=0.0)]
     for kw in bad:
         cfg = mp.default_config(mp.MODEL_KINEMATIC, 20, **kw)
         h = C.c_void_p()
