@@ -335,21 +335,14 @@ static int bind_agent_table(mpc_handle *h, TableKind kind, const double *table, 
     if (kind == TAB_FIELDS && h->cfg.constr_mode == MPC_CONSTR_DISCS)
         return fail(MPC_E_ARG, std::string(who) + ": the handle's constraints are keep-out discs (constr_mode MPC_CONSTR_DISCS): there an "
                                                   "obstacle is a disc (mpc_set_agent_discs)");
-    // a field table and a constraint table together would need kernel forms that take both: whichever comes second is refused
-    for (const TableKind other : {TAB_CONSTR, TAB_FIELDS})
-        if ((kind == TAB_FIELDS || kind == TAB_CONSTR) && kind != other && h->tab[other].table)
+    // A field, road or rate table together with a constraint table would need kernel forms that take both (with_table_form
+    // in mpc_launch.hpp has none): whichever comes second is refused, a constraint table for the first of the three in this order
+    for (const TableKind x : {TAB_FIELDS, TAB_ROADS, TAB_RATES}) {
+        const TableKind other = kind == x ? TAB_CONSTR : x;
+        if ((kind == x || kind == TAB_CONSTR) && h->tab[other].table)
             return fail(MPC_E_ARG, std::string(who) + ": a " + k_tables[other].noun + " table is bound (" + k_tables[other].setter +
-                                   "): a field table and a constraint table cannot be bound together");
-    // ... and a road table and a constraint table
-    for (const TableKind other : {TAB_CONSTR, TAB_ROADS})
-        if ((kind == TAB_ROADS || kind == TAB_CONSTR) && kind != other && h->tab[other].table)
-            return fail(MPC_E_ARG, std::string(who) + ": a " + k_tables[other].noun + " table is bound (" + k_tables[other].setter +
-                                   "): a road table and a constraint table cannot be bound together");
-    // ... and so would a rate table and a constraint table
-    if ((kind == TAB_RATES && h->tab[TAB_CONSTR].table) || (kind == TAB_CONSTR && h->tab[TAB_RATES].table))
-        return fail(MPC_E_ARG, std::string(who) + ": a " + k_tables[kind == TAB_RATES ? TAB_CONSTR : TAB_RATES].noun + " table is bound (" +
-                               k_tables[kind == TAB_RATES ? TAB_CONSTR : TAB_RATES].setter + "): a rate table and a constraint table "
-                               "cannot be bound together");
+                                   "): a " + k_tables[x].noun + " table and a constraint table cannot be bound together");
+    }
     if (P < 1 || B < 1 || !index) return fail(MPC_E_ARG, std::string(who) + ": need P >= 1 rows, B >= 1 agents and an index");
     { const int ra = check_tables_agree(h, B, who, kind); if (ra) return ra; }
     HIPCHK(hipSetDevice(h->device));
@@ -546,12 +539,7 @@ static int eval_cost_grad(mpc_handle *h, int B, const double *x0, const double *
     w.yhe = (yhat && c.m) ? yhat : h->ws.ws_yhe;
     w.psi_direct = psi;
     if (U2) { w.xe2 = const_cast<double *>(U2); w.ge2 = grad2; }
-    w.ptab = h->params().table; w.pidx = h->params().idx;
-    w.ctab = h->tab[TAB_CONSTR].table; w.cidx = h->tab[TAB_CONSTR].idx;
-    w.dtab = h->tab[TAB_DISCS].table; w.didx = h->tab[TAB_DISCS].idx;
-    w.rtab = h->tab[TAB_RATES].table; w.ridx = h->tab[TAB_RATES].idx;
-    w.ftab = h->tab[TAB_FIELDS].table; w.fidx = h->tab[TAB_FIELDS].idx;
-    w.wtab = h->tab[TAB_ROADS].table; w.widx = h->tab[TAB_ROADS].idx;
+    h->bind_tables(w, h->bound_rows());
     if (wave_path) launch_solo_eval(h, w, s, (grad ? 1 : 0) | (U2 ? 2 : 0));
     else launch_eval(h, w, s, nullptr, nullptr, grad ? B : 0, grad ? 0 : B);
     HIPCHK(hipGetLastError());
@@ -637,14 +625,7 @@ static int solve_core(mpc_handle *h, int B, const double *x0, const double *cl, 
     WorkspaceHost &w = h->ws;
     w.cl = cl; w.cl_index = cl_index; w.x0 = x0; w.xo = U; w.y = lambda; w.psi_direct = nullptr;
     w.near = near_for(h, cl);
-    const auto rows_of = [&](TableKind k) { return h->tab[k].table ? idx.of[k] : nullptr; };
-    w.ptab = h->tab[TAB_PARAMS].table; w.pidx = rows_of(TAB_PARAMS);
-    w.btab = h->tab[TAB_BOX].table; w.bidx = rows_of(TAB_BOX);
-    w.ctab = h->tab[TAB_CONSTR].table; w.cidx = rows_of(TAB_CONSTR);
-    w.dtab = h->tab[TAB_DISCS].table; w.didx = rows_of(TAB_DISCS);
-    w.rtab = h->tab[TAB_RATES].table; w.ridx = rows_of(TAB_RATES);
-    w.ftab = h->tab[TAB_FIELDS].table; w.fidx = rows_of(TAB_FIELDS);
-    w.wtab = h->tab[TAB_ROADS].table; w.widx = rows_of(TAB_ROADS);
+    h->bind_tables(w, idx);
     w.xe = w.ws_xe; w.ge = w.ws_ge; w.yhe = w.ws_yhe; w.Sig = w.ws_Sig;
     rc = run_solver(h, s); if (rc) return rc;
     if (stats) hipLaunchKernelGGL(stats_kernel, grid_for(B, 256), dim3(256), 0, s, w, stats);
@@ -765,12 +746,13 @@ static int solve_active_impl(mpc_handle *h, int B, const int32_t *active, const 
     r.list = e.list; r.count = e.count; r.nx = c.nx; r.n = c.n; r.m = c.m;
     r.x0 = const_cast<double *>(x0); r.U = U; r.lam = lambda; r.stats = stats;
     r.cl_index = cl_index; r.pidx = h->params().idx;
-    r.xs = e.xs; r.Us = e.Us; r.lams = e.lams; r.stats_s = e.stats_s; r.cis = e.cis; r.pis = e.pis;
+    r.xs = e.xs; r.Us = e.Us; r.lams = e.lams; r.stats_s = e.stats_s; r.cis = e.cis; r.pis = e.rows[TAB_PARAMS];
     hipLaunchKernelGGL(active_gather_kernel, grows, dim3(EV_BLK), 0, s, r);
-    const AgentIdx gathered = {{e.pis, e.bis, e.kis, e.dis, e.ris, e.fis, e.wis}};   // (the parameter rows ride in the gather above)
-    for (int k = TAB_BOX; k < TAB_KINDS; k++)
+    AgentIdx gathered;
+    for (int k = 0; k < TAB_KINDS; k++) gathered.of[k] = e.rows[k];
+    for (int k = TAB_BOX; k < TAB_KINDS; k++)   // (the parameter rows ride in the gather above)
         if (h->tab[k].table)
-            hipLaunchKernelGGL(active_index_kernel, gblk, dim3(EV_BLK), 0, s, e.list, e.count, h->tab[k].idx, const_cast<int32_t *>(gathered.of[k]));
+            hipLaunchKernelGGL(active_index_kernel, gblk, dim3(EV_BLK), 0, s, e.list, e.count, h->tab[k].idx, e.rows[k]);
     int *cnt = (int *)((char *)h->host_counts + 384);   // pinned (see host_counts)
     HIPCHK(hipMemcpyAsync(cnt, e.count, sizeof(int), hipMemcpyDeviceToHost, s));
     rc = bounded_sync(h, s, "mpc_solve_active"); if (rc) return rc;

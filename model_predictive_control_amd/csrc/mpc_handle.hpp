@@ -62,31 +62,22 @@ struct BoundTable {
 struct AgentIdx { const int32_t *of[TAB_KINDS]; };
 
 // The workspace as the host keeps it: the kernels' Workspace, the parameter table the per-agent kernels get with it
-// (WorkspacePA), and the bounds table of mpc_set_agent_bounds (both null: none bound), which reaches the per-agent-box
-// kernels as an argument of its own (BoxTab) and no other kernel at all; the constraint table of
-// mpc_set_agent_constraints likewise (ConTab, the constraint forms alone), and the disc table of mpc_set_agent_discs
-// (DiscTab, the disc forms alone), and the rate table of mpc_set_agent_rates (RateTab, the rate forms alone), and the field
-// table of mpc_set_agent_fields (FieldTab, the field forms alone), and the road table of mpc_set_agent_roads (RoadTab, the
-// road forms alone).
+// (WorkspacePA: ptab / pidx, a kernel argument), and the caller's other tables by kind (null: none bound).  Each of those
+// reaches the kernel forms that read it as an argument of its own -- the device struct its accessor returns -- and no other
+// kernel at all (which forms those are: with_table_form and launch_step_t in mpc_launch.hpp).
 struct WorkspaceHost : WorkspacePA {
-    const double *btab;                            // [P][MPC_NBOUND] caller's table
-    const int *bidx;                               // [B]             caller's row index per agent
-    const double *ctab;                            // [P][MPC_NCONSTR] caller's table
-    const int *cidx;                               // [B]              caller's row index per agent
-    const double *dtab;                            // [P][MPC_DISC_ROW(N)] caller's table
-    const int *didx;                               // [B]              caller's row index per agent
-    BoxTab box() const { return BoxTab{btab, bidx}; }
-    ConTab con() const { return ConTab{ctab, cidx}; }
-    const double *rtab;                            // [P][MPC_NRATE] caller's table
-    const int *ridx;                               // [B]              caller's row index per agent
-    DiscTab disc() const { return DiscTab{dtab, didx}; }
-    RateTab rate() const { return RateTab{rtab, ridx}; }
-    const double *ftab;                            // [P][MPC_FIELD_ROW(N)] caller's table
-    const int *fidx;                               // [B]              caller's row index per agent
-    FieldTab field() const { return FieldTab{ftab, fidx}; }
-    const double *wtab;                            // [P][MPC_ROAD_ROW(N)] caller's table
-    const int *widx;                               // [B]              caller's row index per agent
-    RoadTab road() const { return RoadTab{wtab, widx}; }
+    struct Tab {
+        const double *table;                       // [P][table_width(kind)] caller's table
+        const int *rows;                           // [B]                    caller's row index per agent
+    } tabs[TAB_KINDS];                             // (tabs[TAB_PARAMS] stays null: ptab / pidx above)
+    bool bound(TableKind k) const { return tabs[k].table != nullptr; }
+    template <class T> T as(TableKind k) const { return T{tabs[k].table, tabs[k].rows}; }
+    BoxTab box() const { return as<BoxTab>(TAB_BOX); }
+    ConTab con() const { return as<ConTab>(TAB_CONSTR); }
+    DiscTab disc() const { return as<DiscTab>(TAB_DISCS); }
+    RateTab rate() const { return as<RateTab>(TAB_RATES); }
+    FieldTab field() const { return as<FieldTab>(TAB_FIELDS); }
+    RoadTab road() const { return as<RoadTab>(TAB_ROADS); }
 };
 
 struct mpc_handle {
@@ -181,7 +172,14 @@ struct mpc_handle {
     const int32_t *pidx_plant = nullptr;   // parameters alone: [B] the plant's row per agent (mpc_closed_loop), null: the controller's
     const BoundTable &params() const { return tab[TAB_PARAMS]; }
     const int32_t *plant_rows() const { return pidx_plant ? pidx_plant : params().idx; }
-    AgentIdx bound_rows() const { return AgentIdx{{tab[TAB_PARAMS].idx, tab[TAB_BOX].idx, tab[TAB_CONSTR].idx, tab[TAB_DISCS].idx, tab[TAB_RATES].idx, tab[TAB_FIELDS].idx, tab[TAB_ROADS].idx}}; }
+    AgentIdx bound_rows() const { AgentIdx r; for (int k = 0; k < TAB_KINDS; k++) r.of[k] = tab[k].idx; return r; }
+    // the bound tables into workspace `w` for agents whose rows are idx.of[kind][b] (a kind with no table bound: nulls, and
+    // idx.of[kind] is not read) -- every kind, for every caller: what a kernel form does not read it is not handed
+    void bind_tables(WorkspaceHost &w, const AgentIdx &idx) const
+    {
+        w.ptab = params().table; w.pidx = params().table ? idx.of[TAB_PARAMS] : nullptr;
+        for (int k = TAB_BOX; k < TAB_KINDS; k++) w.tabs[k] = {tab[k].table, tab[k].table ? idx.of[k] : nullptr};
+    }
     size_t table_width(int kind) const { return (size_t)k_tables[kind].width + (size_t)k_tables[kind].width_per_N * (size_t)cfg.N; }
     // The persistent kernel has its box form together with the parameter form alone, and its constraint form -- as the
     // K1 kernels have theirs -- together with both.  With a table bound but not the ones its kernels come with, they run
@@ -202,7 +200,8 @@ struct mpc_handle {
     struct EventBufs {
         char *base = nullptr;
         int cap = 0;                                   // agents the arena holds
-        int *list = nullptr, *blk = nullptr, *count = nullptr, *fire = nullptr, *cis = nullptr, *pis = nullptr, *bis = nullptr, *kis = nullptr, *dis = nullptr, *ris = nullptr, *fis = nullptr, *wis = nullptr;
+        int *list = nullptr, *blk = nullptr, *count = nullptr, *fire = nullptr, *cis = nullptr;
+        int *rows[TAB_KINDS] = {};                     // the active agents' rows of the bound tables, by kind
         double *xs = nullptr, *Us = nullptr, *lams = nullptr, *stats_s = nullptr, *stats_own = nullptr;
         double *xhat = nullptr;                        // [xhat_B][nx]
         int xhat_B = 0;
@@ -454,7 +453,7 @@ static int reserve_event(mpc_handle *h, int B)
     const DevCfg &c = h->dc;
     const size_t Bp = ((size_t)B + 63) & ~(size_t)63, m = c.m ? c.m : 1, nblk = (Bp + EV_BLK - 1) / EV_BLK;
     const size_t nd = (size_t)c.nx + c.n + m + 8 + 8;            // doubles per agent: xs, Us, lams, stats_s, stats_own
-    const size_t bytes = nd * 8 * Bp + 4 * (10 * Bp + nblk + 64);  // ints: list, fire, cis, pis, bis, kis, dis, ris, fis, wis [Bp], blk [nblk], count
+    const size_t bytes = nd * 8 * Bp + 4 * ((3 + TAB_KINDS) * Bp + nblk + 64);  // ints: list, fire, cis, rows of every kind [Bp], blk [nblk], count
     char *base = nullptr;
     if (hipMalloc((void **)&base, bytes) != hipSuccess) return fail(MPC_E_ALLOC, "masked-solve staging hipMalloc failed");
     e.base = base; e.cap = (int)Bp;
@@ -463,7 +462,9 @@ static int reserve_event(mpc_handle *h, int B)
     e.xs = takeD(c.nx); e.Us = takeD(c.n); e.lams = takeD(m); e.stats_s = takeD(8); e.stats_own = takeD(8);
     int *ip = (int *)dp;
     auto takeI = [&](size_t cnt) { int *r = ip; ip += cnt; return r; };
-    e.list = takeI(Bp); e.fire = takeI(Bp); e.cis = takeI(Bp); e.pis = takeI(Bp); e.bis = takeI(Bp); e.kis = takeI(Bp); e.dis = takeI(Bp); e.ris = takeI(Bp); e.fis = takeI(Bp); e.wis = takeI(Bp); e.blk = takeI(nblk); e.count = takeI(64);
+    e.list = takeI(Bp); e.fire = takeI(Bp); e.cis = takeI(Bp);
+    for (int *&rows : e.rows) rows = takeI(Bp);
+    e.blk = takeI(nblk); e.count = takeI(64);
     HIPCHK(hipMemset(base, 0, bytes));
     return MPC_OK;
 }

@@ -1,14 +1,11 @@
 // mpc_launch.hpp -- host side of libmpc_hip.so, part 2: from the handle's run-time state to ONE instantiation of each
-// kernel template.  Every run-time flag becomes a template argument in one place (with_flag / with_model /
-// with_model_table / with_hist_variant), so every kernel template is named at exactly one launch site and a new flag is
-// added once.  What is instantiated is what the `if constexpr`s below let through -- never the cross product: the
-// Pacejka model has no fused K1b + K1c, lookahead exists for <PAC, NE = 1> alone, adjoint_kernel has no per-agent form,
-// the constraint forms exist beside the parameter form alone (K1b, the wave evaluation), beside the parameter and box
-// forms alone (the persistent kernel) and for constrained problems alone (the step kernel); the disc forms stand where
-// the constraint forms stand, except that the step kernel has none (it reads no discs); the rate forms (RateTab alone, and
-// DiscTab + RateTab) stand where the disc forms stand, never with the lookahead; the field forms are RateTab + FieldTab
-// alone, where the rate forms stand.  Where a form needs a table the caller has not bound, with_own_params /
-// with_own_box / with_own_rates put the handle's own one-row table in its place.
+// kernel template.  Every run-time choice becomes template arguments in one place: a flag in with_flag, the model in
+// with_model / with_model_table, the L-BFGS history variant in with_hist_variant, and the per-agent tables a kernel takes
+// as its trailing pack in with_table_form -- the one list of the table forms that exist.  So each kernel template is named
+// at one launch site, and a new flag or table is added once.  What is instantiated is what these functions and the
+// `if constexpr`s below let through, never the cross product: the Pacejka model has no fused K1b + K1c, the lookahead
+// exists for <PAC, NE = 1> without a table form alone, adjoint_kernel has no per-agent form, and the step kernel has
+// forms of its own (launch_step_t: it reads the box and the constraint data and no other table).
 #pragma once
 #include "mpc_handle.hpp"
 
@@ -31,25 +28,45 @@ template <class F> static void with_model_table(const mpc_handle *h, const int32
     });
 }
 
-// The workspace as the constraint forms of the K1 kernels and the box and constraint forms of the persistent kernel take
-// it: they exist together with the parameter form alone, so without a parameter table of the caller's they run on the
-// handle's own one-row table (mpc_handle::own_ptab; its index of zeros needs no slicing per group)
+// The workspace as every kernel form with a table argument takes it: those forms exist together with the parameter form
+// alone (PA = true), so without a parameter table of the caller's they run on the handle's own one-row table
+// (mpc_handle::own_ptab; its index of zeros needs no slicing per group)
 static WorkspacePA with_own_params(const mpc_handle *h, const WorkspaceHost &w)
 {
     WorkspacePA wp = w;
     if (!wp.ptab) { wp.ptab = h->own_ptab; wp.pidx = h->own_pidx; }
     return wp;
 }
-// ... and the box as the constraint form of the persistent kernel takes it: it exists together with the box form alone,
-// so without a bounds table of the caller's it runs on the handle's own one-row box table (mpc_handle::own_btab)
-static BoxTab with_own_box(const mpc_handle *h, const WorkspaceHost &w) { return w.btab ? w.box() : BoxTab{h->own_btab, h->own_pidx}; }
-// ... and the rates as the field forms take them: they exist behind the rate form alone, so without a rate table of the
-// caller's they run on the handle's own one-row table of zeros (mpc_handle::own_rtab: zero weights change no bit)
-static RateTab with_own_rates(const mpc_handle *h, const WorkspaceHost &w) { return w.rtab ? w.rate() : RateTab{h->own_rtab, h->own_pidx}; }
-// ... and the fields as the road forms of a handle without discs take them: <..., RateTab, FieldTab, RoadTab> alone, so
-// without a field table of the caller's they run on the handle's own one-row table of zeros (mpc_handle::own_ftab: A == 0
-// is skipped by a branch and changes no bit)
-static FieldTab with_own_fields(const mpc_handle *h, const WorkspaceHost &w) { return w.ftab ? w.field() : FieldTab{h->own_ftab, h->own_pidx}; }
+// ... and the box as the table forms of the persistent kernel take it: they exist behind the box form alone, so
+// without a bounds table of the caller's they run on the handle's own one-row box table (mpc_handle::own_btab)
+static BoxTab with_own_box(const mpc_handle *h, const WorkspaceHost &w) { return w.bound(TAB_BOX) ? w.box() : BoxTab{h->own_btab, h->own_pidx}; }
+
+// The table forms of stage_kernel, stage_adjoint_kernel, solo_eval_kernel and (behind BoxTab) solo_kernel: which tables
+// view `w` hands its kernels as their trailing pack t..., decided by what is bound, the first that applies:
+//   1. a road table         on a disc handle <DiscTab, RateTab, RoadTab>, elsewhere <RateTab, FieldTab, RoadTab>
+//   2. a constraint table   <ConTab>
+//   3. a field table        <RateTab, FieldTab>
+//   4. a rate table         beside a disc table <DiscTab, RateTab>, else <RateTab>
+//   5. a disc table         <DiscTab>                                  (a handle of MPC_CONSTR_DISCS)
+//   6. none of them         the empty pack: the kernels without a table argument
+// (bind_agent_table refuses the pairs no form takes).  A form that stands behind a table the caller has not bound runs on
+// the handle's own one-row table of zeros in its place (`rates`: mpc_handle::own_rtab, zero weights; `fields`:
+// mpc_handle::own_ftab, A == 0 is skipped by a branch -- neither changes a bit).  f(PA, wp, t...): a table form is a form
+// of the per-agent kernel (PA = std::true_type, wp = with_own_params), the empty pack keeps the run-time choice (PA says
+// whether a parameter table is bound, wp = w) -- so naming kernel<..., PA(), decltype(t)...> instantiates these forms alone.
+template <class F> static void with_table_form(const mpc_handle *h, const WorkspaceHost &w, F &&f)
+{
+    const auto rates = [&] { return w.bound(TAB_RATES) ? w.rate() : RateTab{h->own_rtab, h->own_pidx}; };
+    const auto fields = [&] { return w.bound(TAB_FIELDS) ? w.field() : FieldTab{h->own_ftab, h->own_pidx}; };
+    const auto form = [&](auto... t) { f(std::true_type{}, with_own_params(h, w), t...); };
+    const bool discs = w.bound(TAB_DISCS);
+    if (w.bound(TAB_ROADS)) { if (discs) form(w.disc(), rates(), w.road()); else form(rates(), fields(), w.road()); }
+    else if (w.bound(TAB_CONSTR)) form(w.con());
+    else if (w.bound(TAB_FIELDS)) form(rates(), w.field());
+    else if (w.bound(TAB_RATES)) { if (discs) form(w.disc(), w.rate()); else form(w.rate()); }
+    else if (discs) form(w.disc());
+    else with_flag(w.ptab != nullptr, [&](auto PA) { f(PA, WorkspacePA(w)); });
+}
 
 // How the step kernel and the persistent kernel read an agent's L-BFGS history -- f(int_c<NE>, int_c<MC>), the two
 // kernels' template arguments (results do not depend on the choice).  NE: elements per lane, 1 up to n = 64 and 2
@@ -111,43 +128,10 @@ static bool launch_eval_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
             const int spb = FUSED_BLK / c.N;
             const int gb = (nblk * 64 + spb - 1) / spb;
             const size_t flds = sizeof(double) * (size_t)(JS + 1) * c.N * spb;
-            if (w.wtab)     // a road table is bound: the road forms of K1b, <rate, field, road> or on a disc handle <discs, rate, road> (here and below)
-                with_flags(shared, w.dtab != nullptr, [&](auto SH, auto DA) {
-                    if constexpr (DA())
-                        hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, DiscTab, RateTab, RoadTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
-                                           with_own_params(h, w), counts, nG, nC, desc, w.disc(), with_own_rates(h, w), w.road());
-                    else
-                        hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, RateTab, FieldTab, RoadTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
-                                           with_own_params(h, w), counts, nG, nC, desc, with_own_rates(h, w), with_own_fields(h, w), w.road());
-                });
-            else if (w.ctab)     // a constraint table is bound: the constraint form of K1b (here and below)
-                with_flag(shared, [&](auto SH) {
-                    hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, ConTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
-                                       with_own_params(h, w), counts, nG, nC, desc, w.con());
-                });
-            else if (w.ftab)     // a field table is bound: the field form of K1b, behind the rate form (here and below)
-                with_flag(shared, [&](auto SH) {
-                    hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, RateTab, FieldTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
-                                       with_own_params(h, w), counts, nG, nC, desc, with_own_rates(h, w), w.field());
-                });
-            else if (w.rtab)     // a rate table is bound: the rate form of K1b, beside the disc form where discs are bound too (here and below)
-                with_flags(shared, w.dtab != nullptr, [&](auto SH, auto DA) {
-                    if constexpr (DA())
-                        hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, DiscTab, RateTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
-                                           with_own_params(h, w), counts, nG, nC, desc, w.disc(), w.rate());
-                    else
-                        hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, RateTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
-                                           with_own_params(h, w), counts, nG, nC, desc, w.rate());
-                });
-            else if (w.dtab)     // a disc table is bound (a handle of MPC_CONSTR_DISCS): the disc form of K1b (here and below)
-                with_flag(shared, [&](auto SH) {
-                    hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), true, DiscTab>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
-                                       with_own_params(h, w), counts, nG, nC, desc, w.disc());
-                });
-            else
-            with_flags(shared, pa, [&](auto SH, auto PA) {
-                hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), PA()>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c, w, counts, nG, nC, desc);
-            });
+            with_table_form(h, w, [&](auto PA, const WorkspacePA &wp, auto... t) { with_flag(shared, [&](auto SH) {
+                hipLaunchKernelGGL((stage_adjoint_kernel<MODEL, SH(), PA(), decltype(t)...>), dim3((unsigned)gb), dim3(FUSED_BLK), flds, s, c,
+                                   wp, counts, nG, nC, desc, t...);
+            }); });
             if (evb) (void)hipEventRecord(evb, s);
             return true;
         }
@@ -156,43 +140,10 @@ static bool launch_eval_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
     // block on XCD sb % 8 so that K1c could read records from the L2 they were written to -- no change: the 13 MB
     // of records per XCD and launch pass through a 4 MB L2 long before K1c starts)
     const size_t xy_lds = (shared && w.near.gmeta && c.S <= GRID_LDS_MAX_S) ? sizeof(double) * 2 * (size_t)c.S : 0;
-    if (w.wtab)
-        with_flags(shared, w.dtab != nullptr, [&](auto SH, auto DA) {
-            if constexpr (DA())
-                hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, DiscTab, RateTab, RoadTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
-                                   with_own_params(h, w), counts, nG, nC, nblk, w.disc(), with_own_rates(h, w), w.road());
-            else
-                hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, RateTab, FieldTab, RoadTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
-                                   with_own_params(h, w), counts, nG, nC, nblk, with_own_rates(h, w), with_own_fields(h, w), w.road());
-        });
-    else if (w.ctab)
-        with_flag(shared, [&](auto SH) {
-            hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, ConTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
-                               with_own_params(h, w), counts, nG, nC, nblk, w.con());
-        });
-    else if (w.ftab)
-        with_flag(shared, [&](auto SH) {
-            hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, RateTab, FieldTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
-                               with_own_params(h, w), counts, nG, nC, nblk, with_own_rates(h, w), w.field());
-        });
-    else if (w.rtab)
-        with_flags(shared, w.dtab != nullptr, [&](auto SH, auto DA) {
-            if constexpr (DA())
-                hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, DiscTab, RateTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
-                                   with_own_params(h, w), counts, nG, nC, nblk, w.disc(), w.rate());
-            else
-                hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, RateTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
-                                   with_own_params(h, w), counts, nG, nC, nblk, w.rate());
-        });
-    else if (w.dtab)
-        with_flag(shared, [&](auto SH) {
-            hipLaunchKernelGGL((stage_kernel<MODEL, SH(), true, DiscTab>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
-                               with_own_params(h, w), counts, nG, nC, nblk, w.disc());
-        });
-    else
-    with_flags(shared, pa, [&](auto SH, auto PA) {
-        hipLaunchKernelGGL((stage_kernel<MODEL, SH(), PA()>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c, w, counts, nG, nC, nblk);
-    });
+    with_table_form(h, w, [&](auto PA, const WorkspacePA &wp, auto... t) { with_flag(shared, [&](auto SH) {
+        hipLaunchKernelGGL((stage_kernel<MODEL, SH(), PA(), decltype(t)...>), dim3((unsigned)(nblk * c.N)), dim3(64), xy_lds, s, c,
+                           wp, counts, nG, nC, nblk, t...);
+    }); });
     if (evb) (void)hipEventRecord(evb, s);
     hipLaunchKernelGGL((adjoint_kernel<MODEL>), dim3((unsigned)nblk), dim3(64), 0, s, c, w, counts, nG, nC, desc);
     return false;
@@ -207,58 +158,10 @@ static bool launch_eval(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, co
 static void launch_solo_eval(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, int want_grad)
 {
     const DevCfg &c = h->dc;
-    if (w.wtab) {
-        with_model(c.model, [&](auto MODEL) {
-            const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
-            if (w.dtab)
-                hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, DiscTab, RateTab, RoadTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
-                                   want_grad, w.disc(), with_own_rates(h, w), w.road());
-            else
-                hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, RateTab, FieldTab, RoadTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
-                                   want_grad, with_own_rates(h, w), with_own_fields(h, w), w.road());
-        });
-        return;
-    }
-    if (w.ctab) {
-        with_model(c.model, [&](auto MODEL) {
-            const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
-            hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, ConTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
-                               want_grad, w.con());
-        });
-        return;
-    }
-    if (w.ftab) {
-        with_model(c.model, [&](auto MODEL) {
-            const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
-            hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, RateTab, FieldTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
-                               want_grad, with_own_rates(h, w), w.field());
-        });
-        return;
-    }
-    if (w.rtab) {
-        with_model(c.model, [&](auto MODEL) {
-            const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
-            if (w.dtab)
-                hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, DiscTab, RateTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
-                                   want_grad, w.disc(), w.rate());
-            else
-                hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, RateTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
-                                   want_grad, w.rate());
-        });
-        return;
-    }
-    if (w.dtab) {
-        with_model(c.model, [&](auto MODEL) {
-            const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
-            hipLaunchKernelGGL((solo_eval_kernel<MODEL(), true, DiscTab>), dim3((unsigned)w.B), dim3(64), lds, s, c, with_own_params(h, w),
-                               want_grad, w.disc());
-        });
-        return;
-    }
-    with_model_table(h, h->params().idx, [&](auto MODEL, auto PA, auto...) {
+    with_model(c.model, [&](auto MODEL) { with_table_form(h, w, [&](auto PA, const WorkspacePA &wp, auto... t) {
         const size_t lds = sizeof(double) * solo_lds_doubles<MODEL()>(c.nfe, c.N, c.n, c.M, false);
-        hipLaunchKernelGGL((solo_eval_kernel<MODEL(), PA()>), dim3((unsigned)w.B), dim3(64), lds, s, c, w, want_grad);
-    });
+        hipLaunchKernelGGL((solo_eval_kernel<MODEL(), PA(), decltype(t)...>), dim3((unsigned)w.B), dim3(64), lds, s, c, wp, want_grad, t...);
+    }); });
 }
 
 // LDS copy of an agent's L-BFGS history in the step kernel (MC < 0): the ring slots 0 .. P - 1, 2 P n doubles per
@@ -325,10 +228,10 @@ static void launch_step_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
     const int apb = apb_env == 64 || apb_env == 32 || apb_env == 16 || apb_env == 8 || apb_env == 4 ? apb_env
                   : w.B >= 32768 ? 64 : w.B >= 16384 ? (lean ? 32 : 64) : w.B >= 6144 ? 16 : 4;
     const int nstep = (w.B + apb - 1) / apb;
-    // (w.ctab: a constraint table is bound -- on a constrained problem, or it would not be -- the constraint form,
+    // (a constraint table is bound -- on a constrained problem, or it would not be -- the constraint form,
     // without or with the box form)
-    if (w.ctab) {
-        with_flag(w.btab != nullptr, [&](auto BA) {
+    if (w.bound(TAB_CONSTR)) {
+        with_flag(w.bound(TAB_BOX), [&](auto BA) {
             if constexpr (BA())
                 hipLaunchKernelGGL((step_kernel_box_con<NE, MC>), dim3((unsigned)(nstep + nchain)), dim3(64 * STEP_WAVES), lds,
                                    s, dcl, w, w.box(), w.con(), lists, counts, counts_next, apb, nstep, par, P);
@@ -338,8 +241,8 @@ static void launch_step_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
         });
         return;
     }
-    // (w.btab: a bounds table is bound, the per-agent-box form -- the one kernel of the round path that reads the box)
-    with_flags(h->dc.m != 0, w.btab != nullptr, [&](auto HASM, auto BA) {
+    // (a bounds table is bound: the per-agent-box form -- the one kernel of the round path that reads the box)
+    with_flags(h->dc.m != 0, w.bound(TAB_BOX), [&](auto HASM, auto BA) {
         if constexpr (BA())
             hipLaunchKernelGGL((step_kernel_box<NE, MC, HASM()>), dim3((unsigned)(nstep + nchain)), dim3(64 * STEP_WAVES), lds,
                                s, dcl, w, w.box(), lists, counts, counts_next, apb, nstep, par, P);
@@ -371,61 +274,22 @@ static void launch_solo_t(mpc_handle *h, const WorkspaceHost &v, hipStream_t s, 
     const size_t lds = sizeof(double) * SOLO_WAVES * solo_lds_doubles<MODEL>(c.nfe, c.N, c.n, c.M, MC < 0, la);
     int nblk = (bound + SOLO_WAVES - 1) / SOLO_WAVES;
     nblk = std::max(1, std::min(nblk, 4 * SoloOcc<MODEL>::WPS * h->num_cus)); // what is resident (registers); the rest queues
-    // (v.ptab: a parameter table is bound, the per-agent variant.  The lookahead kernel exists where solo_lookahead can
-    // say yes: Pacejka model, one element per lane)
-    // v.btab: a bounds table is bound, the box form, which exists together with the parameter form alone (with_own_params)
-    // v.ctab: a constraint table is bound, the constraint form, which exists together with the box form alone
-    // (with_own_box; never with the lookahead: m > 0)
-    // v.wtab: a road table is bound, the road forms -- behind the disc and rate forms on a disc handle, behind the rate and
-    // field forms elsewhere (the caller's tables or the handle's zeros); never with the lookahead, like the rate forms
-    if (v.wtab) {
-        if (v.dtab)
-            hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, DiscTab, RateTab, RoadTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
-                               with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), v.disc(), with_own_rates(h, v), v.road());
-        else
-            hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, RateTab, FieldTab, RoadTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
-                               with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), with_own_rates(h, v), with_own_fields(h, v), v.road());
-        return;
-    }
-    if (v.ctab) {
-        hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, ConTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
-                           with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), v.con());
-        return;
-    }
-    // v.ftab: a field table is bound, the field form, behind the rate form (the caller's rate table or the handle's zeros)
-    if (v.ftab) {
-        hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, RateTab, FieldTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
-                           with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), with_own_rates(h, v), v.field());
-        return;
-    }
-    // v.rtab: a rate table is bound, the rate form, on the disc form's terms and beside it where discs are bound too
-    // (the kernel without the lookahead on the lookahead's LDS size: results do not depend on the lookahead)
-    if (v.rtab) {
-        if (v.dtab)
-            hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, DiscTab, RateTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
-                               with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), v.disc(), v.rate());
-        else
-            hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, RateTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
-                               with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), v.rate());
-        return;
-    }
-    // v.dtab: a disc table is bound, the disc form, on the constraint form's terms
-    if (v.dtab) {
-        hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, false, true, BoxTab, DiscTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
-                           with_own_params(h, v), list, ctr, max_trips, with_own_box(h, v), v.disc());
-        return;
-    }
-    if (v.btab) {
-        with_flag(la, [&](auto LA) {
-            if constexpr (!LA() || (MODEL == PAC && NE == 1))
-                hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, LA(), true, BoxTab>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
-                                   with_own_params(h, v), list, ctr, max_trips, v.box());
+    // The kernel's trailing pack bt...: empty (a parameter table bound or not), <BoxTab> when a bounds table is bound, and
+    // <BoxTab, t...> for every table form of with_table_form (the caller's box or the handle's own).  The lookahead
+    // kernel exists where solo_lookahead can say yes -- Pacejka model, one element per lane -- and without a table form:
+    // those run the kernel without it on the lookahead's LDS size (results do not depend on the lookahead).
+    const auto launch = [&](auto PA, const WorkspacePA &wp, auto... bt) {
+        constexpr bool HAS_LA = MODEL == PAC && NE == 1 && sizeof...(bt) <= 1;
+        with_flag(la && HAS_LA, [&](auto LA) {
+            if constexpr (!LA() || HAS_LA)
+                hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, LA(), PA(), decltype(bt)...>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c,
+                                   wp, list, ctr, max_trips, bt...);
         });
-        return;
-    }
-    with_flags(la, v.ptab != nullptr, [&](auto LA, auto PA) {
-        if constexpr (!LA() || (MODEL == PAC && NE == 1))
-            hipLaunchKernelGGL((solo_kernel<MODEL, NE, MC, LA(), PA()>), dim3((unsigned)nblk), dim3(64 * SOLO_WAVES), lds, s, c, v, list, ctr, max_trips);
+    };
+    with_table_form(h, v, [&](auto PA, const WorkspacePA &wp, auto... t) {
+        if constexpr (sizeof...(t) != 0) launch(PA, wp, with_own_box(h, v), t...);
+        else if (v.bound(TAB_BOX)) launch(std::true_type{}, with_own_params(h, v), v.box());
+        else launch(PA, wp);
     });
 }
 static void launch_solo(mpc_handle *h, const WorkspaceHost &v, hipStream_t s, int *ctr, bool listed, int bound,

@@ -20,8 +20,9 @@ static WorkspaceHost group_view(const WorkspaceHost &w, const DevCfg &c, int g, 
     v.yhe = w.yhe + (size_t)lo * m;
     v.rec = w.rec + (size_t)lo * REC;
     if (w.cl_index) v.cl_index = w.cl_index + lo;
-    for (const int **rows : {&v.pidx, &v.bidx, &v.cidx, &v.didx, &v.ridx, &v.fidx, &v.widx})   // the per-agent row indices of the bound tables
-        if (*rows) *rows += lo;
+    if (w.pidx) v.pidx = w.pidx + lo;   // the per-agent row indices of the bound tables
+    for (WorkspaceHost::Tab &t : v.tabs)
+        if (t.rows) t.rows += lo;
     const size_t soff = 2 * (size_t)lo + 64 * (size_t)g; // disjoint slot intervals inside the shared scratch
     v.trajx = w.trajx + soff; v.useq = w.useq + soff; v.stage_L = w.stage_L + soff; v.jac = w.jac + soff;
     v.agent_of = w.agent_of + soff;

@@ -181,7 +181,7 @@ __device__ __forceinline__ StageRate stage_rate_uniform(const RateTab &t, int a,
 }
 // The field table of mpc_set_agent_fields, as the field forms of the kernels receive it: the LAST trailing argument, behind
 // the RateTab -- the field forms are <..., RateTab, FieldTab> alone (no cross product: without a rate table of the
-// caller's the host puts the handle's own one-row table of zero weights in its place, with_own_rates in mpc_launch.hpp,
+// caller's the host puts the handle's own one-row table of zero weights in its place, with_table_form in mpc_launch.hpp,
 // and zero weights change no bit).  Never beside a DiscTab or a ConTab: the binder refuses both.
 struct FieldTab {
     const double *ftab;                            // [P][N][NFIELD][NFSRC] caller's table
@@ -201,7 +201,7 @@ __device__ __forceinline__ StageField stage_field_uniform(const FieldTab &t, int
 // The road table of mpc_set_agent_roads, as the road forms of the kernels receive it: the LAST trailing argument.  Two
 // families and no cross product beyond them: <..., RateTab, FieldTab, RoadTab> on every handle that is not a disc handle
 // (a missing rate table is the handle's own one-row table of zero weights, a missing field table the handle's own one-row
-// table of zeros: with_own_rates, with_own_fields in mpc_launch.hpp -- neither changes a bit), and <..., DiscTab, RateTab,
+// table of zeros: with_table_form in mpc_launch.hpp -- neither changes a bit), and <..., DiscTab, RateTab,
 // RoadTab> on disc handles.  Never beside a ConTab: the binder refuses it.
 struct RoadTab {
     const double *wtab;                            // [P][N][NROAD] caller's table
