@@ -408,32 +408,70 @@ static void launch_rate_prev(mpc_handle *h, hipStream_t s, int B, const double *
         hipLaunchKernelGGL(rate_prev_kernel, grid_for(B, 64), dim3(64), 0, s, B, h->cfg.N, U, held, fire, const_cast<double *>(rt.table), rt.idx);
 }
 
-// The discs of everybody's opponents from everybody's plans: a pure gather (discs_from_plans_kernel), asynchronous
-extern "C" int mpc_discs_from_plans(mpc_handle *h, int B, const double *X, const int32_t *opp, const double *radius,
-                                    double *table, void *stream)
+// What the loops that rewrite a per-agent table in place (the traffic loops, the obstacle loop) ask of it: `table` is the
+// bound table of `kind`, with a row per agent
+static int check_rewritten_table(const mpc_handle *h, TableKind kind, const double *table, int B, const std::string &who)
 {
-    int rc = check_common(h, B, "mpc_discs_from_plans"); if (rc) return rc;
-    if (B == 0) return MPC_OK;
-    if (!X || !opp || !radius || !table) return fail(MPC_E_ARG, "mpc_discs_from_plans: null buffer");
-    const size_t words = (size_t)B * h->cfg.N * MPC_NDISC;
-    hipLaunchKernelGGL(discs_from_plans_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, h->cfg.N,
-                       h->dc.nx, X, opp, radius, table);
+    const BoundTable &dt = h->tab[kind];
+    if (!table || table != dt.table)
+        return fail(MPC_E_ARG, who + ": table must be the " + k_tables[kind].noun + " table that is bound (" + k_tables[kind].setter +
+                               "): the loop rewrites it in place");
+    if (dt.rows != B)
+        return fail(MPC_E_ARG, who + ": the bound " + k_tables[kind].noun + " table has " + std::to_string(dt.rows) +
+                               " rows, the loop needs one per agent (P == B = " + std::to_string(B) + ", index 0 .. B-1)");
+    return MPC_OK;
+}
+// The body of every closed loop whose step ends in plant_step_kernel: T times before(t), the solve, u_{-1} into the rate
+// table, the plant step, after(t) -- before and after launch what the loop does around a step and return an rc -- then
+// the check for a failed launch.  The final wait is the caller's.  (The event-triggered loops have another step.)
+template <class Before, class After>
+static int plant_loop(mpc_handle *h, int B, int T, int shift, double *x, const double *cl, const int32_t *cl_index, double *U,
+                      double *lambda, double *traj_x, double *traj_u, int32_t *fail_count, double *stats, void *stream, Before before,
+                      After after)
+{
+    // the solves' statistics: into the caller's buffer, or the handle's stage buffer
+    int rc = stats ? MPC_OK : reserve_stage(h, sizeof(double) * 8 * (size_t)B); if (rc) return rc;
+    double *st = stats ? stats : h->stage;
+    hipStream_t s = (hipStream_t)stream;
+    for (int t = 0; t < T; t++) {
+        rc = before(t); if (rc) return rc;
+        rc = mpc_solve_batch(h, B, x, cl, cl_index, U, lambda, st, stream); if (rc) return rc;
+        launch_rate_prev(h, s, B, U, nullptr, nullptr);
+        // bound parameter table: the controller solves with row pidx[b], the plant advances with row pidx_plant[b] (null: the same)
+        with_model_table(h, h->plant_rows(), [&](auto MODEL, auto PA, auto... pt) {
+            hipLaunchKernelGGL((plant_step_kernel<MODEL(), PA(), decltype(pt)...>), grid_for(B, 64), dim3(64), 0,
+                               s, h->dc, B, t, T, shift, x, U, traj_x, traj_u, st, fail_count, pt...);
+        });
+        rc = after(t); if (rc) return rc;
+    }
     HIPCHK(hipGetLastError());
     return MPC_OK;
 }
 
-// The risk fields of everybody's opponents from everybody's plans (fields_from_plans_kernel), asynchronous
+// What the two public gathers from plans share (`kernel`: discs_from_plans_kernel with `per` = radius [B], or
+// fields_from_plans_kernel with `per` = shape [B][4]): a pure gather, asynchronous
+template <class Kernel>
+static int rows_from_plans(const std::string &who, Kernel kernel, mpc_handle *h, int B, const double *X, const int32_t *opp,
+                           const double *per, double *table, void *stream)
+{
+    int rc = check_common(h, B, who.c_str()); if (rc) return rc;
+    if (B == 0) return MPC_OK;
+    if (!X || !opp || !per || !table) return fail(MPC_E_ARG, who + ": null buffer");
+    const size_t words = (size_t)B * h->cfg.N * MPC_NDISC;   // (== MPC_NFIELD)
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, h->cfg.N, h->dc.nx, X, opp,
+                       per, table);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+extern "C" int mpc_discs_from_plans(mpc_handle *h, int B, const double *X, const int32_t *opp, const double *radius,
+                                    double *table, void *stream)
+{
+    return rows_from_plans("mpc_discs_from_plans", discs_from_plans_kernel, h, B, X, opp, radius, table, stream);
+}
 extern "C" int mpc_fields_from_plans(mpc_handle *h, int B, const double *X, const int32_t *opp, const double *shape,
                                      double *table, void *stream)
 {
-    int rc = check_common(h, B, "mpc_fields_from_plans"); if (rc) return rc;
-    if (B == 0) return MPC_OK;
-    if (!X || !opp || !shape || !table) return fail(MPC_E_ARG, "mpc_fields_from_plans: null buffer");
-    const size_t words = (size_t)B * h->cfg.N * MPC_NFIELD;
-    hipLaunchKernelGGL(fields_from_plans_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, h->cfg.N,
-                       h->dc.nx, X, opp, shape, table);
-    HIPCHK(hipGetLastError());
-    return MPC_OK;
+    return rows_from_plans("mpc_fields_from_plans", fields_from_plans_kernel, h, B, X, opp, shape, table, stream);
 }
 
 extern "C" int mpc_rhs(mpc_handle *h, int B, const double *x, const double *u, double *dx, void *stream)
@@ -708,23 +746,12 @@ extern "C" int mpc_closed_loop(mpc_handle *h, int B, int T, int shift, double *x
     if (c.m && !lambda) return fail(MPC_E_ARG, "mpc_closed_loop: lambda is required when m > 0");
     rc = check_tables(h, B, "mpc_closed_loop", READS_ALL, true); if (rc) return rc;
     rc = check_rate_rows(h, B, "mpc_closed_loop"); if (rc) return rc;
-    // bound table: the controller solves with row pidx[b], the plant advances with row pidx_plant[b] (null: the same)
-    hipStream_t s = (hipStream_t)stream;
-    double *st = stats;
-    if (!st) {
-        rc = reserve_stage(h, sizeof(double) * 8 * (size_t)B); if (rc) return rc;
-        st = h->stage;
-    }
-    for (int t = 0; t < T; t++) {
-        rc = mpc_solve_batch(h, B, x, cl, cl_index, U, lambda, st, stream); if (rc) return rc;
-        launch_rate_prev(h, s, B, U, nullptr, nullptr);
-        with_model_table(h, h->plant_rows(), [&](auto MODEL, auto PA, auto... pt) {
-            hipLaunchKernelGGL((plant_step_kernel<MODEL(), PA(), decltype(pt)...>), grid_for(B, 64), dim3(64), 0,
-                               s, c, B, t, T, shift, x, U, traj_x, traj_u, st, fail_count, pt...);
-        });
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
+    const auto nothing = [](int) -> int { return MPC_OK; };
+    rc = plant_loop(h, B, T, shift, x, cl, cl_index, U, lambda, traj_x, traj_u, fail_count, stats, stream, nothing, nothing);
+    if (rc) return rc;
+    // (a plain wait here, bounded_sync in every other loop: they differ in what a device that stops answering does to the
+    // call; making them one is left to a change of its own)
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     return MPC_OK;
 }
 
@@ -1030,41 +1057,27 @@ static int closed_loop_traffic_impl(const std::string &who, TableKind kind, mpc_
                                     double *table, double *traj_x, double *traj_u, int32_t *traj_opp, double *traj_clear,
                                     int32_t *fail_count, double *stats, void *stream, Gather gather)
 {
-    const BoundTable &dt = h->tab[kind];
     int rc = check_tables(h, B, who.c_str(), READS_ALL, true); if (rc) return rc;
-    if (!table || table != dt.table)
-        return fail(MPC_E_ARG, who + ": table must be the " + k_tables[kind].noun + " table that is bound (" + k_tables[kind].setter +
-                               "): the loop rewrites it in place");
-    if (dt.rows != B)
-        return fail(MPC_E_ARG, who + ": the bound " + k_tables[kind].noun + " table has " + std::to_string(dt.rows) +
-                               " rows, the loop needs one per agent (P == B = " + std::to_string(B) + ", index 0 .. B-1)");
+    rc = check_rewritten_table(h, kind, table, B, who); if (rc) return rc;
     rc = check_rate_rows(h, B, who); if (rc) return rc;
     if (B == 0 || T == 0) return MPC_OK;
     if (!x || !cl || !U || (h->dc.m && !lambda)) return fail(MPC_E_ARG, who + ": null buffer");
     rc = reserve_traffic(h, B); if (rc) return rc;
-    const DevCfg &c = h->dc;
+    const int N = h->dc.N;
     mpc_handle::TrafficBufs &tr = h->tr;
     hipStream_t s = (hipStream_t)stream;
-    double *st = stats;
-    if (!st) {
-        rc = reserve_stage(h, sizeof(double) * 8 * (size_t)B); if (rc) return rc;
-        st = h->stage;
-    }
-    for (int t = 0; t < T; t++) {
-        rc = mpc_rollout(h, B, c.N, x, U, tr.X, stream); if (rc) return rc;
-        launch_opponents(h, s, B, G, c.N, tr.X, radius, reach, tr.opp, traj_opp ? traj_opp + (size_t)t * MPC_NDISC : nullptr,
+    const auto before = [&](int t) -> int {
+        const int rr = mpc_rollout(h, B, N, x, U, tr.X, stream); if (rr) return rr;
+        launch_opponents(h, s, B, G, N, tr.X, radius, reach, tr.opp, traj_opp ? traj_opp + (size_t)t * MPC_NDISC : nullptr,
                          (size_t)T * MPC_NDISC, nullptr, 0, 0);
-        rc = gather(tr.X, tr.opp); if (rc) return rc;
-        rc = mpc_solve_batch(h, B, x, cl, cl_index, U, lambda, st, stream); if (rc) return rc;
-        launch_rate_prev(h, s, B, U, nullptr, nullptr);
-        with_model_table(h, h->plant_rows(), [&](auto MODEL, auto PA, auto... pt) {
-            hipLaunchKernelGGL((plant_step_kernel<MODEL(), PA(), decltype(pt)...>), grid_for(B, 64), dim3(64), 0,
-                               s, c, B, t, T, shift, x, U, traj_x, traj_u, st, fail_count, pt...);
-        });
-        if (traj_clear)
-            launch_opponents(h, s, B, G, 1, x, radius, INFINITY, nullptr, nullptr, 0, traj_clear + t, (size_t)T, 1);
-    }
-    HIPCHK(hipGetLastError());
+        return gather(tr.X, tr.opp);
+    };
+    const auto after = [&](int t) -> int {
+        if (traj_clear) launch_opponents(h, s, B, G, 1, x, radius, INFINITY, nullptr, nullptr, 0, traj_clear + t, (size_t)T, 1);
+        return MPC_OK;
+    };
+    rc = plant_loop(h, B, T, shift, x, cl, cl_index, U, lambda, traj_x, traj_u, fail_count, stats, stream, before, after);
+    if (rc) return rc;
     return bounded_sync(h, s, who.c_str());
 }
 
@@ -1136,12 +1149,10 @@ static void launch_obstacles(mpc_handle *h, hipStream_t s, int B, int G, int K, 
     while (Kp < K) Kp <<= 1;
     const int spw = 64 / std::max(Gp, Kp), scenes = B / G;
     const dim3 grid((unsigned)((scenes + spw - 1) / spw));
-    if (obstacle_discs(h))
-        hipLaunchKernelGGL(obstacles_kernel<3>, grid, dim3(TR_BLK), 0, s, B, G, K, Kp, spw, Lt, wrap ? 1 : 0, ti, Nst, h->dc.nx, X, obs,
-                           reach * reach, sel, sel_rec, rec_stride, clear, clear_stride, clear_slots);
-    else
-        hipLaunchKernelGGL(obstacles_kernel<MPC_NFSRC>, grid, dim3(TR_BLK), 0, s, B, G, K, Kp, spw, Lt, wrap ? 1 : 0, ti, Nst, h->dc.nx, X,
-                           obs, reach * reach, sel, sel_rec, rec_stride, clear, clear_stride, clear_slots);
+    with_flag(obstacle_discs(h), [&](auto DISCS) {
+        hipLaunchKernelGGL((obstacles_kernel<DISCS() ? 3 : MPC_NFSRC>), grid, dim3(TR_BLK), 0, s, B, G, K, Kp, spw, Lt, wrap ? 1 : 0, ti,
+                           Nst, h->dc.nx, X, obs, reach * reach, sel, sel_rec, rec_stride, clear, clear_stride, clear_slots);
+    });
 }
 
 extern "C" int mpc_obstacles_select(mpc_handle *h, int B, int G, int K, int Lt, int wrap, int ti, int Nst, const double *X,
@@ -1167,11 +1178,10 @@ static void launch_rows(mpc_handle *h, hipStream_t s, int B, int G, int K, int L
 {
     const size_t words = (size_t)B * h->cfg.N * MPC_NDISC;
     const dim3 grid((unsigned)((words + 255) / 256));
-    if (obstacle_discs(h))
-        hipLaunchKernelGGL(rows_from_obstacles_kernel<3>, grid, dim3(256), 0, s, B, h->cfg.N, G, K, Lt, wrap ? 1 : 0, ti, obs, sel, table);
-    else
-        hipLaunchKernelGGL(rows_from_obstacles_kernel<MPC_NFSRC>, grid, dim3(256), 0, s, B, h->cfg.N, G, K, Lt, wrap ? 1 : 0, ti, obs, sel,
-                           table);
+    with_flag(obstacle_discs(h), [&](auto DISCS) {
+        hipLaunchKernelGGL((rows_from_obstacles_kernel<DISCS() ? 3 : MPC_NFSRC>), grid, dim3(256), 0, s, B, h->cfg.N, G, K, Lt,
+                           wrap ? 1 : 0, ti, obs, sel, table);
+    });
 }
 // what the two public gathers check (`discs`: the disc form), asynchronous
 static int rows_from_obstacles(const std::string &who, bool discs, mpc_handle *h, int B, int G, int K, int Lt, int wrap, int ti,
@@ -1227,7 +1237,8 @@ extern "C" int mpc_roads_from_script(mpc_handle *h, int B, int Lt, int wrap, int
 // (mpc_rollout), the nearest obstacle tracks of every agent's scene on them at the script's time t0 + t + 1, their window
 // into the bound disc or field table, the solve, the plant step of mpc_closed_loop, and the clearance realised on the new
 // states.  Every step is what the public call of that name launches; control returns to the host inside the solve alone.
-// The traffic loops' body is not shared: they stay launch for launch what they are.
+// The step itself is plant_loop's, as in mpc_closed_loop and the traffic loops: this loop is its prologue and what it
+// launches before the solve and behind the plant step.
 extern "C" int mpc_closed_loop_obstacles(mpc_handle *h, int B, int T, int shift, int G, int K, int Lt, int wrap, int t0,
                                          const double *obs, double reach, double *x, const double *cl, int32_t *cl_index,
                                          double *U, double *lambda, double *table, double *traj_x, double *traj_u,
@@ -1241,45 +1252,31 @@ extern "C" int mpc_closed_loop_obstacles(mpc_handle *h, int B, int T, int shift,
     rc = check_common(h, B, who.c_str()); if (rc) return rc;
     rc = check_obstacle_window(who, t0, (long long)T + h->cfg.N, "t0"); if (rc) return rc;   // up to the last step's window
     if (trk) { rc = check_track(h, trk, who.c_str()); if (rc) return rc; }
-    const bool discs = obstacle_discs(h);
-    const TableKind kind = discs ? TAB_DISCS : TAB_FIELDS;
-    const BoundTable &dt = h->tab[kind];
     rc = check_tables(h, B, who.c_str(), READS_ALL, true); if (rc) return rc;
-    if (!table || table != dt.table)
-        return fail(MPC_E_ARG, who + ": table must be the " + k_tables[kind].noun + " table that is bound (" + k_tables[kind].setter +
-                               "): the loop rewrites it in place");
-    if (dt.rows != B)
-        return fail(MPC_E_ARG, who + ": the bound " + k_tables[kind].noun + " table has " + std::to_string(dt.rows) +
-                               " rows, the loop needs one per agent (P == B = " + std::to_string(B) + ", index 0 .. B-1)");
+    rc = check_rewritten_table(h, obstacle_discs(h) ? TAB_DISCS : TAB_FIELDS, table, B, who); if (rc) return rc;
     rc = check_rate_rows(h, B, who); if (rc) return rc;
     if (B == 0 || T == 0) return MPC_OK;
     if (!x || !cl || !U || (h->dc.m && !lambda) || (trk && !cl_index)) return fail(MPC_E_ARG, who + ": null buffer");
     rc = reserve_traffic(h, B); if (rc) return rc;
-    const DevCfg &c = h->dc;
+    const int N = h->dc.N;
     mpc_handle::TrafficBufs &tr = h->tr;
     hipStream_t s = (hipStream_t)stream;
-    double *st = stats;
-    if (!st) {
-        rc = reserve_stage(h, sizeof(double) * 8 * (size_t)B); if (rc) return rc;
-        st = h->stage;
-    }
-    for (int t = 0; t < T; t++) {
-        const int ti = t0 + t + 1;
-        if (trk) { rc = mpc_track_select(h, trk, B, x, cl, nullptr, cl_index, nullptr, stream); if (rc) return rc; }
-        rc = mpc_rollout(h, B, c.N, x, U, tr.X, stream); if (rc) return rc;
-        launch_obstacles(h, s, B, G, K, Lt, wrap, ti, c.N, tr.X, obs, reach, tr.opp, traj_sel ? traj_sel + (size_t)t * MPC_NDISC : nullptr,
+    const auto before = [&](int t) -> int {
+        const int ti = t0 + t + 1;   // the script's time of step t (and in `after`)
+        if (trk) { const int rs = mpc_track_select(h, trk, B, x, cl, nullptr, cl_index, nullptr, stream); if (rs) return rs; }
+        const int rr = mpc_rollout(h, B, N, x, U, tr.X, stream); if (rr) return rr;
+        launch_obstacles(h, s, B, G, K, Lt, wrap, ti, N, tr.X, obs, reach, tr.opp, traj_sel ? traj_sel + (size_t)t * MPC_NDISC : nullptr,
                          (size_t)T * MPC_NDISC, nullptr, 0, 0);
         launch_rows(h, s, B, G, K, Lt, wrap, ti, obs, tr.opp, table);
-        rc = mpc_solve_batch(h, B, x, cl, cl_index, U, lambda, st, stream); if (rc) return rc;
-        launch_rate_prev(h, s, B, U, nullptr, nullptr);
-        with_model_table(h, h->plant_rows(), [&](auto MODEL, auto PA, auto... pt) {
-            hipLaunchKernelGGL((plant_step_kernel<MODEL(), PA(), decltype(pt)...>), grid_for(B, 64), dim3(64), 0,
-                               s, c, B, t, T, shift, x, U, traj_x, traj_u, st, fail_count, pt...);
-        });
+        return MPC_OK;
+    };
+    const auto after = [&](int t) -> int {
         if (traj_clear)
-            launch_obstacles(h, s, B, G, K, Lt, wrap, ti, 1, x, obs, INFINITY, nullptr, nullptr, 0, traj_clear + t, (size_t)T, 1);
-    }
-    HIPCHK(hipGetLastError());
+            launch_obstacles(h, s, B, G, K, Lt, wrap, t0 + t + 1, 1, x, obs, INFINITY, nullptr, nullptr, 0, traj_clear + t, (size_t)T, 1);
+        return MPC_OK;
+    };
+    rc = plant_loop(h, B, T, shift, x, cl, cl_index, U, lambda, traj_x, traj_u, fail_count, stats, stream, before, after);
+    if (rc) return rc;
     return bounded_sync(h, s, who.c_str());
 }
 

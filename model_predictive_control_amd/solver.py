@@ -182,8 +182,7 @@ class BatchedMPC:
     def _bind_agent_table(self, kind, table, *indices):
         """set_agent_<kind>: the shape, dtype, device and range checks, the library's setter, and the tensors kept alive.
         indices: `index`, and `plant_index` (or None) for the kind that has one."""
-        d = _AGENT_TABLES[kind]
-        width = d.width + d.width_per_N * self.N
+        d, width = _AGENT_TABLES[kind], self._table_width(kind)
         self._free()
         if not isinstance(table, torch.Tensor) or table.dim() != 2 or table.shape[1] != width or table.shape[0] < 1:
             raise ValueError(f"table: expected a tensor [P >= 1, {width}]")
@@ -310,6 +309,96 @@ class BatchedMPC:
         if not torch.equal(index, torch.arange(B, dtype=torch.int32, device=index.device)):
             raise ValueError("the bound rate table's index is not arange(B): a closed loop writes the applied input into row b of agent b")
 
+    # ------------------------------------------------------------------ what the closed loops share
+    def _table_width(self, kind):
+        return _AGENT_TABLES[kind].width + _AGENT_TABLES[kind].width_per_N * self.N
+
+    def _multipliers(self, B, lam, inplace=False):
+        """lam [B, m] of a call that writes it: zeros when None, else the caller's (a copy unless inplace), checked; None on
+        an engine without constraints"""
+        if not self.m:
+            return None
+        lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None else (lam if inplace else lam.clone())
+        return self._chk(lam, (B, self.m), "lam")
+
+    def _loop_entry(self, x, U):
+        """B of a closed loop on x [B, nx] and U [B, 2N], a bound rate table being one a loop can write"""
+        B = x.shape[0]
+        self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
+        self._check_rate_rows(B)
+        return B
+
+    def _loop_state(self, B, T, x, U, lam, stats=True):
+        """(x, U, lam, traj_x, traj_u, failures, stats) of a closed loop: copies of what the caller passed and what the
+        library fills (stats=False: None in place of a fresh stats, for the loops that continue the caller's)"""
+        x, U = x.clone(), U.clone()
+        lam = self._multipliers(B, lam)
+        tx, tu = self._empty(B, T, self.nx), self._empty(B, T, 2)
+        fails = torch.zeros(B, dtype=torch.int32, device=self.device)
+        return x, U, lam, tx, tu, fails, self._empty(B, _lib.NSTATS) if stats else None
+
+    def _event_loop_state(self, B, T, x, U, lam, held, disturbance, stats):
+        """the fields of an EventLoopResult, in its order: _loop_state with the caller's held (None: -1, no plan yet) and
+        stats (None: zeros) copied, solved and solve_count; disturbance [B, T, nx] is checked"""
+        held = torch.full((B,), -1, dtype=torch.int32, device=self.device) if held is None else held.clone()
+        self._chk(held, (B,), "held", torch.int32)
+        x, U, lam, tx, tu, fails, _ = self._loop_state(B, T, x, U, lam, stats=False)
+        if disturbance is not None:
+            self._chk(disturbance, (B, T, self.nx), "disturbance")
+        stats = torch.zeros(B, _lib.NSTATS, dtype=torch.float64, device=self.device) if stats is None else stats.clone()
+        self._chk(stats, (B, _lib.NSTATS), "stats")
+        solved = torch.zeros(B, T, dtype=torch.uint8, device=self.device)
+        count = torch.zeros(B, dtype=torch.int32, device=self.device)
+        return x, U, lam, held, tx, tu, solved, count, fails, stats
+
+    def _loop_table(self, kind, B, table, identity_index=False):
+        """The table of `kind` ("discs" or "fields") that a loop rewrites in place: None -- zeros, bound with arange(B) and
+        left bound; else the caller's, checked.  identity_index: a bound table whose index is not arange(B) is refused --
+        closed_loop_obstacles alone asks for that; the traffic loops leave the index to the caller, as the library does
+        (an asymmetry kept as it was found)."""
+        if table is None:
+            table = torch.zeros(B, self._table_width(kind), dtype=torch.float64, device=self.device)
+            self._bind_agent_table(kind, table, torch.arange(B, dtype=torch.int32, device=self.device))
+            return table
+        self._chk(table, (B, self._table_width(kind)), "table")
+        if identity_index and kind in self._keep and self._keep[kind][0] is table and \
+                not torch.equal(self._keep[kind][1], torch.arange(B, dtype=torch.int32, device=self.device)):
+            raise ValueError(f"the bound {kind[:-1]} table's index is not arange(B): the loop writes row b for agent b")
+        return table
+
+    def _check_scene(self, B, G):
+        """scenes are blocks of G consecutive agents"""
+        if not 1 <= G <= _lib.SCENE_MAX:
+            raise ValueError(f"G: a scene holds 1 .. {_lib.SCENE_MAX} agents")
+        if B % G:
+            raise ValueError(f"the batch of {B} agents is not a whole number of scenes of {G} (pad the scenes)")
+
+    def _plans(self, X):
+        """(X, B, Nst) of a selection on plans X [B, Nst >= 1, nx]; [B, nx] is one stage, the states as they are now"""
+        self._free()
+        if isinstance(X, torch.Tensor) and X.dim() == 2:
+            X = X.unsqueeze(1)
+        if not isinstance(X, torch.Tensor) or X.dim() != 3 or X.shape[1] < 1:
+            raise ValueError(f"X: expected [B, Nst >= 1, {self.nx}]")
+        B, Nst = int(X.shape[0]), int(X.shape[1])
+        return self._chk(X, (B, Nst, self.nx), "X"), B, Nst
+
+    def _rows_from_plans(self, fn, kind, X, opp, per, per_name, out):
+        """discs_from_plans / fields_from_plans: X [B, N, nx], opp [B, NDISC] int32, `per` [B, ...] (agent b as an obstacle)
+        and the table of `kind`, `out` or a new one"""
+        self._free()
+        if not isinstance(X, torch.Tensor) or X.dim() != 3:
+            raise ValueError(f"X: expected [B, {self.N}, {self.nx}]")
+        B = X.shape[0]
+        self._chk(X, (B, self.N, self.nx), "X")
+        assert _lib.NDISC == _lib.NFIELD        # one opp [B, 2] serves the discs and the fields, as in the library
+        self._chk(opp, (B, _lib.NDISC), "opp", torch.int32)
+        self._chk(per, (B,) if kind == "discs" else (B, 4), per_name)
+        width = self._table_width(kind)
+        table = self._empty(B, width) if out is None else self._chk(out, (B, width), "out")
+        _lib.check(fn(self._h, B, _ptr(X), _ptr(opp), _ptr(per), _ptr(table), self._stream()))
+        return table
+
     def set_agent_fields(self, table, index):
         """Binds a per-agent table of risk fields (mpc_set_agent_fields; not on an engine of CONSTR_DISCS): table
         [P, NFIELD * NFSRC * N] float64 (rows [N][NFIELD][NFSRC], sources [cx, cy, c, s, A, kx, ky, alpha], as
@@ -385,17 +474,7 @@ class BatchedMPC:
         [A, kx, ky, gain] of agent b as an obstacle: the source sits at the opponent's planned position in the frame of
         its planned heading, skewed by gain * (own speed - its speed).  A gather on the current stream; `out`: a table to
         write in place (one that is bound, say), else a new one."""
-        self._free()
-        if not isinstance(X, torch.Tensor) or X.dim() != 3:
-            raise ValueError(f"X: expected [B, {self.N}, {self.nx}]")
-        B = X.shape[0]
-        self._chk(X, (B, self.N, self.nx), "X")
-        self._chk(opp, (B, _lib.NFIELD), "opp", torch.int32)
-        self._chk(shape, (B, 4), "shape")
-        width = _lib.field_row(self.N)
-        table = self._empty(B, width) if out is None else self._chk(out, (B, width), "out")
-        _lib.check(self.lib.mpc_fields_from_plans(self._h, B, _ptr(X), _ptr(opp), _ptr(shape), _ptr(table), self._stream()))
-        return table
+        return self._rows_from_plans(self.lib.mpc_fields_from_plans, "fields", X, opp, shape, "shape", out)
 
     def discs_from_plans(self, X, opp, radius, out=None):
         """mpc_discs_from_plans: the disc table [B, 3 * NDISC * N] in which agent b's discs are the plans of its
@@ -403,24 +482,11 @@ class BatchedMPC:
         opponents of agent b; < 0 or >= B: none, a disc of radius 0), radius [B] (of agent b as an obstacle).  A gather
         on the current stream; `out`: a table to write in place (one that is bound, say), else a new one.  Bound with
         index = arange(B) it makes the next solve "everyone avoids everyone's last plan"."""
-        self._free()
-        if not isinstance(X, torch.Tensor) or X.dim() != 3:
-            raise ValueError(f"X: expected [B, {self.N}, {self.nx}]")
-        B = X.shape[0]
-        self._chk(X, (B, self.N, self.nx), "X")
-        self._chk(opp, (B, _lib.NDISC), "opp", torch.int32)
-        self._chk(radius, (B,), "radius")
-        width = 3 * _lib.NDISC * self.N
-        table = self._empty(B, width) if out is None else self._chk(out, (B, width), "out")
-        _lib.check(self.lib.mpc_discs_from_plans(self._h, B, _ptr(X), _ptr(opp), _ptr(radius), _ptr(table), self._stream()))
-        return table
+        return self._rows_from_plans(self.lib.mpc_discs_from_plans, "discs", X, opp, radius, "radius", out)
 
     def _scene_args(self, B, G, radius, reach):
         G, reach = int(G), float(reach)
-        if not 1 <= G <= _lib.SCENE_MAX:
-            raise ValueError(f"G: a scene holds 1 .. {_lib.SCENE_MAX} agents")
-        if B % G:
-            raise ValueError(f"the batch of {B} agents is not a whole number of scenes of {G} (pad the scenes)")
+        self._check_scene(B, G)
         if not reach >= 0.0:
             raise ValueError("reach must be >= 0 (inf: every agent of the scene)")
         self._chk(radius, (B,), "radius")
@@ -432,13 +498,7 @@ class BatchedMPC:
         states as they are now): c(b, o) = min_k (dx dx + dy dy) - radius[o]^2, candidates c < reach^2 with every stage
         finite, the smallest in the order (c, o) first.  opp holds global agent indices, -1 for an unused slot (clear
         +inf): what discs_from_plans takes.  On the current stream."""
-        self._free()
-        if isinstance(X, torch.Tensor) and X.dim() == 2:
-            X = X.unsqueeze(1)
-        if not isinstance(X, torch.Tensor) or X.dim() != 3 or X.shape[1] < 1:
-            raise ValueError(f"X: expected [B, Nst >= 1, {self.nx}]")
-        B, Nst = int(X.shape[0]), int(X.shape[1])
-        self._chk(X, (B, Nst, self.nx), "X")
+        X, B, Nst = self._plans(X)
         G, reach = self._scene_args(B, G, radius, reach)
         opp = torch.full((B, _lib.NDISC), -1, dtype=torch.int32, device=self.device)
         clear = torch.full((B, _lib.NDISC), float("inf"), dtype=torch.float64, device=self.device)
@@ -564,12 +624,7 @@ class BatchedMPC:
         cl = self._centerline(centerline, cl_index, B)
         if not inplace:
             U = U.clone()
-        if self.m:
-            lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None \
-                else (lam if inplace else lam.clone())
-            self._chk(lam, (B, self.m), "lam")
-        else:
-            lam = None
+        lam = self._multipliers(B, lam, inplace)
         stats = self._empty(B, _lib.NSTATS)
         _lib.check(self.lib.mpc_solve_batch(self._h, B, _ptr(x0), _ptr(cl), _ptr(cl_index), _ptr(U),
                                             _ptr(lam), _ptr(stats), self._stream()))
@@ -584,11 +639,7 @@ class BatchedMPC:
         self._chk(x0, (B, self.nx), "x0"); self._chk(U, (B, self.n), "U")
         cl = self._centerline(centerline, cl_index, B)
         U = U.clone()
-        if self.m:
-            lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None else lam.clone()
-            self._chk(lam, (B, self.m), "lam")
-        else:
-            lam = None
+        lam = self._multipliers(B, lam)
         stats = self._empty(B, _lib.NSTATS)
         keep = (x0, cl, cl_index, U, lam, stats)      # the buffers stay alive until the wait
         _lib.check(self.lib.mpc_solve_batch_async(self._h, B, _ptr(x0), _ptr(cl), _ptr(cl_index), _ptr(U),
@@ -606,19 +657,9 @@ class BatchedMPC:
     def closed_loop(self, x, centerline, U, T, lam=None, cl_index=None, shift=False):
         """f-1 (main.py:121-146) for B agents: returns (x_T, U, lam, traj_x[B,T,nx], traj_u[B,T,2],
         failures[B], stats of the last solve)."""
-        B = x.shape[0]
-        self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
-        self._check_rate_rows(B)
+        B = self._loop_entry(x, U)
         cl = self._centerline(centerline, cl_index, B)
-        x, U = x.clone(), U.clone()
-        if self.m:
-            lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None \
-                else lam.clone()
-        else:
-            lam = None
-        tx, tu = self._empty(B, T, self.nx), self._empty(B, T, 2)
-        fails = torch.zeros(B, dtype=torch.int32, device=self.device)
-        stats = self._empty(B, _lib.NSTATS)
+        x, U, lam, tx, tu, fails, stats = self._loop_state(B, T, x, U, lam)
         _lib.check(self.lib.mpc_closed_loop(self._h, B, int(T), int(bool(shift)), _ptr(x), _ptr(cl),
                                             _ptr(cl_index), _ptr(U), _ptr(lam), _ptr(tx), _ptr(tu),
                                             _ptr(fails), _ptr(stats), self._stream()))
@@ -632,29 +673,17 @@ class BatchedMPC:
         obstacle.  table: the bound disc table [B, 3 NDISC N] (set_agent_discs with index = arange(B)), rewritten in
         place; None: a table of zeros is made, bound with arange(B) and left bound.  Returns a TrafficLoopResult (x, U
         and lam are copies; the table is the bound one)."""
-        B, T = x.shape[0], int(T)
-        self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
-        self._check_rate_rows(B)
+        B, T = self._loop_entry(x, U), int(T)
         if T < 0:
             raise ValueError("T must be >= 0")
         G, reach = self._scene_args(B, G, radius, reach)
         if int(self.cfg.constr_mode) != _lib.CONSTR_DISCS:     # before a table is made and bound for the caller
             raise _lib.MpcError("libmpc_hip error -1: mpc_closed_loop_traffic: the handle's constr_mode is not MPC_CONSTR_DISCS")
-        width = 3 * _lib.NDISC * self.N
-        if table is None:
-            table = torch.zeros(B, width, dtype=torch.float64, device=self.device)
-            self.set_agent_discs(table, torch.arange(B, dtype=torch.int32, device=self.device))
-        else:
-            self._chk(table, (B, width), "table")
+        table = self._loop_table("discs", B, table)
         cl = self._centerline(centerline, cl_index, B)
-        x, U = x.clone(), U.clone()
-        lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None else lam.clone()
-        self._chk(lam, (B, self.m), "lam")
-        tx, tu = self._empty(B, T, self.nx), self._empty(B, T, 2)
+        x, U, lam, tx, tu, fails, stats = self._loop_state(B, T, x, U, lam)    # (an engine of CONSTR_DISCS has m > 0)
         topp = torch.full((B, T, _lib.NDISC), -1, dtype=torch.int32, device=self.device)
         tclear = torch.full((B, T), float("inf"), dtype=torch.float64, device=self.device)
-        fails = torch.zeros(B, dtype=torch.int32, device=self.device)
-        stats = self._empty(B, _lib.NSTATS)
         _lib.check(self.lib.mpc_closed_loop_traffic(
             self._h, B, T, int(bool(shift)), G, _ptr(radius), reach, _ptr(x), _ptr(cl), _ptr(cl_index), _ptr(U), _ptr(lam),
             _ptr(table), _ptr(tx), _ptr(tu), _ptr(topp), _ptr(tclear), _ptr(fails), _ptr(stats), self._stream()))
@@ -670,9 +699,7 @@ class BatchedMPC:
         arange(B)), rewritten in place; None: a table of zeros is made, bound with arange(B) and left bound.  Returns a
         TrafficLoopResult (x, U and lam are copies, lam None where the engine has no constraints; the table is the bound
         one)."""
-        B, T = x.shape[0], int(T)
-        self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
-        self._check_rate_rows(B)
+        B, T = self._loop_entry(x, U), int(T)
         if T < 0:
             raise ValueError("T must be >= 0")
         G, reach = self._scene_args(B, G, radius, reach)
@@ -680,24 +707,11 @@ class BatchedMPC:
         if int(self.cfg.constr_mode) == _lib.CONSTR_DISCS:     # before a table is made and bound for the caller
             raise ValueError("closed_loop_traffic_field: the engine's constr_mode is CONSTR_DISCS, where an obstacle is a disc "
                              "(closed_loop_traffic)")
-        width = _lib.field_row(self.N)
-        if table is None:
-            table = torch.zeros(B, width, dtype=torch.float64, device=self.device)
-            self.set_agent_fields(table, torch.arange(B, dtype=torch.int32, device=self.device))
-        else:
-            self._chk(table, (B, width), "table")
+        table = self._loop_table("fields", B, table)
         cl = self._centerline(centerline, cl_index, B)
-        x, U = x.clone(), U.clone()
-        if self.m:
-            lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None else lam.clone()
-            self._chk(lam, (B, self.m), "lam")
-        else:
-            lam = None
-        tx, tu = self._empty(B, T, self.nx), self._empty(B, T, 2)
+        x, U, lam, tx, tu, fails, stats = self._loop_state(B, T, x, U, lam)
         topp = torch.full((B, T, _lib.NFIELD), -1, dtype=torch.int32, device=self.device)
         tclear = torch.full((B, T), float("inf"), dtype=torch.float64, device=self.device)
-        fails = torch.zeros(B, dtype=torch.int32, device=self.device)
-        stats = self._empty(B, _lib.NSTATS)
         _lib.check(self.lib.mpc_closed_loop_traffic_field(
             self._h, B, T, int(bool(shift)), G, _ptr(radius), _ptr(shape), reach, _ptr(x), _ptr(cl), _ptr(cl_index), _ptr(U),
             _ptr(lam), _ptr(table), _ptr(tx), _ptr(tu), _ptr(topp), _ptr(tclear), _ptr(fails), _ptr(stats), self._stream()))
@@ -730,12 +744,7 @@ class BatchedMPC:
         cl = self._centerline(centerline, cl_index, B)
         if not inplace:
             U = U.clone()
-        if self.m:
-            lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None \
-                else (lam if inplace else lam.clone())
-            self._chk(lam, (B, self.m), "lam")
-        else:
-            lam = None
+        lam = self._multipliers(B, lam, inplace)
         if stats is None:
             stats = torch.zeros(B, _lib.NSTATS, dtype=torch.float64, device=self.device)
         elif not inplace:
@@ -767,34 +776,17 @@ class BatchedMPC:
         applied.  held [B] int32 (None: -1, no plan yet) and the returned U / held / lam / stats continue a loop
         on this engine: pass them to the next call.  disturbance [B, T, nx] is added to the plant's state at every
         step.  Returns an EventLoopResult (copies; the arguments are not written)."""
-        B, T = x.shape[0], int(T)
-        self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
-        self._check_rate_rows(B)
+        B, T = self._loop_entry(x, U), int(T)
         thr, max_hold = self._trigger_args(thr, max_hold)
         if T < 0:
             raise ValueError("T must be >= 0")
         cl = self._centerline(centerline, cl_index, B)
-        x, U = x.clone(), U.clone()
-        held = torch.full((B,), -1, dtype=torch.int32, device=self.device) if held is None else held.clone()
-        self._chk(held, (B,), "held", torch.int32)
-        if self.m:
-            lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None else lam.clone()
-            self._chk(lam, (B, self.m), "lam")
-        else:
-            lam = None
-        if disturbance is not None:
-            self._chk(disturbance, (B, T, self.nx), "disturbance")
-        stats = torch.zeros(B, _lib.NSTATS, dtype=torch.float64, device=self.device) if stats is None else stats.clone()
-        self._chk(stats, (B, _lib.NSTATS), "stats")
-        tx, tu = self._empty(B, T, self.nx), self._empty(B, T, 2)
-        solved = torch.zeros(B, T, dtype=torch.uint8, device=self.device)
-        count = torch.zeros(B, dtype=torch.int32, device=self.device)
-        fails = torch.zeros(B, dtype=torch.int32, device=self.device)
+        res = EventLoopResult(*self._event_loop_state(B, T, x, U, lam, held, disturbance, stats))
         _lib.check(self.lib.mpc_closed_loop_event(
-            self._h, B, T, int(bool(shift)), self._weights(w), thr, max_hold, _ptr(x), _ptr(cl), _ptr(cl_index), _ptr(U),
-            _ptr(lam), _ptr(held), _ptr(disturbance), _ptr(tx), _ptr(tu), _ptr(solved), _ptr(count), _ptr(fails),
-            _ptr(stats), self._stream()))
-        return EventLoopResult(x, U, lam, held, tx, tu, solved, count, fails, stats)
+            self._h, B, T, int(bool(shift)), self._weights(w), thr, max_hold, _ptr(res.x), _ptr(cl), _ptr(cl_index), _ptr(res.U),
+            _ptr(res.lam), _ptr(res.held), _ptr(disturbance), _ptr(res.traj_x), _ptr(res.traj_u), _ptr(res.solved),
+            _ptr(res.solve_count), _ptr(res.failures), _ptr(res.stats), self._stream()))
+        return res
 
     # ------------------------------------------------------------------ lap driving: windows of a track
     def track_windows(self, track, stride, lead, closed):
@@ -868,46 +860,26 @@ class BatchedMPC:
         result, with its U / held / lam / stats, to continue).  Returns a TrackLoopResult (copies; the arguments are
         not written)."""
         trk = self._track(track_obj)
-        B, T = x.shape[0], int(T)
-        self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
-        self._check_rate_rows(B)
+        B, T = self._loop_entry(x, U), int(T)
         thr, max_hold = self._trigger_args(thr, max_hold)
         if T < 0:
             raise ValueError("T must be >= 0")
         if cl_index is None:
             raise ValueError("cl_index: the rows to start from are required (track_locate)")
         win = self._centerline(trk.win, cl_index, B)
-        x, U, ci = x.clone(), U.clone(), cl_index.clone()
-        held = torch.full((B,), -1, dtype=torch.int32, device=self.device) if held is None else held.clone()
-        self._chk(held, (B,), "held", torch.int32)
-        if self.m:
-            lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None else lam.clone()
-            self._chk(lam, (B, self.m), "lam")
-        else:
-            lam = None
-        if disturbance is not None:
-            self._chk(disturbance, (B, T, self.nx), "disturbance")
-        stats = torch.zeros(B, _lib.NSTATS, dtype=torch.float64, device=self.device) if stats is None else stats.clone()
-        self._chk(stats, (B, _lib.NSTATS), "stats")
-        tx, tu = self._empty(B, T, self.nx), self._empty(B, T, 2)
-        solved = torch.zeros(B, T, dtype=torch.uint8, device=self.device)
-        count = torch.zeros(B, dtype=torch.int32, device=self.device)
-        fails = torch.zeros(B, dtype=torch.int32, device=self.device)
-        rows = torch.zeros(B, T, dtype=torch.int32, device=self.device)
+        res = TrackLoopResult(*self._event_loop_state(B, T, x, U, lam, held, disturbance, stats), cl_index.clone(),
+                              torch.zeros(B, T, dtype=torch.int32, device=self.device))
         _lib.check(self.lib.mpc_closed_loop_track(
-            self._h, B, T, int(bool(shift)), self._weights(w), thr, max_hold, _ptr(x), _ptr(win), _ptr(ci), _ptr(U),
-            _ptr(lam), _ptr(held), _ptr(disturbance), _ptr(tx), _ptr(tu), _ptr(solved), _ptr(count), _ptr(fails),
-            _ptr(stats), self._stream(), C.byref(trk._c), _ptr(rows)))
-        return TrackLoopResult(x, U, lam, held, tx, tu, solved, count, fails, stats, ci, rows)
+            self._h, B, T, int(bool(shift)), self._weights(w), thr, max_hold, _ptr(res.x), _ptr(win), _ptr(res.cl_index), _ptr(res.U),
+            _ptr(res.lam), _ptr(res.held), _ptr(disturbance), _ptr(res.traj_x), _ptr(res.traj_u), _ptr(res.solved),
+            _ptr(res.solve_count), _ptr(res.failures), _ptr(res.stats), self._stream(), C.byref(trk._c), _ptr(res.traj_row)))
+        return res
 
     # ------------------------------------------------------------------ scripted obstacles
     def _obstacle_args(self, B, G, obs, wrap, ti, Nst, reach=0.0):
         """(G, K, Lt, wrap, ti, reach) of a call on the obstacle tracks obs [B / G, K, Lt, W]"""
         G, ti, reach = int(G), int(ti), float(reach)
-        if not 1 <= G <= _lib.SCENE_MAX:
-            raise ValueError(f"G: a scene holds 1 .. {_lib.SCENE_MAX} agents")
-        if B % G:
-            raise ValueError(f"the batch of {B} agents is not a whole number of scenes of {G} (pad the scenes)")
+        self._check_scene(B, G)
         W = _lib.obstacle_width(self.cfg)
         if not isinstance(obs, torch.Tensor) or obs.dim() != 4 or obs.shape[3] != W:
             raise ValueError(f"obs: expected a tensor [B / G, K, Lt, {W}]")
@@ -928,13 +900,7 @@ class BatchedMPC:
         c(b, o) = min over the present samples of (dx dx + dy dy) - r^2 (fields: r = 0), candidates c < reach^2 with every
         stage finite, the smallest in the order (c, o) first.  sel holds indices within the scene, -1 for an unused slot
         (clear +inf): what discs_from_obstacles / fields_from_obstacles take.  On the current stream."""
-        self._free()
-        if isinstance(X, torch.Tensor) and X.dim() == 2:
-            X = X.unsqueeze(1)
-        if not isinstance(X, torch.Tensor) or X.dim() != 3 or X.shape[1] < 1:
-            raise ValueError(f"X: expected [B, Nst >= 1, {self.nx}]")
-        B, Nst = int(X.shape[0]), int(X.shape[1])
-        self._chk(X, (B, Nst, self.nx), "X")
+        X, B, Nst = self._plans(X)
         G, K, Lt, wrap, ti, reach = self._obstacle_args(B, G, obs, wrap, ti, Nst, reach)
         sel = torch.full((B, _lib.NDISC), -1, dtype=torch.int32, device=self.device)
         clear = torch.full((B, _lib.NDISC), float("inf"), dtype=torch.float64, device=self.device)
@@ -982,23 +948,12 @@ class BatchedMPC:
         track_locate) from its state before every step.  t0: the script's time at the call (a second call with t0 + T,
         and x, U, lam, cl_index of the first's result, continues it).  Returns an ObstacleLoopResult (copies; the table is
         the bound one)."""
-        B, T, t0 = x.shape[0], int(T), int(t0)
-        self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
-        self._check_rate_rows(B)
+        B, T, t0 = self._loop_entry(x, U), int(T), int(t0)
         if T < 0:
             raise ValueError("T must be >= 0")
         G, K, Lt, wrap, t0, reach = self._obstacle_args(B, G, obs, wrap, t0, T + self.N, reach)
-        discs = int(self.cfg.constr_mode) == _lib.CONSTR_DISCS
-        kind, width = ("discs", 3 * _lib.NDISC * self.N) if discs else ("fields", _lib.field_row(self.N))
-        if table is None:
-            table = torch.zeros(B, width, dtype=torch.float64, device=self.device)
-            arange = torch.arange(B, dtype=torch.int32, device=self.device)
-            self.set_agent_discs(table, arange) if discs else self.set_agent_fields(table, arange)
-        else:
-            self._chk(table, (B, width), "table")
-            if kind in self._keep and self._keep[kind][0] is table and \
-                    not torch.equal(self._keep[kind][1], torch.arange(B, dtype=torch.int32, device=self.device)):
-                raise ValueError(f"the bound {kind[:-1]} table's index is not arange(B): the loop writes row b for agent b")
+        kind = "discs" if int(self.cfg.constr_mode) == _lib.CONSTR_DISCS else "fields"
+        table = self._loop_table(kind, B, table, identity_index=True)
         trk = None
         if track_obj is not None:
             trk = self._track(track_obj)
@@ -1008,18 +963,10 @@ class BatchedMPC:
                 raise ValueError("cl_index: the rows to start from are required with track_obj (track_locate)")
             centerline = trk.win
         cl = self._centerline(centerline, cl_index, B)
-        x, U = x.clone(), U.clone()
+        x, U, lam, tx, tu, fails, stats = self._loop_state(B, T, x, U, lam)
         ci = None if cl_index is None else cl_index.clone()
-        if self.m:
-            lam = torch.zeros(B, self.m, dtype=torch.float64, device=self.device) if lam is None else lam.clone()
-            self._chk(lam, (B, self.m), "lam")
-        else:
-            lam = None
-        tx, tu = self._empty(B, T, self.nx), self._empty(B, T, 2)
         tsel = torch.full((B, T, _lib.NDISC), -1, dtype=torch.int32, device=self.device)
         tclear = torch.full((B, T), float("inf"), dtype=torch.float64, device=self.device)
-        fails = torch.zeros(B, dtype=torch.int32, device=self.device)
-        stats = self._empty(B, _lib.NSTATS)
         _lib.check(self.lib.mpc_closed_loop_obstacles(
             self._h, B, T, int(bool(shift)), G, K, Lt, wrap, t0, _ptr(obs), reach, _ptr(x), _ptr(cl), _ptr(ci), _ptr(U), _ptr(lam),
             _ptr(table), _ptr(tx), _ptr(tu), _ptr(tsel), _ptr(tclear), _ptr(fails), _ptr(stats), self._stream(),

@@ -326,6 +326,9 @@ def test_refusals(dev):
             eng.opponents_from_plans(x0, **{**dict(G=G, radius=rt), **kw})
     with pytest.raises(ValueError):
         eng.closed_loop_traffic(x0, cl, U0, -1, G, rt, table=table)
+    for run in (lambda **kw: eng.closed_loop(x0, cl, U0, 1, **kw), lambda **kw: eng.closed_loop_traffic(x0, cl, U0, 1, G, rt, table=table, **kw)):
+        with pytest.raises(ValueError, match="lam"):
+            run(lam=lam[:, :-1].contiguous())                              # a lam of the wrong width: every loop, the plain one too
     # while solve_async is in flight
     wait = eng.solve_async(x0, cl, U0)
     refused(loop(eng), "mpc_closed_loop_traffic", "a solve of this handle is in flight")
