@@ -588,16 +588,12 @@ __device__ __forceinline__ void stage_geom(const DevCfg &c, const Workspace &w, 
 // two-kernel path (records in the slot-indexed scratch), the fused kernel and the persistent solo kernel
 // (records in LDS).  The cost arithmetic is written with fixed roundings (no contraction, explicit
 // fma): the same request must give the same bits whichever kernel this is inlined into.
-// DS: empty, or the stage's keep-out discs (one trailing StageDiscs: the disc forms of the kernels, constr_mode 3) -- the
-// constraints of the stage are then the NDISC discs and nothing else; the ALM terms are formed exactly as below --
-// and / or the stage's move penalty (one trailing StageRate, last: the rate forms): rate_term is added to the stage cost
-// and to its direct input gradient right behind stage_cost, before the ALM terms, so psi stays the stage-order sum --
-// and, behind the StageRate, the stage's risk field (one trailing StageField, last: the field forms): field_term adds the
-// sources to the stage cost and to its state gradient xb[0], xb[1] behind rate_term and before the ALM terms; the adjoint
-// recursion carries that like any other stage gradient --
-// and, last of all, the stage's road data (one trailing StageRoad: the road forms, <rate, field, road> and <discs, rate,
-// road>): road_term adds the lane target, the road edges and the speed target to the stage cost and to its state gradient
-// behind field_term (on a disc handle: behind rate_term) and before the ALM terms.
+// DS: what stage_data made of the kernel's table pack (the forms: table_form_ok, mpc_solver.hpp), in any order --
+// StageDiscs: the constraints of the stage are the NDISC discs and nothing else; the ALM terms are formed exactly as below.
+// StageRate: rate_term is added to the stage cost and to its direct input gradient right behind stage_cost, before the ALM
+// terms, so psi stays the stage-order sum.  StageField: field_term adds the sources to the stage cost and to its state
+// gradient xb[0], xb[1] behind rate_term; the adjoint recursion carries that like any other stage gradient.  StageRoad:
+// road_term adds the lane target, the road edges and the speed target behind field_term.
 template <int MODEL, class Put, class... DS>
 __device__ __forceinline__ void stage_record(const DevCfg &c, const Workspace &w, int a, bool ch2, bool is_g,
                                              int k, const double (&xs)[ModelDim<MODEL>::NX],
@@ -607,10 +603,7 @@ __device__ __forceinline__ void stage_record(const DevCfg &c, const Workspace &w
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE;
     constexpr bool DD = has_tab<StageDiscs, DS...>, RR = has_tab<StageRate, DS...>, FF = has_tab<StageField, DS...>;
     constexpr bool WW = has_tab<StageRoad, DS...>;
-    static_assert(sizeof...(DS) == (DD ? 1 : 0) + (RR ? 1 : 0) + (FF ? 1 : 0) + (WW ? 1 : 0),
-                  "at most the stage's discs, its move penalty, its risk field and its road data");
-    static_assert(!FF || (RR && !DD), "the field forms stand behind the rate forms alone, never beside the discs");
-    static_assert(!WW || (RR && FF != DD), "the road forms are <rate, field, road> and <discs, rate, road> alone");
+    static_assert(table_form_ok<DS...>(), MPC_TABLE_FORMS);
     double xb[NX], ub[2] = {0.0, 0.0};
 #pragma unroll
     for (int i = 0; i < NX; i++) xb[i] = 0.0;
@@ -821,31 +814,19 @@ __device__ __forceinline__ void adjoint_rec_quad_kin(const DevCfg &c, bool is_g,
 // (tried: the gradient blocks and the cost blocks by kernels of their own -- the cost-only variant needs 55
 // registers and runs eight waves per SIMD, 13 us per launch against 75 us for the gradient blocks -- but
 // the pair of launches is slower than the one: 180.2 vs 175.6 ms per solve)
-// CT (here, in the fused kernel and in the wave evaluation): empty, or the constraint table (one trailing ConTab
-// argument: mpc_set_agent_constraints) -- the agent's private DevCfg takes g_off, D_lb, D_ub and the lane halfwidth of
-// the agent's own row next to its parameter row.  The constraint form exists together with PA alone: without a
-// parameter table of the caller's the host binds a one-row table of the handle's own values (mpc_launch.hpp).
-// ... or the disc table (one trailing DiscTab argument: mpc_set_agent_discs, constr_mode 3), on the same terms: the
-// thread loads the six doubles of its own (agent, stage) and stage_record evaluates the discs in the constraints' place.
-// ... or the rate table (a trailing RateTab, alone or behind the DiscTab: mpc_set_agent_rates), on the same terms: the
-// thread loads the weights of its agent's row and its stage's two neighbours -- u_{k-1} and u_{k+1} from useq at its own
-// slot (u_{-1} from the row at stage 0, nothing past stage N - 1) -- and stage_record adds the move penalty.
-// ... or the rate table and the field table behind it (RateTab, FieldTab: mpc_set_agent_fields): the thread also hands
-// stage_record the address of its (agent, stage)'s sources, which field_term loads one at a time.
-// ... or the road table last of all (RateTab, FieldTab, RoadTab or DiscTab, RateTab, RoadTab: mpc_set_agent_roads): the
-// thread hands stage_record the address of its (agent, stage)'s eight doubles as well, which road_term loads.
+// CT (here, in the fused kernel and in the wave evaluation): one of the table forms (table_form_ok, mpc_solver.hpp).  A
+// form exists together with PA alone: without a parameter table of the caller's the host binds a one-row table of the
+// handle's own values (mpc_launch.hpp).  The constraint table goes into the agent's private DevCfg (g_off, D_lb, D_ub and
+// the lane halfwidth of the agent's own row, next to its parameter row); every other table reaches stage_record as the
+// data of the thread's own (agent, stage) (stage_data) -- the rate table's u_{k-1} and u_{k+1} come from useq at the
+// thread's own slot (u_{-1} from the row at stage 0, nothing past stage N - 1).
 template <int MODEL, bool SHARED_CL, bool PA = false, class... CT>
 __global__ void __launch_bounds__(64, (MODEL == KIN ? MPC_K1B_WAVES : MPC_K1B_WAVES_PAC))
 stage_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, int nG_imm, int nC_imm,
              int nblk_max, CT... ct)
 {
     static_assert(sizeof...(CT) == 0 || PA, "the constraint form exists in the per-agent-parameter form alone");
-    constexpr bool DA = has_tab<DiscTab, CT...>;   // the disc form: CT = DiscTab
-    constexpr bool RA = has_tab<RateTab, CT...>;   // the rate form: CT = RateTab or DiscTab, RateTab
-    constexpr bool FA = has_tab<FieldTab, CT...>;  // the field form: CT = RateTab, FieldTab
-    static_assert(!FA || (RA && !DA), "the field forms are <..., RateTab, FieldTab> alone");
-    constexpr bool WA = has_tab<RoadTab, CT...>;   // the road forms: CT = RateTab, FieldTab, RoadTab or DiscTab, RateTab, RoadTab
-    static_assert(!WA || (RA && FA != DA), "the road forms are <..., RateTab, FieldTab, RoadTab> and <..., DiscTab, RateTab, RoadTab> alone");
+    static_assert(table_form_ok<CT...>(), MPC_TABLE_FORMS);
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE;
 #if MPC_DEV_STAMP == 6
     DevStamp stamp(blockIdx.x);
@@ -892,23 +873,9 @@ stage_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ counts, 
     } else {
         stage_geom(c, w, clp, SHARED_CL ? 0 : w.cl_index[a], xe[0], xe[1], g);
     }
-    if constexpr (WA && FA)
-        stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_rate(pack_get<RateTab>(ct...), a, k, c.N, w.useq + uslot, St),
-                            stage_field(pack_get<FieldTab>(ct...), a, k, c.N), stage_road(pack_get<RoadTab>(ct...), a, k, c.N));
-    else if constexpr (WA)
-        stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(pack_get<DiscTab>(ct...), a, k, c.N),
-                            stage_rate(pack_get<RateTab>(ct...), a, k, c.N, w.useq + uslot, St), stage_road(pack_get<RoadTab>(ct...), a, k, c.N));
-    else if constexpr (FA)
-        stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_rate(pack_get<RateTab>(ct...), a, k, c.N, w.useq + uslot, St),
-                            stage_field(pack_get<FieldTab>(ct...), a, k, c.N));
-    else if constexpr (DA && RA)
-        stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(pack_get<DiscTab>(ct...), a, k, c.N),
-                            stage_rate(pack_get<RateTab>(ct...), a, k, c.N, w.useq + uslot, St));
-    else if constexpr (RA)
-        stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_rate(pack_get<RateTab>(ct...), a, k, c.N, w.useq + uslot, St));
-    else if constexpr (DA) stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(ct..., a, k, c.N));
+    if constexpr (has_tab<ConTab, CT...>) stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put);   // (it is in cm)
     else
-    stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put);
+    stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_data(ct, a, k, c.N, w.useq + uslot, St)...);
 }
 
 // (tried: four lanes per gradient request -- lane `role` of a DPP quad owning lambda[role] and one row of the
@@ -955,12 +922,7 @@ stage_adjoint_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ 
                      int *__restrict__ desc, CT... ct)
 {
     static_assert(sizeof...(CT) == 0 || PA, "the constraint form exists in the per-agent-parameter form alone");
-    constexpr bool DA = has_tab<DiscTab, CT...>;   // the disc form: CT = DiscTab
-    constexpr bool RA = has_tab<RateTab, CT...>;   // the rate form: CT = RateTab or DiscTab, RateTab
-    constexpr bool FA = has_tab<FieldTab, CT...>;  // the field form: CT = RateTab, FieldTab
-    static_assert(!FA || (RA && !DA), "the field forms are <..., RateTab, FieldTab> alone");
-    constexpr bool WA = has_tab<RoadTab, CT...>;   // the road forms: CT = RateTab, FieldTab, RoadTab or DiscTab, RateTab, RoadTab
-    static_assert(!WA || (RA && FA != DA), "the road forms are <..., RateTab, FieldTab, RoadTab> and <..., DiscTab, RateTab, RoadTab> alone");
+    static_assert(table_form_ok<CT...>(), MPC_TABLE_FORMS);
     static_assert(MODEL == KIN, "the fused K1b + K1c kernel is the kinematic model's");
     constexpr int NX = ModelDim<MODEL>::NX, JS = JacRec<MODEL>::SIZE, BLK = FUSED_BLK;
     extern __shared__ double s_rec[];                    // [JS + 1][N][SPB]; row JS = stage cost
@@ -999,23 +961,9 @@ stage_adjoint_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ 
             if (is_g) stage_sens_record<MODEL>(cm, xs, xe, d, dl, put);
             Geom g;
             stage_geom(c, w, clp, SHARED_CL ? 0 : w.cl_index[a], xe[0], xe[1], g);
-            if constexpr (WA && FA)
-                stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_rate(pack_get<RateTab>(ct...), a, k, N, w.useq + uslot, St),
-                                    stage_field(pack_get<FieldTab>(ct...), a, k, N), stage_road(pack_get<RoadTab>(ct...), a, k, N));
-            else if constexpr (WA)
-                stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(pack_get<DiscTab>(ct...), a, k, N),
-                                    stage_rate(pack_get<RateTab>(ct...), a, k, N, w.useq + uslot, St), stage_road(pack_get<RoadTab>(ct...), a, k, N));
-            else if constexpr (FA)
-                stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_rate(pack_get<RateTab>(ct...), a, k, N, w.useq + uslot, St),
-                                    stage_field(pack_get<FieldTab>(ct...), a, k, N));
-            else if constexpr (DA && RA)
-                stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(pack_get<DiscTab>(ct...), a, k, N),
-                                    stage_rate(pack_get<RateTab>(ct...), a, k, N, w.useq + uslot, St));
-            else if constexpr (RA)
-                stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_rate(pack_get<RateTab>(ct...), a, k, N, w.useq + uslot, St));
-            else if constexpr (DA) stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_discs(ct..., a, k, N));
+            if constexpr (has_tab<ConTab, CT...>) stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put);   // (it is in cm)
             else
-            stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put);
+            stage_record<MODEL>(cm, w, a, ch2, is_g, k, xs, xe, d, dl, g, put, stage_data(ct, a, k, N, w.useq + uslot, St)...);
         }
     }
     __syncthreads();

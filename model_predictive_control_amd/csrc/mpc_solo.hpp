@@ -84,16 +84,16 @@ template <int MODEL> __host__ __device__ inline size_t solo_lds_doubles(int nfe,
 #if MPC_DEV_STAMP == 5
 struct SoloClk { long long roll = 0, recs = 0, adj = 0; };
 #define SOLO_CLK_ARG , SoloClk &clk
+#define SOLO_CLK_PASS , clk
 #define SOLO_CLK(field, t) do { const long long now_ = __builtin_amdgcn_s_memrealtime(); clk.field += now_ - t; t = now_; } while (0)
 #else
 #define SOLO_CLK_ARG
+#define SOLO_CLK_PASS
 #define SOLO_CLK(field, t) do { } while (0)
 #endif
-// DS: empty, or the disc table (the disc forms: one trailing DiscTab) -- lane k loads the discs of its stage from the
-// agent's row, whose address is wave-uniform -- and / or the rate table (the rate forms: a trailing RateTab, last) -- lane k
-// takes u_{k-1} and u_{k+1} from the row it evaluates (`row`: xe, or xe2 on the speculative half), u_{-1} from the table
-// -- and, behind the RateTab, the field table (the field forms) -- lane k hands on the address of its stage's sources
-// -- and, last, the road table (the road forms: RateTab, FieldTab, RoadTab or DiscTab, RateTab, RoadTab) -- likewise
+// DS: the tables that hold stage data (the forms: table_form_ok, mpc_solver.hpp) -- lane k hands stage_record the data
+// of its stage from the agent's rows, whose addresses are wave-uniform (stage_data); the rate table's u_{k-1} and u_{k+1}
+// are the evaluated row's (`row`: xe, or xe2 on the speculative half)
 // alt: where the second half's trajectory and record block lie (solo_halves); nullptr: behind the first half's (solo_dual)
 template <int MODEL, class... DS>
 __device__ __forceinline__ void solo_eval(const DevCfg &c, const Workspace &w, int a, int lane, int req,
@@ -170,24 +170,7 @@ __device__ __forceinline__ void solo_eval(const DevCfg &c, const Workspace &w, i
         if (is_g) stage_sens_record<MODEL>(c, xs, xe, d, dl, put);
         Geom g;
         stage_geom(c, w, clp, w.cl_index ? w.cl_index[a] : 0, xe[0], xe[1], g);
-        constexpr bool DA = has_tab<DiscTab, DS...>, RA = has_tab<RateTab, DS...>, FA = has_tab<FieldTab, DS...>, WA = has_tab<RoadTab, DS...>;
-        if constexpr (WA && FA)
-            stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_rate_uniform(pack_get<RateTab>(ds...), a, hl, N, row),
-                                stage_field_uniform(pack_get<FieldTab>(ds...), a, hl, N), stage_road_uniform(pack_get<RoadTab>(ds...), a, hl, N));
-        else if constexpr (WA)
-            stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_discs_uniform(pack_get<DiscTab>(ds...), a, hl, N),
-                                stage_rate_uniform(pack_get<RateTab>(ds...), a, hl, N, row), stage_road_uniform(pack_get<RoadTab>(ds...), a, hl, N));
-        else if constexpr (FA)
-            stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_rate_uniform(pack_get<RateTab>(ds...), a, hl, N, row),
-                                stage_field_uniform(pack_get<FieldTab>(ds...), a, hl, N));
-        else if constexpr (DA && RA)
-            stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_discs_uniform(pack_get<DiscTab>(ds...), a, hl, N),
-                                stage_rate_uniform(pack_get<RateTab>(ds...), a, hl, N, row));
-        else if constexpr (RA)
-            stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_rate_uniform(pack_get<RateTab>(ds...), a, hl, N, row));
-        else if constexpr (DA) stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_discs_uniform(ds..., a, hl, N));
-        else
-        stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put);
+        stage_record<MODEL>(c, w, a, ch2, is_g, hl, xs, xe, d, dl, g, put, stage_data(ds, a, hl, N, row)...);
     }
     __builtin_amdgcn_wave_barrier();
     SOLO_CLK(recs, tclk);
@@ -296,8 +279,7 @@ __global__ void __launch_bounds__(64, 1) solo_eval_kernel(const DevCfg c_, const
     // constraint row, the same way)
     DevCfg cm_;
     if constexpr (PA) { cm_ = c_; agent_cfg_uniform(cm_, w.ptab, w.pidx, blockIdx.x); }
-    // the disc, rate and field forms (CT = DiscTab, RateTab, both, or RateTab + FieldTab): the tables go on to the evaluation
-    constexpr bool DA = has_tab<DiscTab, CT...> || has_tab<RateTab, CT...>;
+    static_assert(table_form_ok<CT...>(), MPC_TABLE_FORMS);
     if constexpr (has_tab<ConTab, CT...>) agent_con_uniform(cm_, ct..., blockIdx.x);
     const DevCfg &c = PA ? cm_ : c_;
     double *traj = s_solo;
@@ -307,14 +289,10 @@ __global__ void __launch_bounds__(64, 1) solo_eval_kernel(const DevCfg c_, const
     const int ereq = ((want_grad & 1) ? REQ_GRAD : REQ_COST) | ((want_grad & 2) ? REQ_SPEC : 0);
 #if MPC_DEV_STAMP == 5
     SoloClk clk;
-    if constexpr (DA) solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, ereq, traj, rec, alt, clk, ct...);
-    else
-    solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, ereq, traj, rec, alt, clk);
-#else
-    if constexpr (DA) solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, ereq, traj, rec, alt, ct...);
-    else
-    solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, ereq, traj, rec, alt);
 #endif
+    if constexpr (has_tab<ConTab, CT...>) solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, ereq, traj, rec, alt SOLO_CLK_PASS);   // (it is in c)
+    else
+    solo_eval<MODEL>(c, w, blockIdx.x, threadIdx.x, ereq, traj, rec, alt SOLO_CLK_PASS, ct...);
 }
 
 // One agent's solve with the lookahead (Pacejka, NE = 1): the loop of solo_kernel with a cache lookup before every
@@ -468,33 +446,21 @@ template <int MODEL> struct SoloOcc { static constexpr int WPS = MODEL == KIN ? 
 // same place, its row by scalar loads and this lane's two values of it chosen once per agent (lane_box_uniform); the state
 // machine and the lookahead's candidate points project onto it.  The box form exists together with PA alone: without a
 // parameter table of the caller's the host binds a one-row table of the handle's own values (mpc_launch.hpp).
-// BT = (BoxTab, ConTab): the constraint form (mpc_set_agent_constraints) -- the evaluations' DevCfg takes the agent's
-// constraint row with its parameter row, and the state machine projects the multipliers with the row's bounds (RowCon).
-// It exists together with the box form alone (the host supplies a one-row box table of the handle's own values when the
-// caller bound none), and never with the lookahead, which is an unconstrained problem's.
-// BT = (BoxTab, DiscTab): the disc form (mpc_set_agent_discs), on the same terms -- the evaluations read the discs of the
-// agent's row; the state machine projects the multipliers with the handle's bounds [0, +inf), the same for every agent.
-// BT = (BoxTab, RateTab) or (BoxTab, DiscTab, RateTab): the rate forms (mpc_set_agent_rates), on the disc form's terms --
-// the evaluations add the move penalty of the agent's row; the state machine is what it is without them.  Never with the
-// lookahead (results do not depend on it).
-// BT = (BoxTab, RateTab, FieldTab): the field form (mpc_set_agent_fields), on the rate form's terms -- the evaluations add
-// the risk field of the agent's row, stage by stage.
-// BT = (BoxTab, RateTab, FieldTab, RoadTab) or (BoxTab, DiscTab, RateTab, RoadTab): the road forms (mpc_set_agent_roads),
-// on the same terms -- the evaluations add the lane target, road edges and speed target of the agent's row, stage by stage.
+// BT = (BoxTab, one of the table forms: table_form_ok, mpc_solver.hpp) -- a form exists together with the box form alone
+// (the host supplies a one-row box table of the handle's own values when the caller bound none) and never with the
+// lookahead, which is an unconstrained problem's and changes no result.  The constraint form: the evaluations' DevCfg
+// takes the agent's constraint row with its parameter row, and the state machine projects the multipliers with the row's
+// bounds (RowCon).  Every other table goes on to the evaluations (solo_eval) and leaves the state machine what it is; on a
+// disc handle it projects the multipliers with the handle's bounds [0, +inf), the same for every agent.
 template <int MODEL, int NE, int MC, bool LA = false, bool PA = false, class... BT>
 __global__ void __launch_bounds__(64 * SOLO_WAVES, SoloOcc<MODEL>::WPS)
 solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int *__restrict__ ctr,
             long long max_trips, BT... bt)
 {
-    constexpr bool BA = sizeof...(BT) != 0, DA = has_tab<DiscTab, BT...>, CA = has_tab<ConTab, BT...>, RA = has_tab<RateTab, BT...>;
+    constexpr bool BA = has_tab<BoxTab, BT...>, CA = has_tab<ConTab, BT...>;
     static_assert(!BA || PA, "the box form of the persistent kernel exists in the per-agent-parameter form alone");
-    static_assert((!CA && !DA) || !LA, "the lookahead is an unconstrained problem's: it has no constraint or disc form");
-    static_assert(!RA || !LA, "the rate forms run without the lookahead");
-    constexpr bool FA = has_tab<FieldTab, BT...>;
-    constexpr bool WA = has_tab<RoadTab, BT...>;
-    static_assert(!FA || (RA && !DA && !CA && sizeof...(BT) == (WA ? 4 : 3)), "the field forms are <..., BoxTab, RateTab, FieldTab> and <..., BoxTab, RateTab, FieldTab, RoadTab> alone");
-    static_assert(!WA || (RA && !CA && FA != DA && sizeof...(BT) == 4),
-                  "the road forms are <..., BoxTab, RateTab, FieldTab, RoadTab> and <..., BoxTab, DiscTab, RateTab, RoadTab> alone");
+    static_assert(table_form_ok<BT...>() && (BA || sizeof...(BT) == 0), MPC_TABLE_FORMS ", behind the BoxTab");
+    static_assert(!LA || sizeof...(BT) <= 1, "the lookahead is an unconstrained problem's: it has no table form but the box form");
     using BOX = BoxOf<BA, LaneBox>;
     using CON = ConOf<CA, RowCon>;
     extern __shared__ double s_solo[];
@@ -567,25 +533,19 @@ solo_kernel(const DevCfg c, const WsArg<PA> w, const int *__restrict__ list, int
 #if MPC_DEV_STAMP == 5
             t_adv += __builtin_amdgcn_s_memrealtime() - ta;
             if ((req & (REQ_GRAD | REQ_COST | REQ_SPEC)) == REQ_GRAD && (rec_int_of(w.rec[(size_t)a * REC + R_PHASE]) & PH_MASK) == PH_W_HESS) nhess++;
-            if constexpr (WA && FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...), pack_get<RoadTab>(bt...));
-            else if constexpr (WA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...), pack_get<RoadTab>(bt...));
-            else if constexpr (FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...));
-            else if constexpr (DA && RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...));
-            else if constexpr (RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<RateTab>(bt...));
-            else if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk, pack_get<DiscTab>(bt...));
-            else
-            solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, clk);
             ntrip++;
-#else
-            if constexpr (WA && FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...), pack_get<RoadTab>(bt...));
-            else if constexpr (WA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...), pack_get<RoadTab>(bt...));
-            else if constexpr (FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...));
-            else if constexpr (DA && RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...));
-            else if constexpr (RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<RateTab>(bt...));
-            else if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt, pack_get<DiscTab>(bt...));
-            else
-            solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt);
 #endif
+            // (the ladder stays here: handing solo_eval the tables behind the BoxTab through a forwarding overload, or the
+            // whole pack, changes the instruction streams of this kernel's forms -- profiles/r24_stage_data.txt)
+            constexpr bool DA = has_tab<DiscTab, BT...>, RA = has_tab<RateTab, BT...>, FA = has_tab<FieldTab, BT...>, WA = has_tab<RoadTab, BT...>;
+            if constexpr (WA && FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt SOLO_CLK_PASS, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...), pack_get<RoadTab>(bt...));
+            else if constexpr (WA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt SOLO_CLK_PASS, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...), pack_get<RoadTab>(bt...));
+            else if constexpr (FA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt SOLO_CLK_PASS, pack_get<RateTab>(bt...), pack_get<FieldTab>(bt...));
+            else if constexpr (DA && RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt SOLO_CLK_PASS, pack_get<DiscTab>(bt...), pack_get<RateTab>(bt...));
+            else if constexpr (RA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt SOLO_CLK_PASS, pack_get<RateTab>(bt...));
+            else if constexpr (DA) solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt SOLO_CLK_PASS, pack_get<DiscTab>(bt...));
+            else
+            solo_eval<MODEL>(cm, w, a, lane, req, traj, rec, alt SOLO_CLK_PASS);
         }
 #if MPC_DEV_STAMP == 5
         if (lane == 0 && i < DEV_STAMPS) {   // (one buffer for all groups: the claim index of the group whose kernel ran last wins)

@@ -119,14 +119,23 @@ struct ConTab {
 };
 __device__ __forceinline__ void agent_con(DevCfg &c, const ConTab &t, int a) { agent_con(c, t.ctab, t.cidx, a); }
 __device__ __forceinline__ void agent_con_uniform(DevCfg &c, const ConTab &t, int a) { agent_con_uniform(c, t.ctab, t.cidx, a); }
-// The disc table of mpc_set_agent_discs, as the disc forms of the kernels receive it: the same trailing argument, in the
-// ConTab's place (a handle has constraint data or discs, never both).
+// stage_data(table, where): what a table holds for stage k of agent a, as stage_record (mpc_eval.hpp) takes it.  One name,
+// overloaded on the table and on where the caller stands -- the two routes differ in their last arguments, which the rate
+// table alone reads:
+//   (t, a, k, N, useq_slot, St)  a different agent in every lane (K1b, the fused kernel): vector loads of the thread's own
+//                                entries; u_{k-1} and u_{k+1} are the slot's own entries of useq, stride St
+//   (t, a, k, N, row)            one agent per wave (the wave evaluation): the row's address is wave-uniform, lane k takes its
+//                                stage; u_{k-1} and u_{k+1} are the evaluated row's
+// A site hands stage_record `stage_data(t, ...)...` over its whole pack.  The box and the constraint table hold nothing for
+// a stage (the agent's box, DevCfg and multiplier bounds have taken their rows) and have no stage_data: the constraint form
+// is peeled off in front of the call (`if constexpr (has_tab<ConTab, ...>)`, the same at every site), the BoxTab never
+// gets there.
+// The disc table of mpc_set_agent_discs, as the disc forms of the kernels receive it (which forms exist: table_form_ok below).
 struct DiscTab {
     const double *dtab;                            // [P][N][NDISC][3] caller's table
     const int *didx;                               // [B]              caller's row index per agent
 };
-// the discs of stage k of agent a's row: a different agent in every lane (vector loads of the thread's own six doubles)
-__device__ __forceinline__ StageDiscs stage_discs(const DiscTab &t, int a, int k, int N)
+__device__ __forceinline__ StageDiscs stage_data(const DiscTab &t, int a, int k, int N, const double *, size_t)
 {
     const double *__restrict__ r = t.dtab + ((size_t)t.didx[a] * N + k) * (3 * NDISC);
     StageDiscs s;
@@ -134,8 +143,7 @@ __device__ __forceinline__ StageDiscs stage_discs(const DiscTab &t, int a, int k
     for (int i = 0; i < 3 * NDISC; i++) s.v[i] = r[i];
     return s;
 }
-// ... one agent per wave: the row address is wave-uniform, lane k loads its stage
-__device__ __forceinline__ StageDiscs stage_discs_uniform(const DiscTab &t, int a, int k, int N)
+__device__ __forceinline__ StageDiscs stage_data(const DiscTab &t, int a, int k, int N, const double *)
 {
     const int row = __builtin_amdgcn_readfirstlane(t.didx[a]);
     const double *__restrict__ r = t.dtab + (size_t)row * N * (3 * NDISC) + (size_t)k * (3 * NDISC);
@@ -144,8 +152,7 @@ __device__ __forceinline__ StageDiscs stage_discs_uniform(const DiscTab &t, int 
     for (int i = 0; i < 3 * NDISC; i++) s.v[i] = r[i];
     return s;
 }
-// The rate table of mpc_set_agent_rates, as the rate forms of the kernels receive it: the LAST trailing argument, alone
-// or behind the DiscTab (a handle with a rate table has no constraint table: the binder refuses the second of the two).
+// The rate table of mpc_set_agent_rates, as the rate forms of the kernels receive it.
 struct RateTab {
     const double *rtab;                            // [P][NRATE] caller's table
     const int *ridx;                               // [B]        caller's row index per agent
@@ -165,55 +172,44 @@ __device__ __forceinline__ StageRate stage_rate_from(const double *__restrict__ 
     else { s.next[0] = next_of(0); s.next[1] = next_of(1); }
     return s;
 }
-// a different agent in every lane (K1b, the fused kernel): the neighbours are the slot's own entries of useq
-__device__ __forceinline__ StageRate stage_rate(const RateTab &t, int a, int k, int N, const double *__restrict__ useq_slot, size_t St)
+__device__ __forceinline__ StageRate stage_data(const RateTab &t, int a, int k, int N, const double *__restrict__ useq_slot, size_t St)
 {
     return stage_rate_from(t.rtab + (size_t)t.ridx[a] * NRATE, k, N,
                            [=](int i) { return useq_slot[(size_t)(2 * (k - 1) + i) * St]; },
                            [=](int i) { return useq_slot[(size_t)(2 * (k + 1) + i) * St]; });
 }
-// ... one agent per wave (the wave evaluation): the row address is wave-uniform, the neighbours are the evaluated row's
-__device__ __forceinline__ StageRate stage_rate_uniform(const RateTab &t, int a, int k, int N, const double *__restrict__ row)
+__device__ __forceinline__ StageRate stage_data(const RateTab &t, int a, int k, int N, const double *__restrict__ row)
 {
     const int ri = __builtin_amdgcn_readfirstlane(t.ridx[a]);
     return stage_rate_from(t.rtab + (size_t)ri * NRATE, k, N, [=](int i) { return row[2 * (k - 1) + i]; },
                            [=](int i) { return row[2 * (k + 1) + i]; });
 }
-// The field table of mpc_set_agent_fields, as the field forms of the kernels receive it: the LAST trailing argument, behind
-// the RateTab -- the field forms are <..., RateTab, FieldTab> alone (no cross product: without a rate table of the
-// caller's the host puts the handle's own one-row table of zero weights in its place, with_table_form in mpc_launch.hpp,
-// and zero weights change no bit).  Never beside a DiscTab or a ConTab: the binder refuses both.
+// The field table of mpc_set_agent_fields, as the field forms of the kernels receive it.
 struct FieldTab {
     const double *ftab;                            // [P][N][NFIELD][NFSRC] caller's table
     const int *fidx;                               // [B]                   caller's row index per agent
 };
-// the address of stage k's sources in agent a's row: a different agent in every lane ...
-__device__ __forceinline__ StageField stage_field(const FieldTab &t, int a, int k, int N)
+// (the address of stage k's sources in agent a's row)
+__device__ __forceinline__ StageField stage_data(const FieldTab &t, int a, int k, int N, const double *, size_t)
 {
     return StageField{t.ftab + ((size_t)t.fidx[a] * N + k) * (NFIELD * NFSRC)};
 }
-// ... one agent per wave: the row is wave-uniform, lane k takes its stage
-__device__ __forceinline__ StageField stage_field_uniform(const FieldTab &t, int a, int k, int N)
+__device__ __forceinline__ StageField stage_data(const FieldTab &t, int a, int k, int N, const double *)
 {
     const int row = __builtin_amdgcn_readfirstlane(t.fidx[a]);
     return StageField{t.ftab + (size_t)row * N * (NFIELD * NFSRC) + (size_t)k * (NFIELD * NFSRC)};
 }
-// The road table of mpc_set_agent_roads, as the road forms of the kernels receive it: the LAST trailing argument.  Two
-// families and no cross product beyond them: <..., RateTab, FieldTab, RoadTab> on every handle that is not a disc handle
-// (a missing rate table is the handle's own one-row table of zero weights, a missing field table the handle's own one-row
-// table of zeros: with_table_form in mpc_launch.hpp -- neither changes a bit), and <..., DiscTab, RateTab,
-// RoadTab> on disc handles.  Never beside a ConTab: the binder refuses it.
+// The road table of mpc_set_agent_roads, as the road forms of the kernels receive it.
 struct RoadTab {
     const double *wtab;                            // [P][N][NROAD] caller's table
     const int *widx;                               // [B]           caller's row index per agent
 };
-// the address of stage k's entry in agent a's row: a different agent in every lane ...
-__device__ __forceinline__ StageRoad stage_road(const RoadTab &t, int a, int k, int N)
+// (the address of stage k's entry in agent a's row)
+__device__ __forceinline__ StageRoad stage_data(const RoadTab &t, int a, int k, int N, const double *, size_t)
 {
     return StageRoad{t.wtab + ((size_t)t.widx[a] * N + k) * NROAD};
 }
-// ... one agent per wave: the row is wave-uniform, lane k takes its stage
-__device__ __forceinline__ StageRoad stage_road_uniform(const RoadTab &t, int a, int k, int N)
+__device__ __forceinline__ StageRoad stage_data(const RoadTab &t, int a, int k, int N, const double *)
 {
     const int row = __builtin_amdgcn_readfirstlane(t.widx[a]);
     return StageRoad{t.wtab + (size_t)row * N * NROAD + (size_t)k * NROAD};
@@ -229,6 +225,29 @@ __device__ __forceinline__ const X &pack_get(const T0 &t0, const T &...t)
     if constexpr (SameTab<X, T0>::v) return t0;
     else return pack_get<X>(t...);
 }
+// Which table forms exist: THE list on the device, as with_table_form's (mpc_launch.hpp) is on the host, which never hands
+// over another.  A kernel's trailing pack -- behind the BoxTab in the persistent kernel's -- is one of
+//     (empty)                            nothing bound
+//     ConTab                             a constraint table: alone, the binder refuses every table below beside it
+//     DiscTab                            a disc handle (constr_mode 3)
+//     RateTab                            a rate table ...
+//     DiscTab, RateTab                   ... on a disc handle
+//     RateTab, FieldTab                  a field table: behind the rates, never beside discs
+//     RateTab, FieldTab, RoadTab         a road table ...
+//     DiscTab, RateTab, RoadTab          ... on a disc handle
+// No cross product: a rate or field table that a form stands behind and the caller has not bound is the handle's own
+// one-row table of zeros, which changes no bit.  stage_record's pack is the same list in stage data (what stage_data makes
+// of each table), so the predicate reads either.  Adding a table kind adds its line here and its term below.
+template <class... T> constexpr bool table_form_ok()
+{
+    constexpr bool B = has_tab<BoxTab, T...>, C = has_tab<ConTab, T...>, D = has_tab<DiscTab, T...> || has_tab<StageDiscs, T...>,
+                   R = has_tab<RateTab, T...> || has_tab<StageRate, T...>, F = has_tab<FieldTab, T...> || has_tab<StageField, T...>,
+                   W = has_tab<RoadTab, T...> || has_tab<StageRoad, T...>;
+    return sizeof...(T) == B + C + D + R + F + W                  // each kind once at most, and nothing else
+           && (!C || D + R + F + W == 0) && (!F || (R && !D)) && (!W || (R && F != D));
+}
+#define MPC_TABLE_FORMS "the table forms are <ConTab>, <DiscTab>, <RateTab>, <DiscTab, RateTab>, <RateTab, FieldTab>, " \
+                        "<RateTab, FieldTab, RoadTab> and <DiscTab, RateTab, RoadTab> alone (table_form_ok, mpc_solver.hpp)"
 template <bool PA> struct WsArgT { using type = Workspace; };
 template <> struct WsArgT<true> { using type = WorkspacePA; };
 template <bool PA> using WsArg = typename WsArgT<PA>::type;
