@@ -616,11 +616,12 @@ extern "C" int mpc_prox_step(mpc_handle *h, int B, const double *x, const double
     if (B == 0) return MPC_OK;
     if (!x || !grad || !gamma || !out) return fail(MPC_E_ARG, "mpc_prox_step: null buffer");
     rc = check_tables(h, B, "mpc_prox_step", READS_BOX); if (rc) return rc;
-    if (const BoundTable &box = h->tab[TAB_BOX]; box.table)
-        hipLaunchKernelGGL(prox_box_kernel, grid_for(B, 64), dim3(64), 0, (hipStream_t)stream, h->dc, B, x, grad, gamma, xhat, p, out,
-                           BoxTab{box.table, box.idx});
-    else
-        hipLaunchKernelGGL(prox_kernel, grid_for(B, 64), dim3(64), 0, (hipStream_t)stream, h->dc, B, x, grad, gamma, xhat, p, out);
+    const auto launch = [&](auto... t) {
+        hipLaunchKernelGGL((prox_kernel<decltype(t)...>), grid_for(B, 64), dim3(64), 0, (hipStream_t)stream, h->dc, B, x, grad, gamma, xhat, p,
+                           out, t...);
+    };
+    if (const BoundTable &box = h->tab[TAB_BOX]; box.table) launch(BoxTab{box.table, box.idx});
+    else launch();
     HIPCHK(hipGetLastError());
     return MPC_OK;
 }

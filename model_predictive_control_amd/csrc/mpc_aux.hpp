@@ -162,36 +162,24 @@ __global__ void __launch_bounds__(64) stage_cost_kernel(const DevCfg c_, int B, 
     out[a] = stage_cost<MODEL, false>(c, g, xv, u[2 * (size_t)a], u[2 * (size_t)a + 1], xb, ub);
 }
 
-// K2 standalone (agent-major arrays)
+// K2 standalone (agent-major arrays).  T...: empty -- the handle's box -- or <BoxTab>: onto every agent's own box, row
+// bt.bidx[a] of the bounds table (mpc_set_agent_bounds)
+template <class... T>
 __global__ void prox_kernel(const DevCfg c, int B, const double *__restrict__ x,
                             const double *__restrict__ g, const double *__restrict__ gamma,
                             double *__restrict__ xhat, double *__restrict__ p,
-                            double *__restrict__ out)
+                            double *__restrict__ out, const T... t)
 {
+    constexpr bool BA = has_tab<BoxTab, T...>;
+    static_assert(sizeof...(T) == BA, "prox_kernel's forms are <> and <BoxTab>");
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= B) return;
-    double pp = 0.0, gp = 0.0;
-    const double gm = gamma[a];
-    for (int j = 0; j < c.n; j++) {
-        const double xv = x[(size_t)a * c.n + j], gv = g[(size_t)a * c.n + j];
-        const double pv = prox_p(c, CfgBox(), j & 1, xv, gv, gm);
-        if (xhat) xhat[(size_t)a * c.n + j] = xv + pv;
-        if (p) p[(size_t)a * c.n + j] = pv;
-        pp += pv * pv; gp += gv * pv;
+    BoxOf<BA, AgentBox> bx{};
+    if constexpr (BA) {
+        const BoxTab &bt = pack_get<BoxTab>(t...);
+        const double *__restrict__ row = bt.btab + (size_t)bt.bidx[a] * NBOUND;
+        bx.lb[0] = row[0]; bx.lb[1] = row[1]; bx.ub[0] = row[2]; bx.ub[1] = row[3];
     }
-    out[2 * (size_t)a] = pp; out[2 * (size_t)a + 1] = gp;
-}
-// ... onto every agent's own box, row bt.bidx[a] of the bounds table (mpc_set_agent_bounds)
-__global__ void prox_box_kernel(const DevCfg c, int B, const double *__restrict__ x,
-                                const double *__restrict__ g, const double *__restrict__ gamma,
-                                double *__restrict__ xhat, double *__restrict__ p,
-                                double *__restrict__ out, const BoxTab bt)
-{
-    const int a = blockIdx.x * blockDim.x + threadIdx.x;
-    if (a >= B) return;
-    const double *__restrict__ row = bt.btab + (size_t)bt.bidx[a] * NBOUND;
-    AgentBox bx;
-    bx.lb[0] = row[0]; bx.lb[1] = row[1]; bx.ub[0] = row[2]; bx.ub[1] = row[3];
     double pp = 0.0, gp = 0.0;
     const double gm = gamma[a];
     for (int j = 0; j < c.n; j++) {

@@ -1,20 +1,20 @@
 // mpc_launch.hpp -- host side of libmpc_hip.so, part 2: from the handle's run-time state to ONE instantiation of each
 // kernel template.  Every run-time choice becomes template arguments in one place: a flag in with_flag, the model in
 // with_model / with_model_table, the L-BFGS history variant in with_hist_variant, and the per-agent tables a kernel takes
-// as its trailing pack in with_table_form -- the one list of the table forms that exist.  So each kernel template is named
-// at one launch site, and a new flag or table is added once.  What is instantiated is what these functions and the
-// `if constexpr`s below let through, never the cross product: the Pacejka model has no fused K1b + K1c, the lookahead
-// exists for <PAC, NE = 1> without a table form alone, adjoint_kernel has no per-agent form, and the step kernel has
-// forms of its own (launch_step_t: it reads the box and the constraint data and no other table).
+// as its pack in with_table_form -- the one list of the table forms that exist -- and, for the step kernel, which reads
+// the box and the constraint data and no other table, in with_step_form.  So each kernel template is named at one launch
+// site, and a new flag or table is added once.  What is instantiated is what these functions and the `if constexpr`s
+// below let through, never the cross product: the Pacejka model has no fused K1b + K1c, the lookahead exists for
+// <PAC, NE = 1> without a table form alone, adjoint_kernel has no per-agent form, and the step kernel has a constraint
+// form on a constrained problem alone.
 #pragma once
 #include "mpc_handle.hpp"
 
 #include <type_traits>
 
 template <int V> using int_c = std::integral_constant<int, V>;
-// f(std::true_type / std::false_type) for a run-time flag; two of them: f(A, B)
+// f(std::true_type / std::false_type) for a run-time flag
 template <class F> static void with_flag(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
-template <class F> static void with_flags(bool a, bool b, F &&f) { with_flag(a, [&](auto A) { with_flag(b, [&](auto B) { f(A, B); }); }); }
 // f(int_c<KIN> / int_c<PAC>) for the handle's model; returns what f returns
 template <class F> static auto with_model(int model, F &&f) { if (model == PAC) return f(int_c<PAC>{}); return f(int_c<KIN>{}); }
 // The standalone kernels (mpc_aux.hpp, solo_eval_kernel) for this handle's model, with or without the bound parameter
@@ -66,6 +66,17 @@ template <class F> static void with_table_form(const mpc_handle *h, const Worksp
     else if (w.bound(TAB_RATES)) { if (discs) form(w.disc(), w.rate()); else form(w.rate()); }
     else if (discs) form(w.disc());
     else with_flag(w.ptab != nullptr, [&](auto PA) { f(PA, WorkspacePA(w)); });
+}
+
+// The forms of step_kernel, the one kernel of the round path that reads the box and the constraint data: f(HASM, t...)
+// with the tables view `w` hands it as its pack -- the bounds table and the constraint table where they are bound, the
+// box first (the same list on the device: step_form_ok).  A constraint table is bound on a constrained problem or it
+// would not be, so its forms exist for HASM = true alone.
+template <class F> static void with_step_form(const mpc_handle *h, const WorkspaceHost &w, F &&f)
+{
+    const auto form = [&](auto HASM, auto... t) { if (w.bound(TAB_BOX)) f(HASM, w.box(), t...); else f(HASM, t...); };
+    if (w.bound(TAB_CONSTR)) form(std::true_type{}, w.con());
+    else with_flag(h->dc.m != 0, [&](auto HASM) { form(HASM); });
 }
 
 // How the step kernel and the persistent kernel read an agent's L-BFGS history -- f(int_c<NE>, int_c<MC>), the two
@@ -228,27 +239,9 @@ static void launch_step_t(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, 
     const int apb = apb_env == 64 || apb_env == 32 || apb_env == 16 || apb_env == 8 || apb_env == 4 ? apb_env
                   : w.B >= 32768 ? 64 : w.B >= 16384 ? (lean ? 32 : 64) : w.B >= 6144 ? 16 : 4;
     const int nstep = (w.B + apb - 1) / apb;
-    // (a constraint table is bound -- on a constrained problem, or it would not be -- the constraint form,
-    // without or with the box form)
-    if (w.bound(TAB_CONSTR)) {
-        with_flag(w.bound(TAB_BOX), [&](auto BA) {
-            if constexpr (BA())
-                hipLaunchKernelGGL((step_kernel_box_con<NE, MC>), dim3((unsigned)(nstep + nchain)), dim3(64 * STEP_WAVES), lds,
-                                   s, dcl, w, w.box(), w.con(), lists, counts, counts_next, apb, nstep, par, P);
-            else
-                hipLaunchKernelGGL((step_kernel_con<NE, MC>), dim3((unsigned)(nstep + nchain)), dim3(64 * STEP_WAVES), lds,
-                                   s, dcl, w, w.con(), lists, counts, counts_next, apb, nstep, par, P);
-        });
-        return;
-    }
-    // (a bounds table is bound: the per-agent-box form -- the one kernel of the round path that reads the box)
-    with_flags(h->dc.m != 0, w.bound(TAB_BOX), [&](auto HASM, auto BA) {
-        if constexpr (BA())
-            hipLaunchKernelGGL((step_kernel_box<NE, MC, HASM()>), dim3((unsigned)(nstep + nchain)), dim3(64 * STEP_WAVES), lds,
-                               s, dcl, w, w.box(), lists, counts, counts_next, apb, nstep, par, P);
-        else
-            hipLaunchKernelGGL((step_kernel<NE, MC, HASM()>), dim3((unsigned)(nstep + nchain)), dim3(64 * STEP_WAVES), lds,
-                               s, dcl, w, lists, counts, counts_next, apb, nstep, par, P);
+    with_step_form(h, w, [&](auto HASM, auto... t) {
+        hipLaunchKernelGGL((step_kernel<NE, MC, HASM(), decltype(t)...>), dim3((unsigned)(nstep + nchain)), dim3(64 * STEP_WAVES), lds,
+                           s, dcl, w, t..., lists, counts, counts_next, apb, nstep, par, P);
     });
 }
 static void launch_step(mpc_handle *h, const WorkspaceHost &w, hipStream_t s, int *lists, int *counts, int *counts_next,

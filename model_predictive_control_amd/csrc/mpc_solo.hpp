@@ -66,7 +66,7 @@ __host__ __device__ inline size_t la_lds_doubles(int n) { return (size_t)LA_ENTR
 // The persistent kernel hands advance_agent a history copy that is NOT filled ahead of the step (hist_ready): the copy is
 // filled, waited for and read inside PH_LS_INIT of one step, so between two steps -- during an evaluation -- it is free.
 // The overlay below is sound on that condition alone; a kernel that prefetches the history across an evaluation (as
-// mpc_step_body.hpp does) sets this to true and gets the second half's LDS behind the first half's instead.
+// step_kernel does) sets this to true and gets the second half's LDS behind the first half's instead.
 constexpr bool SOLO_HIST_PREFETCH = false;
 template <int MODEL> __host__ __device__ inline bool solo_second_on_hist(int N, int n, int M, bool hist)
 {

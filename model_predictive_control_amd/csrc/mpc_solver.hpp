@@ -103,16 +103,16 @@ struct WorkspacePA : Workspace {
     const double *ptab;                            // [P][NPARAM] caller's table
     const int *pidx;                               // [B]         caller's row index per agent
 };
-// The input-box table of mpc_set_agent_bounds, as the per-agent-box kernels (step_kernel_box, the box form of solo_kernel,
-// prox_box_kernel) receive it: an argument of its own BEHIND the DevCfg and the Workspace, so that Workspace -- and with
-// it the argument segment and the code of every kernel that has no box form -- is what it was, and KernArgs::W_OFF holds
-// for the new kernels too.
+// The input-box table of mpc_set_agent_bounds, as the box forms of the kernels (step_kernel, solo_kernel, prox_kernel:
+// a BoxTab in their table pack) receive it: an argument of its own, never a member of the Workspace, so that Workspace
+// -- and with it the argument segment and the code of every form without a box -- is what it was, and KernArgs::W_OFF
+// holds for every form.
 struct BoxTab {
     const double *btab;                            // [P][NBOUND] caller's table
     const int *bidx;                               // [B]         caller's row index per agent
 };
-// The constraint table of mpc_set_agent_constraints, as the constraint forms of the kernels receive it: an argument of
-// its own behind everything the form without it takes (behind the BoxTab where a kernel has both).
+// The constraint table of mpc_set_agent_constraints, as the constraint forms of the kernels receive it: the next
+// argument of the pack (behind the BoxTab where a kernel has both: step_form_ok, table_form_ok below).
 struct ConTab {
     const double *ctab;                            // [P][NCONSTR] caller's table
     const int *cidx;                               // [B]          caller's row index per agent
@@ -225,6 +225,12 @@ __device__ __forceinline__ const X &pack_get(const T0 &t0, const T &...t)
     if constexpr (SameTab<X, T0>::v) return t0;
     else return pack_get<X>(t...);
 }
+// ... and how many tables stand in front of it there
+template <class X, class T0, class... T> constexpr size_t pack_index()
+{
+    if constexpr (SameTab<X, T0>::v) return 0;
+    else return 1 + pack_index<X, T...>();
+}
 // Which table forms exist: THE list on the device, as with_table_form's (mpc_launch.hpp) is on the host, which never hands
 // over another.  A kernel's trailing pack -- behind the BoxTab in the persistent kernel's -- is one of
 //     (empty)                            nothing bound
@@ -248,6 +254,21 @@ template <class... T> constexpr bool table_form_ok()
 }
 #define MPC_TABLE_FORMS "the table forms are <ConTab>, <DiscTab>, <RateTab>, <DiscTab, RateTab>, <RateTab, FieldTab>, " \
                         "<RateTab, FieldTab, RoadTab> and <DiscTab, RateTab, RoadTab> alone (table_form_ok, mpc_solver.hpp)"
+// The step kernel reads the box and the constraint data and no other table, so its pack -- BEHIND the Workspace there,
+// in front of the list pointers: KernArgs -- has forms of its own, as with_step_form's (mpc_launch.hpp) list is on the host:
+//     (empty)            nothing bound
+//     BoxTab             a bounds table
+//     ConTab             a constraint table: on a constrained problem (HASM) alone, nothing else has constraint data
+//     BoxTab, ConTab     both, the box first
+template <bool HASM, class... T> constexpr bool step_form_ok()
+{
+    constexpr bool B = has_tab<BoxTab, T...>, C = has_tab<ConTab, T...>;
+    if constexpr (sizeof...(T) != B + C || (C && !HASM)) return false;   // each kind once at most, and nothing else
+    else if constexpr (B && C) return pack_index<BoxTab, T...>() == 0;
+    else return true;
+}
+#define MPC_STEP_FORMS "the step kernel's forms are <>, <BoxTab>, <ConTab> and <BoxTab, ConTab>, a ConTab with HASM alone " \
+                       "(step_form_ok, mpc_solver.hpp)"
 template <bool PA> struct WsArgT { using type = Workspace; };
 template <> struct WsArgT<true> { using type = WorkspacePA; };
 template <bool PA> using WsArg = typename WsArgT<PA>::type;
@@ -270,17 +291,17 @@ struct KernArgs {
     }
     __device__ __forceinline__ const DevCfg &c() const { return *(const DevCfg *)p; }
     __device__ __forceinline__ const Workspace &w() const { return *(const Workspace *)(p + W_OFF); }
-    // (the per-agent-box kernels alone: their third parameter)
-    static constexpr size_t B_OFF = (W_OFF + sizeof(Workspace) + alignof(BoxTab) - 1) / alignof(BoxTab) * alignof(BoxTab);
-    __device__ __forceinline__ const BoxTab &box() const { return *(const BoxTab *)(p + B_OFF); }
-    // (the constraint forms alone: their third parameter, or their fourth behind the BoxTab)
+    // The step kernel's pack T... (step_form_ok) lies behind the Workspace, one table after the other: table X of it ...
+    static constexpr size_t T_OFF = (W_OFF + sizeof(Workspace) + alignof(BoxTab) - 1) / alignof(BoxTab) * alignof(BoxTab);
     static_assert(sizeof(ConTab) == sizeof(BoxTab) && alignof(ConTab) == alignof(BoxTab), "one layout for the two table arguments");
-    __device__ __forceinline__ const ConTab &con(bool behind_box) const { return *(const ConTab *)(p + B_OFF + (behind_box ? sizeof(BoxTab) : 0)); }
-    // ... and pointer i of the three every step kernel's parameter list goes on with (lists_out, counts_out, counts_next),
-    // which in those forms lie behind the ConTab
-    __device__ __forceinline__ int *con_tail(bool behind_box, int i) const
+    template <class X, class... T> __device__ __forceinline__ const X &tab() const
     {
-        return *(int *const *)(p + B_OFF + (behind_box ? sizeof(BoxTab) : 0) + sizeof(ConTab) + i * sizeof(int *));
+        return *(const X *)(p + T_OFF + pack_index<X, T...>() * sizeof(BoxTab));
+    }
+    // ... and pointer i of the three the parameter list goes on with behind the pack (lists_out, counts_out, counts_next)
+    template <class... T> __device__ __forceinline__ int *tail(int i) const
+    {
+        return *(int *const *)(p + T_OFF + sizeof...(T) * sizeof(BoxTab) + i * sizeof(int *));
     }
 };
 
@@ -459,7 +480,7 @@ __device__ __forceinline__ void strow(double *__restrict__ p, int n, int lane, c
 // Where the projection takes the input box C = [lo, hi] of element parity `par` (0 drive, 1 steering) from.
 //   CfgBox    the handle's box, read from the DevCfg at the point of use -- what every kernel without a box form does
 //   LaneBox   the agent's own box in the wave-per-agent code: this lane's two values (par = lane & 1 is the lane's)
-//   AgentBox  the agent's own box where a thread owns the agent (chain_block, prox_box_kernel): the whole row
+//   AgentBox  the agent's own box where a thread owns the agent (chain_block, prox_kernel): the whole row
 struct CfgBox {
     __device__ __forceinline__ double lo(const DevCfg &c, int par) const { return c.u_lb[par]; }
     __device__ __forceinline__ double hi(const DevCfg &c, int par) const { return c.u_ub[par]; }
@@ -503,10 +524,10 @@ __device__ __forceinline__ LaneBox lane_box_uniform(const BoxTab &bt, int a, int
 //   CfgCon   the handle's, read from the DevCfg at the point of use -- what every kernel without a constraint form does
 //   RowCon   the agent's own row of a bound constraint table, at a wave-uniform address the persistent kernel forms when
 //            it claims the agent: lane kk's two values by vector loads
-//   KernCon  the same row in the step kernels, found where it is needed: the table out of the kernel's argument segment
-//            (KernArgs::con), the agent's row index, then the two values -- dependent loads in a phase an agent passes
+//   KernCon  the same row in the step kernel, found where it is needed: the table out of the kernel's argument segment
+//            (KernArgs::tab), the agent's row index, then the two values -- dependent loads in a phase an agent passes
 //            a few times per solve, and nothing held in registers across the state machine meanwhile (the constrained
-//            step kernels use all 106 scalar registers as they are)
+//            forms use all 106 scalar registers as they are)
 MPC_DEV void row_bounds(const DevCfg &c, const double *__restrict__ row, int kk, double &lb, double &ub)
 {
     if (c.constr_mode == 2) { const double hw = row[18]; lb = -hw; ub = hw; }
@@ -525,10 +546,10 @@ struct RowCon {
         row_bounds(c, row, kk, lb, ub);
     }
 };
-template <bool BEHIND_BOX> struct KernCon {
+template <class... T> struct KernCon {                   // T...: the step kernel's pack
     __device__ __forceinline__ void bounds(const DevCfg &c, const KernArgs &ka, int a, int kk, double &lb, double &ub) const
     {
-        const ConTab &t = ka.con(BEHIND_BOX);
+        const ConTab &t = ka.tab<ConTab, T...>();
         row_bounds(c, t.ctab + (size_t)__builtin_amdgcn_readfirstlane(t.cidx[a]) * NCONSTR, kk, lb, ub);
     }
 };
@@ -1592,63 +1613,159 @@ __host__ __device__ constexpr int step_waves_per_simd(int ne, int mc, bool hasm)
     return (ne == 1 && mc < 0 && !hasm) ? MPC_STEP_WAVES_LEAN : (ne == 2 && mc < 0) ? 3 : 2;
 }
 
-template <int NE, int MC, bool HASM>
+// the BoxTab of the step kernel's pack; a null one, which nothing reads, where it holds none
+template <class... T> __device__ __forceinline__ decltype(auto) step_box(const T &...t)
+{
+    if constexpr (has_tab<BoxTab, T...>) return pack_get<BoxTab>(t...);
+    else return BoxTab{nullptr, nullptr};
+}
+
+// T...: the step kernel's form (step_form_ok) -- with a BoxTab (BA) every agent projects onto its own input box
+// (mpc_set_agent_bounds), with a ConTab (CA) it has its own constraint bounds (mpc_set_agent_constraints): same
+// occupancy targets, same LDS plan.  The pack stands in the middle of the parameter list, so nothing deduces it: a launch
+// names it.  The body reads the ConTab out of the argument segment where it needs it (KernCon), so that table is named
+// by nothing but the launch.
+//
+// The box form: the workgroup's row indices arrive with its phase words (one coalesced read, lane l: agent base + l), so
+// an agent's row is addressed from a register, and its two values per lane are asked for with the record and the rows
+// of the wave's NEXT agent -- in flight one agent ahead like everything else, never a dependent load where the
+// projection needs them.
+template <int NE, int MC, bool HASM, class... T>
 __global__ void __launch_bounds__(64 * STEP_WAVES, step_waves_per_simd(NE, MC, HASM))
-step_kernel(const DevCfg c, const Workspace w, int *__restrict__ lists_out,
+step_kernel(const DevCfg c, const Workspace w, const T... t, int *__restrict__ lists_out,
             int *__restrict__ counts_out, int *__restrict__ counts_next, int apb, int nstep, int par, int P)
 {
-#define MPC_STEP_BA false
-#define MPC_STEP_BT BoxTab{nullptr, nullptr}
-#define MPC_STEP_CA false
-#include "mpc_step_body.hpp"
-#undef MPC_STEP_BA
-#undef MPC_STEP_BT
-#undef MPC_STEP_CA
-}
-// ... with every agent's own input box (mpc_set_agent_bounds): same body, same occupancy targets, same LDS plan
-template <int NE, int MC, bool HASM>
-__global__ void __launch_bounds__(64 * STEP_WAVES, step_waves_per_simd(NE, MC, HASM))
-step_kernel_box(const DevCfg c, const Workspace w, const BoxTab bt, int *__restrict__ lists_out,
-                int *__restrict__ counts_out, int *__restrict__ counts_next, int apb, int nstep, int par, int P)
-{
-#define MPC_STEP_BA true
-#define MPC_STEP_BT bt
-#define MPC_STEP_CA false
-#include "mpc_step_body.hpp"
-#undef MPC_STEP_BA
-#undef MPC_STEP_BT
-#undef MPC_STEP_CA
-}
-// ... with every agent's own constraint data (mpc_set_agent_constraints), without and with its own box.  Only a
-// constrained problem has constraint data: these exist for HASM alone.  (The body reads the table out of the argument
-// segment where it needs it -- KernCon -- so `ct` is named by nothing but the launch.)
-template <int NE, int MC>
-__global__ void __launch_bounds__(64 * STEP_WAVES, step_waves_per_simd(NE, MC, true))
-step_kernel_con(const DevCfg c, const Workspace w, const ConTab ct, int *__restrict__ lists_out,
-                int *__restrict__ counts_out, int *__restrict__ counts_next, int apb, int nstep, int par, int P)
-{
-    constexpr bool HASM = true;
-#define MPC_STEP_BA false
-#define MPC_STEP_BT BoxTab{nullptr, nullptr}
-#define MPC_STEP_CA true
-#include "mpc_step_body.hpp"
-#undef MPC_STEP_BA
-#undef MPC_STEP_BT
-#undef MPC_STEP_CA
-}
-template <int NE, int MC>
-__global__ void __launch_bounds__(64 * STEP_WAVES, step_waves_per_simd(NE, MC, true))
-step_kernel_box_con(const DevCfg c, const Workspace w, const BoxTab bt, const ConTab ct, int *__restrict__ lists_out,
-                    int *__restrict__ counts_out, int *__restrict__ counts_next, int apb, int nstep, int par, int P)
-{
-    constexpr bool HASM = true;
-#define MPC_STEP_BA true
-#define MPC_STEP_BT bt
-#define MPC_STEP_CA true
-#include "mpc_step_body.hpp"
-#undef MPC_STEP_BA
-#undef MPC_STEP_BT
-#undef MPC_STEP_CA
+    static_assert(step_form_ok<HASM, T...>(), MPC_STEP_FORMS);
+    constexpr bool BA = has_tab<BoxTab, T...>, CA = has_tab<ConTab, T...>;
+    const BoxTab &bt = step_box(t...);
+    // blocks [0, nstep): the wave-per-agent state machine; blocks beyond (c.chain): PH_W_LS_G by one thread per
+    // agent for the gradient slots of the round just finished, whose count K1c left in counts_next[2] (the buffer
+    // of that round: this kernel zeroes its two list counters for the round after this one, not that word)
+    if ((int)blockIdx.x >= nstep) {
+        extern __shared__ double s_chain[];
+        if (NE == 1) chain_block<BA>(c, w, bt, (int)blockIdx.x - nstep, counts_next[2], par, lists_out, counts_out, s_chain);
+        return;
+    }
+    // apb = agents per workgroup (64, 16 or 4): a wave walks its agents one after the other, so a small
+    // batch is spread over more workgroups (one agent per wave at apb = 4) -- latency, not throughput
+    __shared__ int s_req[64];
+    __shared__ int s_next;
+    extern __shared__ double s_hist[];                   // MC < 0: 2 M n doubles per wave
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#if MPC_DEV_STAMP == 3
+    DevStamp stamp(blockIdx.x * STEP_WAVES + wv);
+#endif
+    double *hist = s_hist + (MC < 0 ? (size_t)wv * 2 * P * c.n : 0);
+    if (blockIdx.x == 0 && threadIdx.x == 0) { counts_next[0] = 0; counts_next[1] = 0; } // next round's buffer
+    // Which of the workgroup's agents are still running: one coalesced look at their phase words.
+    // Only the running ones are handed to the waves, so a wave never pays a memory round trip to
+    // find out that an agent is finished.
+    const int base = blockIdx.x * apb;
+    const int phw = lane < apb && base + lane < w.B ? rec_int_of(w.rec[(size_t)(base + lane) * REC + R_PHASE]) : 0;
+    int brow = 0;                                        // (BA) row of the bounds table of agent base + lane
+    if constexpr (BA) brow = lane < apb && base + lane < w.B ? bt.bidx[base + lane] : 0;
+    using CON = ConOf<CA, KernCon<T...>>;
+    using BOX = BoxOf<BA, LaneBox>;
+    const auto box_of = [&](const BoxTab &b, int l) {
+        if constexpr (BA) return load_lane_box(b, __builtin_amdgcn_readlane(brow, l), lane);
+        else return CfgBox();
+    };
+    // (PH_DONE == 0; with c.chain an agent that waits in PH_W_LS_G is served by a chain_block of this launch)
+    const bool runnable = phw != 0 && !(c.chain && (phw == PH_W_LS_G || phw == PH_W_LS_C + chain_tag(par)));
+    const unsigned long long act = __ballot(runnable);
+    const int rank = __popcll(act & ((1ull << lane) - 1ull));
+    const int nact = __popcll(act);
+    if (threadIdx.x == 0) s_next = 0;
+    if (wv == 0) s_req[lane] = REQ_NONE;
+    __syncthreads();
+    // the waves take the running agents from a shared counter, one ahead of the one they work on (its
+    // rows are in flight meanwhile): an agent-step costs between ~0.3 and ~3 us depending on its phase,
+    // and a static deal leaves three waves waiting for the unlucky one
+    auto claim = [&]() -> int {
+        int i = 0;
+        if (lane == 0) i = atomicAdd(&s_next, 1);
+        i = __builtin_amdgcn_readfirstlane(i);
+        if (i >= nact) return -1;
+        return (int)__builtin_ctzll(__ballot(runnable && rank == i));
+    };
+    AgentIn<NE> nxt;
+    BOX nbx{};
+    int loc = claim();
+    // (MPC_ALL_ROWS: the six-row fetch of rounds 1 - 2, for the A/B measurement and the bit-identity test)
+    const auto phase_of = [&](const DevCfg &cc, int l) { return cc.all_rows ? -1 : (__builtin_amdgcn_readlane(phw, l) & PH_MASK); };
+    if (loc >= 0) { nxt = load_agent<NE>(c, w, base + loc, lane, phase_of(c, loc)); nbx = box_of(bt, loc); }
+    while (loc >= 0) {
+        // (the kernel's parameters c and w are not used inside this loop: see KernArgs)
+        const KernArgs ka;
+        const DevCfg &c = ka.c();
+        const Workspace &w = ka.w();
+        const int a = base + loc;
+        const AgentIn<NE> cur = nxt;
+        const BOX cbx = nbx;
+        const int loc_next = claim();
+        if (loc_next >= 0) {                             // in flight during agent a
+            nxt = load_agent<NE>(c, w, base + loc_next, lane, phase_of(c, loc_next));
+            if constexpr (BA) nbx = box_of(ka.tab<BoxTab, T...>(), loc_next);
+        }
+        bool hist_ready = false;
+        if (MC < 0) {
+            // An agent that comes back from its Hessian-vector evaluation (or from the cost of a trial
+            // whose speculative gradient is there) runs the two-loop almost first thing: start the
+            // LDS-DMA of its history now.  Issued BEHIND the next agent's row loads: the wait for the
+            // history drains the wave's vector-memory queue in order, so nothing younger than what it
+            // needs should be in it.
+            const int rlo = __double2loint(cur.rv);      // (the integers of the record: rec_int)
+            const int ph = __builtin_amdgcn_readlane(rlo, R_PHASE) & PH_MASK;
+            const int hi = __builtin_amdgcn_readlane(rlo, R_LIDX), hf = __builtin_amdgcn_readlane(rlo, R_LFULL);
+            const int hl = hi | hf;
+            const int sp = __builtin_amdgcn_readlane(rlo, R_SPEC);
+            if ((ph == PH_W_HESS || (ph == PH_W_LS_C && sp != 0)) && hl != 0) {
+                hist_dma(w.S + (size_t)a * c.M * c.n, w.Y + (size_t)a * c.M * c.n, hist, P * c.n,
+                         (hf ? c.M : hi) * c.n, lane);
+                hist_ready = true;
+            }
+        }
+#if MPC_DEV_STAMP == 3
+        stamp.nfall++;                                   // agent-steps of this wave
+        const long long tv0 = __builtin_amdgcn_s_memrealtime();
+        const int ph_in = __builtin_amdgcn_readlane(__double2loint(cur.rv), R_PHASE) & PH_MASK;
+#endif
+        const int req = advance_agent<NE, MC, HASM, true, BOX, CON>(c, w, a, lane, cur, hist, hist_ready, true, /*allow_chain=*/true, P, cbx, CON());
+#if MPC_DEV_STAMP == 3
+        {   // the longest agent-step of this wave: its length in 10 ns ticks (nmid, capped at 255) and the phase it came in with (nslow)
+            const int dt = (int)(__builtin_amdgcn_s_memrealtime() - tv0);
+            if (dt > stamp.nmid) { stamp.nmid = dt > 255 ? 255 : dt; stamp.nslow = ph_in; }
+        }
+#endif
+        if (lane == 0) s_req[loc] = req;
+        loc = loc_next;
+    }
+    __syncthreads();
+    // (CA: the two list pointers are read again from the argument segment here, where they are used, and so are not held
+    // across the loop above -- four scalar registers that the constrained forms, at 106 of 106, do not have)
+    int *lists_o = lists_out, *counts_o = counts_out;
+    if constexpr (CA) {
+        const KernArgs kt;
+        lists_o = kt.tail<T...>(0); counts_o = kt.tail<T...>(1);
+    }
+    if (wv == 0) {
+        const int r = s_req[lane];
+#pragma unroll
+        for (int kind = 0; kind < 2; kind++) { // 0: gradient list (normal or channel 2), 1: cost list
+            const bool on = kind == 0 ? (r & (REQ_GRAD | REQ_SPEC)) != 0 : (r & REQ_COST) != 0;
+            const unsigned long long bal = __ballot(on);
+            const int cnt = __popcll(bal);
+            if (cnt == 0) continue;                      // uniform
+            int base = 0;
+            if (lane == 0) base = atomicAdd(&counts_o[kind], cnt);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (on) {
+                const int off = __popcll(bal & ((1ull << lane) - 1ull));
+                const int flag = kind == 0 ? ((r & REQ_SPEC) ? CH2_BIT : 0) | ((r & REQ_CHAIN) ? CHAIN_BIT : 0) : 0;
+                lists_o[(size_t)kind * w.Ls + base + off] = (blockIdx.x * apb + lane) | flag;
+            }
+        }
+    }
 }
 
 // solver state initialisation for a fresh solve (ALMSolver::operator() prologue)

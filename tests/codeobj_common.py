@@ -2,6 +2,7 @@
 spills, LDS or argument layout, and by tools/dev/codeobj_diff.py): the AMDGPU metadata of every kernel, as the LLVM
 tools of the ROCm installation print it.  No GPU needed."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -39,6 +40,24 @@ def built_library_kernels(tmp_path_factory, skip=True):
     assert not missing, "needs " + ", ".join(missing)
     _lib.build()
     return kernel_metadata(_lib.LIB_PATH, str(tmp_path_factory.mktemp("codeobj")))
+
+
+STEP_LEAN_TARGS = "Li1ELin1ELb0E"      # <NE, MC, HASM> = <1, -1, false>: the benchmark problem's step kernel
+
+
+def step_forms(kernels, *tables):
+    """The instantiations step_kernel<NE, MC, HASM, tables...> in `kernels` (`tables`: struct names, the whole pack in
+    its order; none: the empty pack), by their mangled names: [(mangled <NE, MC, HASM>, kernel name)], sorted."""
+    pack = "J" + "".join("NS_%d%sE" % (len(t), t) for t in tables) + "EEE"      # J <pack> E, template arguments E, name E
+    rx = re.compile(r"_ZN3mpc11step_kernelI(Li\d+ELin?\d+ELb[01]E)" + pack + "v")
+    return sorted((m.group(1), n) for n in kernels for m in [rx.match(n)] if m)
+
+
+def step_form(kernels, targs, *tables):
+    """The metadata of the one step_kernel<targs, tables...>."""
+    found = [n for t, n in step_forms(kernels, *tables) if t == targs]
+    assert len(found) == 1, (targs, tables, found)
+    return kernels[found[0]]
 
 
 def _waves_by_vgprs(vgprs):

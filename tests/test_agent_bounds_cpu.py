@@ -15,11 +15,9 @@ import pytest
 from conftest import ROOT
 
 import model_predictive_control_amd as mp
-from codeobj_common import _waves_by_vgprs, built_library_kernels
+from codeobj_common import STEP_LEAN_TARGS, _waves_by_vgprs, built_library_kernels, step_form, step_forms
 from model_predictive_control_amd import _lib
 
-STEP_BOX = "_ZN3mpc15step_kernel_boxI"            # every per-agent-box step kernel
-STEP_BOX_LEAN = STEP_BOX + "Li1ELin1ELb0EEE"      # step_kernel_box<1, -1, false>: the benchmark problem's
 STEP_LDS_BYTES = 264                              # s_req[64] + s_next (+ padding), as the shared kernel
 LEAN_WAVES_PER_SIMD = 5                           # the shared lean kernel's target, and this one's
 
@@ -115,9 +113,7 @@ def kernels(tmp_path_factory):
 
 
 def test_lean_box_step_kernel_fits_the_shared_kernels_target(L, kernels):
-    lean = [k for n, k in kernels.items() if n.startswith(STEP_BOX_LEAN)]
-    assert len(lean) == 1
-    k = lean[0]
+    k = step_form(kernels, STEP_LEAN_TARGS, "BoxTab")       # step_kernel<1, -1, false, BoxTab>: exactly one
     assert k[".sgpr_spill_count"] == 0
     assert k[".vgpr_spill_count"] == 0
     assert k[".private_segment_fixed_size"] == 0
@@ -133,19 +129,17 @@ def test_lean_box_step_kernel_fits_the_shared_kernels_target(L, kernels):
 
 
 def test_every_step_kernel_has_a_box_form_with_the_shared_argument_layout(kernels):
-    shared = sorted(n for n in kernels if n.startswith("_ZN3mpc11step_kernelI"))
-    box = sorted(n for n in kernels if n.startswith(STEP_BOX))
+    shared, box = step_forms(kernels), step_forms(kernels, "BoxTab")
     assert len(shared) == 8 and len(box) == 8
     # the same eight <NE, MC, HASM>
-    targs = lambda n, pre: n[len(pre):n.index("EEE") + 3]
-    assert [targs(n, "_ZN3mpc11step_kernelI") for n in shared] == [targs(n, STEP_BOX) for n in box]
-    for sn, bn in zip(shared, box):
+    assert [t for t, _ in shared] == [t for t, _ in box]
+    for (_, sn), (_, bn) in zip(shared, box):
         s, k = kernels[sn], kernels[bn]
         cfg, ws, bt = k[".args"][0], k[".args"][1], k[".args"][2]
         assert cfg[".value_kind"] == ws[".value_kind"] == bt[".value_kind"] == "by_value"
         assert cfg[".offset"] == 0 and cfg[".size"] % 8 == 0
         assert ws[".offset"] == cfg[".size"]                                  # KernArgs::W_OFF
         assert (cfg[".size"], ws[".size"]) == (s[".args"][0][".size"], s[".args"][1][".size"])
-        assert bt[".offset"] == ws[".offset"] + ws[".size"] and bt[".size"] == 16   # KernArgs::B_OFF: two pointers
+        assert bt[".offset"] == ws[".offset"] + ws[".size"] and bt[".size"] == 16   # KernArgs::T_OFF: two pointers
         assert k[".group_segment_fixed_size"] == s[".group_segment_fixed_size"]
         assert k[".private_segment_fixed_size"] == 0 and k[".vgpr_spill_count"] == 0

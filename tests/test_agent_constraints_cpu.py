@@ -15,13 +15,8 @@ import pytest
 from conftest import ROOT
 
 import model_predictive_control_amd as mp
-from codeobj_common import _waves_by_vgprs, built_library_kernels
+from codeobj_common import _waves_by_vgprs, built_library_kernels, step_forms
 from model_predictive_control_amd import _lib
-
-STEP = "_ZN3mpc11step_kernelI"
-STEP_BOX = "_ZN3mpc15step_kernel_boxI"
-STEP_CON = "_ZN3mpc15step_kernel_conI"
-STEP_BOX_CON = "_ZN3mpc19step_kernel_box_conI"
 
 
 @pytest.fixture(scope="module")
@@ -133,17 +128,17 @@ def _waves(k):
 
 
 def test_every_constrained_step_kernel_has_its_constraint_forms(kernels):
-    """step_kernel<NE, MC, true> -> step_kernel_con<NE, MC>, step_kernel_box<NE, MC, true> -> step_kernel_box_con<NE, MC>:
-    no scratch, no spilled vector register, no more spilled scalars and no more vector registers than the form it derives
-    from, its LDS, and -- by registers (512 per SIMD lane, blocks of 8) -- exactly its waves per SIMD."""
-    for parent_pre, con_pre in ((STEP, STEP_CON), (STEP_BOX, STEP_BOX_CON)):
-        key = lambda n, pre: re.match(r"(Li\d+ELin?\d+E)", n[len(pre):]).group(1)        # <NE, MC>
-        parents = sorted(n for n in kernels if n.startswith(parent_pre) and n[len(parent_pre) + len(key(n, parent_pre)):].startswith("Lb1E"))
-        cons = sorted(n for n in kernels if n.startswith(con_pre))
+    """step_kernel<NE, MC, true> -> step_kernel<NE, MC, true, ConTab>, step_kernel<NE, MC, true, BoxTab> ->
+    step_kernel<NE, MC, true, BoxTab, ConTab>: no scratch, no spilled vector register, no more spilled scalars and no more
+    vector registers than the form it derives from, its LDS, and -- by registers (512 per SIMD lane, blocks of 8) --
+    exactly its waves per SIMD."""
+    for box in ((), ("BoxTab",)):
+        parents = [(t, n) for t, n in step_forms(kernels, *box) if t.endswith("Lb1E")]      # HASM
+        cons = step_forms(kernels, *box, "ConTab")
         assert len(parents) == 4 and len(cons) == 4
-        # the same four <NE, MC>
-        assert [key(n, parent_pre) for n in parents] == [key(n, con_pre) for n in cons]
-        for pn, cn in zip(parents, cons):
+        # the same four <NE, MC>, and a constraint form of a constrained kernel alone
+        assert [t for t, _ in parents] == [t for t, _ in cons]
+        for (_, pn), (_, cn) in zip(parents, cons):
             p, k = kernels[pn], kernels[cn]
             assert k[".private_segment_fixed_size"] == 0 and k[".vgpr_spill_count"] == 0
             assert k[".sgpr_spill_count"] <= p[".sgpr_spill_count"], (cn, k[".sgpr_spill_count"], p[".sgpr_spill_count"])
@@ -152,15 +147,15 @@ def test_every_constrained_step_kernel_has_its_constraint_forms(kernels):
             assert k[".group_segment_fixed_size"] == p[".group_segment_fixed_size"]
             assert k[".max_flat_workgroup_size"] == 256
             # the argument layout KernArgs reads: DevCfg, Workspace, the tables (two pointers each), then the list
-            # pointers the constraint forms read again behind their loop (KernArgs::con_tail)
+            # pointers the constraint forms read again behind their loop (KernArgs::tail)
             args, pargs = k[".args"], p[".args"]
             assert (args[0][".size"], args[1][".size"]) == (pargs[0][".size"], pargs[1][".size"])
             assert args[1][".offset"] == args[0][".size"]                     # KernArgs::W_OFF
-            ntab = 2 if con_pre == STEP_BOX_CON else 1
+            ntab = len(box) + 1
             for j in range(ntab):
                 t = args[2 + j]
                 assert t[".value_kind"] == "by_value" and t[".size"] == 16
-                assert t[".offset"] == args[1][".offset"] + args[1][".size"] + 16 * j   # KernArgs::B_OFF, KernArgs::con
+                assert t[".offset"] == args[1][".offset"] + args[1][".size"] + 16 * j   # KernArgs::T_OFF, KernArgs::tab
             for j in range(3):
                 t = args[2 + ntab + j]
                 assert t[".value_kind"] == "global_buffer" and t[".size"] == 8
@@ -175,5 +170,6 @@ def test_the_k1_kernels_and_the_persistent_kernel_have_constraint_forms(kernels)
     assert count("20stage_adjoint_kernel", k1) == 2    # the kinematic model's fused K1b + K1c
     assert count("16solo_eval_kernel", k1) == 2        # the wave evaluation
     assert count("11solo_kernel", "Lb0ELb1EJNS_6BoxTabENS_6ConTabEEE") == 6   # two models x three history variants, never the lookahead
-    # ... and in no other form: every kernel that names the ConTab in its template arguments is one of these
-    assert sum(1 for n in kernels if "JNS_6ConTabEE" in n or "ENS_6ConTabEEE" in n) == 14
+    # ... and in no other form: every kernel that names the ConTab in its template arguments is one of these 4 + 2 + 2 + 6
+    # = 14 or one of the step kernel's 4 + 4 constraint forms (test_every_constrained_step_kernel_has_its_constraint_forms)
+    assert sum(1 for n in kernels if "JNS_6ConTabEE" in n or "ENS_6ConTabEEE" in n) == 14 + 8

@@ -9,10 +9,9 @@ import pytest
 
 from conftest import ROOT  # noqa: F401  (puts the repository on sys.path)
 
-from codeobj_common import _waves_by_vgprs, built_library_kernels
+from codeobj_common import STEP_LEAN_TARGS, _waves_by_vgprs, built_library_kernels, step_form
 from model_predictive_control_amd import _lib
 
-STEP_LEAN = "_ZN3mpc11step_kernelILi1ELin1ELb0EEEvNS_6DevCfgENS_9WorkspaceEPiS3_S3_iiii"
 STEP_LDS_BYTES = 264          # s_req[64] + s_next (+ padding): the history copy is dynamic LDS, sized at launch
 LEAN_WAVES_PER_SIMD = 5
 CU_LDS = 160 * 1024
@@ -31,7 +30,7 @@ def kernels(tmp_path_factory):
 
 
 def test_lean_step_kernel_fits_its_target(kernels):
-    k = kernels[STEP_LEAN]
+    k = step_form(kernels, STEP_LEAN_TARGS)
     assert k[".sgpr_spill_count"] == 0
     assert k[".vgpr_spill_count"] == 0
     assert k[".private_segment_fixed_size"] == 0

@@ -7,11 +7,10 @@ import pytest
 
 from conftest import ROOT  # noqa: F401  (puts the repository on sys.path)
 
-from codeobj_common import built_library_kernels
+from codeobj_common import STEP_LEAN_TARGS, built_library_kernels, step_form, step_forms
 
 pytest.importorskip("yaml")
 
-STEP_LEAN = "_ZN3mpc11step_kernelILi1ELin1ELb0EEEvNS_6DevCfgENS_9WorkspaceEPiS3_S3_iiii"
 STEP_LDS_BYTES = 264   # s_req[64] + s_next (+ padding): the history copy is dynamic LDS, sized at launch
 
 
@@ -21,7 +20,8 @@ def kernels(tmp_path_factory):
 
 
 def test_lean_step_kernel_does_not_spill(kernels):
-    k = kernels[STEP_LEAN]
+    k = step_form(kernels, STEP_LEAN_TARGS)
+    assert [a[".value_kind"] for a in k[".args"][:9]] == ["by_value"] * 2 + ["global_buffer"] * 3 + ["by_value"] * 4
     assert k[".sgpr_spill_count"] == 0
     assert k[".vgpr_spill_count"] == 0
     assert k[".private_segment_fixed_size"] == 0          # no scratch
@@ -30,8 +30,10 @@ def test_lean_step_kernel_does_not_spill(kernels):
 
 
 def test_step_kernels_argument_layout(kernels):
-    steps = [k for n, k in kernels.items() if n.startswith("_ZN3mpc11step_kernel")]
-    assert len(steps) >= 8
+    forms = [step_forms(kernels, *t) for t in ((), ("BoxTab",), ("ConTab",), ("BoxTab", "ConTab"))]
+    assert [len(f) for f in forms] == [8, 8, 4, 4]
+    steps = [kernels[n] for f in forms for _, n in f]
+    assert len(steps) == sum(1 for n in kernels if n.startswith("_ZN3mpc11step_kernelI"))    # no form but these
     for k in steps:
         cfg, ws = k[".args"][0], k[".args"][1]
         assert cfg[".value_kind"] == "by_value" and ws[".value_kind"] == "by_value"

@@ -6,7 +6,8 @@ For every kernel present in both: registers (vector, accumulator, scalar), spill
 bytes must be equal; differences are listed.  Kernels only in NEW (the per-agent instantiations) are listed with
 the same figures and the waves per SIMD their registers allow (512 unified registers per SIMD lane on gfx950,
 allocated in blocks of 8; at most 8 waves).  A kernel that gained a trailing `false` template argument (the
-per-agent flag at its default) is matched with the old kernel of the same name without it.  No GPU needed.
+per-agent flag at its default) is matched with the old kernel of the same name without it, and a box or constraint
+form of step_kernel or prox_kernel with the kernel of a name of its own that it was (old_name).  No GPU needed.
 """
 import os
 import re
@@ -27,7 +28,20 @@ def kernels(lib):
         ks = list(kernel_metadata(lib, d).values())
     filt = _tool("llvm-cxxfilt") or _tool("c++filt")
     names = subprocess.check_output([filt] + [k[".name"] for k in ks], text=True).split("\n")
-    return {re.sub(r"\(.*$", "", nm).replace("void ", "").replace("mpc::", ""): k for k, nm in zip(ks, names)}
+    return {old_name(re.sub(r"\(.*$", "", nm).replace("void ", "").replace("mpc::", "")): k for k, nm in zip(ks, names)}
+
+
+def old_name(nm):
+    """A box or constraint form of step_kernel or prox_kernel by the name it had as a kernel of its own, so that the two
+    spellings match: step_kernel<1, 0, true, BoxTab, ConTab> was step_kernel_box_con<1, 0>, prox_kernel<BoxTab> prox_box_kernel."""
+    m = re.fullmatch(r"(step|prox)_kernel<(.*?)(?:, )?(BoxTab)?(?:, )?(ConTab)?>", nm)
+    if not m:
+        return nm
+    k, args, box, con = m.groups()
+    sfx = "_box" * bool(box) + "_con" * bool(con)
+    if con:
+        args = args[:-len(", true")]
+    return (k + "_kernel" + sfx if k == "step" else k + sfx + "_kernel") + ("<%s>" % args if args else "")
 
 
 def waves(k):

@@ -3,7 +3,8 @@
     python tools/dev/isa_diff.py OLD.s NEW.s
 
 Every kernel of OLD is matched with the kernel of the same demangled name in NEW (or the one that gained a trailing
-`false` template argument: the per-agent flag at its default) and their instruction streams are compared with labels
+`false` template argument: the per-agent flag at its default; or the box / constraint form of step_kernel or prox_kernel
+that was a kernel of a name of its own, in either direction) and their instruction streams are compared with labels
 and symbol names masked.  Prints the kernels that differ and the counts.  No GPU needed.
 """
 import re,subprocess,sys
@@ -30,11 +31,18 @@ for n in new:
 for n in new:   # the per-agent flag at its default, stripped -- only where that name is not taken
     b=base(n); s=re.sub(r"<false>$","",re.sub(r", false>$",">",b))
     if s!=b and (b.endswith("false>")): newby.setdefault("STRIP:"+s,n)
+def old_name(b):   # a box or constraint form that had a kernel name of its own: step_kernel<1, 0, true, BoxTab, ConTab> was
+    m=re.fullmatch(r"(.*::)?(step|prox)_kernel<(.*?)(?:, )?(mpc::BoxTab)?(?:, )?(mpc::ConTab)?>",b)   # step_kernel_box_con<1, 0>
+    if not m: return b
+    ns,k,args,box,con=m.groups(); sfx="_box"*bool(box)+"_con"*bool(con)
+    if con: args=args[:-len(", true")]
+    return (ns or "")+(k+"_kernel"+sfx if k=="step" else k+sfx+"_kernel")+("<%s>"%args if args else "")
+for n in new: newby.setdefault("STRIP:"+old_name(base(n)),n)
 mask=lambda x: re.sub(r"\.L\w+","LBL",re.sub(r"_Z\w+","SYM",x))
 same=diff=0
 for n in old:
     if "kernel" not in dem[n]: continue
-    k=newby.get("STRIP:"+base(n)) or newby.get(base(n))
+    k=newby.get("STRIP:"+old_name(base(n))) or newby.get(base(n))
     if k is None: print("missing",dem[n][:80]); continue
     ma=[mask(x) for x in old[n]]; mb=[mask(x) for x in new[k]]
     if ma==mb: same+=1
