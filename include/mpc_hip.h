@@ -625,6 +625,63 @@ int mpc_closed_loop_obstacles(mpc_handle *h, int B, int T, int shift, int G, int
                               int32_t *traj_sel, double *traj_clear, int32_t *fail_count, double *stats, void *stream,
                               const mpc_track *trk);
 
+/* Event-triggered holding among scripted obstacles: mpc_closed_loop_event's trigger watches the car alone, and an obstacle
+ * that appears does not move the plant off its plan; these three calls add the trigger that watches the obstacles.  It is
+ * time-aligned: stage held + k of a held plan meets sample ti + k of the scripts.
+ * mpc_rollout_held: X [B][N][nx] (out), the states agent b reaches from x[b] by going on applying the plan U[b] ([B][2N])
+ * of which it has applied held[b] stages: with k_b = min(max(held[b], 0), N - 1), X[b][j] is the state after the inputs
+ * u_{min(k_b + i, N - 1)}, i = 0 .. j -- the last input repeated into the tail, the index rule of the in-place shift of
+ * mpc_closed_loop_event.  On the controller's parameter row, as mpc_rollout.  Bit for bit mpc_rollout(x, the shifted U);
+ * held <= 0 is mpc_rollout(x, U).  One thread per agent, asynchronous on `stream`.  MPC_E_ARG: a NULL buffer, with tables
+ * bound a B other than the bound one, an asynchronous solve in flight.
+ * mpc_obstacle_trigger: the obstacle rule, pure -- it shifts no plan and rewrites no table.  The scene arguments are
+ * mpc_obstacles_select's; X [B][N][nx] is mpc_rollout_held's; sel_plan [B][MPC_NDISC] (int32) holds the tracks the held
+ * plan was solved against (-1: none).  The selection of mpc_obstacles_select runs for agent b over the stages its plan
+ * still holds, j < N - k_b, and no others (the repeated tail was never constrained and does not fire the rule), stage j
+ * against sample ti + j: sel_chk [B][MPC_NDISC] and clear_chk [B][MPC_NDISC] (out; slot 0 is the smallest c < reach^2,
+ * +inf if there is none).  Then, per agent, why[b] (uint8, out, NULL ok):
+ *     bit 0 (1)  fire_in[b] != 0 (fire_in [B] int32, e.g. mpc_trigger_eval's; NULL: none)
+ *     bit 1 (2)  held[b] > 0, watch & 1 and !(clear_chk[b][0] >= clear_thr): the plan comes too close
+ *     bit 2 (4)  held[b] > 0, watch & 2 and some sel_chk[b][j] >= 0 is not a member of {sel_plan[b][0], sel_plan[b][1]}:
+ *                a new obstacle (set membership: a change of order is none)
+ * and fire_out[b] = why[b] != 0 (int32, out; may be fire_in).  clear_thr is in the units of the clearance: on a handle of
+ * MPC_CONSTR_DISCS g = d^2 - r^2, and a solved plan rides g = 0 to within alm_delta, so a useful clear_thr is slightly
+ * negative; on every other handle r2 = 0 and clear_thr is a squared distance.  Asynchronous on `stream`.  MPC_E_ARG before
+ * any launch: everything mpc_obstacles_select refuses (Nst = N), clear_thr > reach^2 (slot 0 would not see it) or NaN,
+ * watch outside [0, 3], a NULL X, held, sel_plan, sel_chk, clear_chk or fire_out.
+ * mpc_closed_loop_obstacles_event: mpc_closed_loop_obstacles in which an agent keeps applying the plan it holds.  The
+ * arguments are those of mpc_closed_loop_event (w, thr, max_hold, held, disturbance, solved, solve_count) and of
+ * mpc_closed_loop_obstacles (the scene, t0, table, traj_sel, traj_clear, trk), clear_thr and watch as above, sel_plan
+ * [B][MPC_NDISC] (in/out) and traj_why [B][T] (uint8, NULL ok).  Blocking.  Step t, ti = t0 + t + 1, every launch being
+ * the one the public call of that name makes:
+ *   1. fire = mpc_trigger_eval(x, xhat, held) -- no plan is shifted yet; a handle that has no nominal states for this B
+ *      fires everybody at its first step, as in mpc_closed_loop_event
+ *   2. X = mpc_rollout_held(x, U, held)
+ *   3. fire, traj_why[.][t] = mpc_obstacle_trigger(X, held, sel_plan, fire_in = fire) at ti
+ *   4. shift != 0: the plans of the firing agents with held > 0 are shifted in place by k_b stages
+ *   5. trk != NULL: mpc_track_select(x, active = fire) -- the firing agents re-select their window
+ *   6. sel = mpc_obstacles_select(X, ti, Nst = N) of everybody; traj_sel [B][T][MPC_NDISC] records it
+ *   7. the gather of the handle's kind at ti into the rows of the FIRING agents alone, and sel_plan[b] = sel[b] for them:
+ *      a held agent's row stays the one its plan was solved on
+ *   8. mpc_solve_active(fire); 9. the rate table's u_prev write; 10. the step of mpc_closed_loop_event (plant, nominal
+ *      state, held, solved, solve_count, fail_count, disturbance)
+ *  11. traj_clear[.][t] as in mpc_closed_loop_obstacles: the realised clearance on the new states
+ * held, sel_plan, U and lambda are in/out: a second call with t0 + T and what the first returned continues both the script
+ * and the holding.  U returns as last solved (not shifted by the stages applied since).  MPC_E_ARG: what
+ * mpc_closed_loop_event, mpc_closed_loop_obstacles and mpc_obstacle_trigger refuse, and a NULL sel_plan. */
+int mpc_rollout_held(mpc_handle *h, int B, const double *x, const double *U, const int32_t *held, double *X, void *stream);
+int mpc_obstacle_trigger(mpc_handle *h, int B, int G, int K, int Lt, int wrap, int ti, const double *X, const double *obs,
+                         double reach, const int32_t *held, const int32_t *sel_plan, double clear_thr, int watch,
+                         const int32_t *fire_in, int32_t *sel_chk, double *clear_chk, uint8_t *why, int32_t *fire_out,
+                         void *stream);
+int mpc_closed_loop_obstacles_event(mpc_handle *h, int B, int T, int shift, const double *w, double thr, int max_hold, int G,
+                                    int K, int Lt, int wrap, int t0, const double *obs, double reach, double clear_thr,
+                                    int watch, double *x, const double *cl, int32_t *cl_index, double *U, double *lambda,
+                                    int32_t *held, int32_t *sel_plan, double *table, const double *disturbance,
+                                    double *traj_x, double *traj_u, int32_t *traj_sel, double *traj_clear,
+                                    uint8_t *traj_why, uint8_t *solved, int32_t *solve_count, int32_t *fail_count,
+                                    double *stats, void *stream, const mpc_track *trk);
+
 /* profiling aid: rounds (eval launches) and kernel time of the last mpc_solve_batch */
 int mpc_last_solve_info(mpc_handle *h, int64_t *rounds, int64_t *evals_grad, int64_t *evals_cost,
                         double *eval_ms, double *step_ms);

@@ -168,6 +168,7 @@ extern "C" int mpc_destroy(mpc_handle *h)
     if (h->ev.base) (void)hipFree(h->ev.base);
     if (h->ev.xhat) (void)hipFree(h->ev.xhat);
     if (h->tr.base) (void)hipFree(h->tr.base);
+    if (h->orule.base) (void)hipFree(h->orule.base);
     if (h->own_ptab) (void)hipFree(h->own_ptab);
     if (h->cl_gmeta) (void)hipFree(h->cl_gmeta);
     if (h->cl_gxy) (void)hipFree(h->cl_gxy);
@@ -498,6 +499,20 @@ extern "C" int mpc_rollout(mpc_handle *h, int B, int Nsim, const double *x0, con
     hipStream_t s = (hipStream_t)stream;
     with_model_table(h, h->params().idx, [&](auto MODEL, auto PA, auto... pt) {
         hipLaunchKernelGGL((simulate_kernel<MODEL(), PA(), decltype(pt)...>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, Nsim, x0, U, X, pt...);
+    });
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
+extern "C" int mpc_rollout_held(mpc_handle *h, int B, const double *x, const double *U, const int32_t *held, double *X, void *stream)
+{
+    int rc = check_common(h, B, "mpc_rollout_held"); if (rc) return rc;
+    if (B == 0) return MPC_OK;
+    if (!x || !U || !held || !X) return fail(MPC_E_ARG, "mpc_rollout_held: null buffer");
+    rc = check_tables(h, B, "mpc_rollout_held", READS_PARAMS); if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    with_model_table(h, h->params().idx, [&](auto MODEL, auto PA, auto... pt) {
+        hipLaunchKernelGGL((simulate_held_kernel<MODEL(), PA(), decltype(pt)...>), grid_for(B, 64), dim3(64), 0, s, h->dc, B, x, U, held, X, pt...);
     });
     HIPCHK(hipGetLastError());
     return MPC_OK;
@@ -938,11 +953,17 @@ extern "C" int mpc_track_select(mpc_handle *h, const mpc_track *t, int B, const 
 // the solve, once per round window, as in every solve); data never leaves the device.
 // (trk != null: mpc_closed_loop_track -- between the trigger and the masked solve the firing agents re-select their row
 // of the window table `cl` on the plant state, and traj_row records the row in force; trk == null launches nothing more)
+// (Hook::on: mpc_closed_loop_obstacles_event -- the trigger leaves the plans alone and hook.fired(t, fire) (the obstacle rule on
+// top of fire, then the shift) runs behind it, hook.selected (the selection and the firing agents' rows) behind the track's
+// re-selection and before the solve, hook.stepped (the realised clearance) behind the step; each returns an rc, as
+// plant_loop's before and after do.  NoEventHook launches nothing more.)
+struct NoEventHook { static constexpr bool on = false; };
+template <class Hook = NoEventHook>
 static int closed_loop_event_impl(const char *who_, mpc_handle *h, int B, int T, int shift, const double *w, double thr, int max_hold,
                                   double *x, const double *cl, const int32_t *cl_index, double *U, double *lambda,
                                   int32_t *held, const double *disturbance, double *traj_x, double *traj_u,
                                   uint8_t *solved, int32_t *solve_count, int32_t *fail_count, double *stats, void *stream,
-                                  const mpc_track *trk, int32_t *cl_index_rw, int32_t *traj_row)
+                                  const mpc_track *trk, int32_t *cl_index_rw, int32_t *traj_row, const Hook &hook = Hook())
 {
     const std::string who(who_);
     int rc = check_trigger_args(who_, w, thr, max_hold, held); if (rc) return rc;
@@ -966,10 +987,12 @@ static int closed_loop_event_impl(const char *who_, mpc_handle *h, int B, int T,
     const TrigW tw = trigger_weights(h, w);
     for (int t = 0; t < T; t++) {
         // (nominal states just allocated: every agent re-plans at the first step, whatever `held` says)
-        launch_trigger(h, s, B, x, e.xhat, held, tw, thr, max_hold, fresh && t == 0, nullptr, e.fire, shift ? U : nullptr);
+        launch_trigger(h, s, B, x, e.xhat, held, tw, thr, max_hold, fresh && t == 0, nullptr, e.fire, shift && !Hook::on ? U : nullptr);
+        if constexpr (Hook::on) { rc = hook.fired(t, e.fire); if (rc) return rc; }
         if (trk)
             hipLaunchKernelGGL(track_select_kernel, grid_for(B, 64), dim3(64), 0, s, c, track_geom(trk), B, c.nx, x, cl, e.fire,
                                near_for(h, cl), cl_index_rw, (int *)nullptr, traj_row, t, T);
+        if constexpr (Hook::on) { rc = hook.selected(t, e.fire); if (rc) return rc; }
         rc = solve_active_impl(h, B, e.fire, x, cl, cl_index, U, lambda, st, nullptr, s, false); if (rc) return rc;
         launch_rate_prev(h, s, B, U, held, e.fire);
         // bound table: the plant advances with row pidx_plant[b] (null: the controller's), the nominal state with pidx[b]
@@ -983,6 +1006,7 @@ static int closed_loop_event_impl(const char *who_, mpc_handle *h, int B, int T,
                                    c, B, t, T, x, e.xhat, U, held, e.fire, disturbance, traj_x, traj_u, solved, solve_count,
                                    st, fail_count);
         });
+        if constexpr (Hook::on) { rc = hook.stepped(t, e.fire); if (rc) return rc; }
     }
     HIPCHK(hipGetLastError());
     return bounded_sync(h, s, who_);
@@ -1141,9 +1165,10 @@ static int check_obstacle_window(const std::string &who, int ti, long long stage
 static bool obstacle_discs(const mpc_handle *h) { return h->cfg.constr_mode == MPC_CONSTR_DISCS; }
 
 // the selection on plans X [B][Nst][nx] against the window from sample `ti` (see obstacles_kernel for the three outputs)
+// (held != null: the held form -- agent b compares the stages a plan of Nst of which held[b] are applied still holds)
 static void launch_obstacles(mpc_handle *h, hipStream_t s, int B, int G, int K, int Lt, int wrap, int ti, int Nst, const double *X,
                              const double *obs, double reach, int32_t *sel, int32_t *sel_rec, size_t rec_stride, double *clear,
-                             size_t clear_stride, int clear_slots)
+                             size_t clear_stride, int clear_slots, const int32_t *held = nullptr)
 {
     int Gp = 1, Kp = 1;
     while (Gp < G) Gp <<= 1;
@@ -1151,8 +1176,13 @@ static void launch_obstacles(mpc_handle *h, hipStream_t s, int B, int G, int K, 
     const int spw = 64 / std::max(Gp, Kp), scenes = B / G;
     const dim3 grid((unsigned)((scenes + spw - 1) / spw));
     with_flag(obstacle_discs(h), [&](auto DISCS) {
-        hipLaunchKernelGGL((obstacles_kernel<DISCS() ? 3 : MPC_NFSRC>), grid, dim3(TR_BLK), 0, s, B, G, K, Kp, spw, Lt, wrap ? 1 : 0, ti,
-                           Nst, h->dc.nx, X, obs, reach * reach, sel, sel_rec, rec_stride, clear, clear_stride, clear_slots);
+        if (held)
+            hipLaunchKernelGGL((obstacles_kernel<DISCS() ? 3 : MPC_NFSRC, true, const int32_t *>), grid, dim3(TR_BLK), 0, s, B, G, K, Kp, spw,
+                               Lt, wrap ? 1 : 0, ti, Nst, h->dc.nx, X, obs, reach * reach, sel, sel_rec, rec_stride, clear, clear_stride,
+                               clear_slots, held);
+        else
+            hipLaunchKernelGGL((obstacles_kernel<DISCS() ? 3 : MPC_NFSRC>), grid, dim3(TR_BLK), 0, s, B, G, K, Kp, spw, Lt, wrap ? 1 : 0, ti,
+                               Nst, h->dc.nx, X, obs, reach * reach, sel, sel_rec, rec_stride, clear, clear_stride, clear_slots);
     });
 }
 
@@ -1174,14 +1204,19 @@ extern "C" int mpc_obstacles_select(mpc_handle *h, int B, int G, int K, int Lt, 
 }
 
 // the gather of the window of the selected tracks from sample `ti` into table [B][N][MPC_NDISC][W] (rows_from_obstacles_kernel)
+// (mask != null: the masked form -- the rows of the agents with mask[b] != 0 alone, and sel_plan[b] <- sel[b] for them)
 static void launch_rows(mpc_handle *h, hipStream_t s, int B, int G, int K, int Lt, int wrap, int ti, const double *obs,
-                        const int32_t *sel, double *table)
+                        const int32_t *sel, double *table, const int32_t *mask = nullptr, int32_t *sel_plan = nullptr)
 {
     const size_t words = (size_t)B * h->cfg.N * MPC_NDISC;
     const dim3 grid((unsigned)((words + 255) / 256));
     with_flag(obstacle_discs(h), [&](auto DISCS) {
-        hipLaunchKernelGGL((rows_from_obstacles_kernel<DISCS() ? 3 : MPC_NFSRC>), grid, dim3(256), 0, s, B, h->cfg.N, G, K, Lt,
-                           wrap ? 1 : 0, ti, obs, sel, table);
+        if (mask)
+            hipLaunchKernelGGL((rows_from_obstacles_kernel<DISCS() ? 3 : MPC_NFSRC, true, RowMask>), grid, dim3(256), 0, s, B, h->cfg.N, G, K,
+                               Lt, wrap ? 1 : 0, ti, obs, sel, table, RowMask{mask, sel_plan});
+        else
+            hipLaunchKernelGGL((rows_from_obstacles_kernel<DISCS() ? 3 : MPC_NFSRC>), grid, dim3(256), 0, s, B, h->cfg.N, G, K, Lt,
+                               wrap ? 1 : 0, ti, obs, sel, table);
     });
 }
 // what the two public gathers check (`discs`: the disc form), asynchronous
@@ -1279,6 +1314,116 @@ extern "C" int mpc_closed_loop_obstacles(mpc_handle *h, int B, int T, int shift,
     rc = plant_loop(h, B, T, shift, x, cl, cl_index, U, lambda, traj_x, traj_u, fail_count, stats, stream, before, after);
     if (rc) return rc;
     return bounded_sync(h, s, who.c_str());
+}
+
+// ------------------------------------------------------------------- event-triggered holding among scripted obstacles
+// what mpc_obstacle_trigger and mpc_closed_loop_obstacles_event ask of the rule's arguments (checked without a device)
+static int check_obstacle_rule(const std::string &who, double reach, double clear_thr, int watch)
+{
+    if (!(reach >= 0.0)) return fail(MPC_E_ARG, who + ": reach must be >= 0 (+inf: every obstacle of the scene)");
+    if (!(clear_thr <= reach * reach))
+        return fail(MPC_E_ARG, who + ": clear_thr must be a number <= reach^2 (the selection sees no clearance beyond reach)");
+    if (watch < 0 || watch > 3) return fail(MPC_E_ARG, who + ": watch must be in [0, 3] (bit 0: the clearance rule, bit 1: the new-obstacle rule)");
+    return MPC_OK;
+}
+// the selection over the stages every plan still holds, then the rule (sel_chk [B][MPC_NDISC], clear_chk [B][MPC_NDISC])
+static void launch_obstacle_trigger(mpc_handle *h, hipStream_t s, int B, int G, int K, int Lt, int wrap, int ti, const double *X,
+                                    const double *obs, double reach, const int32_t *held, const int32_t *sel_plan, double clear_thr,
+                                    int watch, const int32_t *fire_in, int32_t *sel_chk, double *clear_chk, uint8_t *why,
+                                    size_t why_stride, int32_t *fire_out)
+{
+    launch_obstacles(h, s, B, G, K, Lt, wrap, ti, h->cfg.N, X, obs, reach, sel_chk, nullptr, 0, clear_chk, MPC_NDISC, MPC_NDISC, held);
+    hipLaunchKernelGGL(obstacle_rule_kernel, grid_for(B, 64), dim3(64), 0, s, B, held, sel_chk, clear_chk, sel_plan, clear_thr, watch,
+                       fire_in, fire_out, why, why_stride);
+}
+
+extern "C" int mpc_obstacle_trigger(mpc_handle *h, int B, int G, int K, int Lt, int wrap, int ti, const double *X, const double *obs,
+                                    double reach, const int32_t *held, const int32_t *sel_plan, double clear_thr, int watch,
+                                    const int32_t *fire_in, int32_t *sel_chk, double *clear_chk, uint8_t *why, int32_t *fire_out,
+                                    void *stream)
+{
+    const std::string who = "mpc_obstacle_trigger";
+    int rc = check_obstacle_args(who, B, G, K, Lt, ti, "ti", obs); if (rc) return rc;
+    rc = check_obstacle_rule(who, reach, clear_thr, watch); if (rc) return rc;
+    if (!X || !held || !sel_plan || !sel_chk || !clear_chk || !fire_out)
+        return fail(MPC_E_ARG, who + ": null X, held, sel_plan, sel_chk, clear_chk or fire_out");
+    rc = check_common(h, B, who.c_str()); if (rc) return rc;
+    rc = check_obstacle_window(who, ti, h->cfg.N, "ti"); if (rc) return rc;
+    rc = check_tables(h, B, who.c_str(), READS_ALL); if (rc) return rc;
+    if (B == 0) return MPC_OK;
+    launch_obstacle_trigger(h, (hipStream_t)stream, B, G, K, Lt, wrap, ti, X, obs, reach, held, sel_plan, clear_thr, watch, fire_in,
+                            sel_chk, clear_chk, why, 1, fire_out);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
+// The event-triggered loop among scripted obstacles: closed_loop_event_impl with the hook of the obstacles -- every launch
+// the one the public call of that name makes (see include/mpc_hip.h for the eleven steps)
+struct ObstacleEventHook {
+    static constexpr bool on = true;
+    mpc_handle *h; hipStream_t s; void *stream;
+    int B, T, shift, G, K, Lt, wrap, t0;
+    const double *obs; double reach, clear_thr; int watch;
+    double *x, *U; int32_t *held, *sel_plan; double *table;
+    int32_t *traj_sel; double *traj_clear; uint8_t *traj_why;
+    // steps 2 - 4: what every agent will go on applying, the rule on top of `fire`, the shift of the agents that fire
+    int fired(int t, int32_t *fire) const
+    {
+        const int rr = mpc_rollout_held(h, B, x, U, held, h->tr.X, stream); if (rr) return rr;
+        launch_obstacle_trigger(h, s, B, G, K, Lt, wrap, t0 + t + 1, h->tr.X, obs, reach, held, sel_plan, clear_thr, watch, fire,
+                                h->orule.sel_chk, h->orule.clear_chk, traj_why ? traj_why + t : nullptr, (size_t)T, fire);
+        if (shift) hipLaunchKernelGGL(plan_shift_kernel, grid_for(B, 64), dim3(64), 0, s, B, h->dc.N, held, fire, U);
+        return MPC_OK;
+    }
+    // steps 6 - 7: everybody's selection on the full window, the rows and sel_plan of the agents that fire
+    int selected(int t, int32_t *fire) const
+    {
+        const int ti = t0 + t + 1;
+        launch_obstacles(h, s, B, G, K, Lt, wrap, ti, h->dc.N, h->tr.X, obs, reach, h->tr.opp,
+                         traj_sel ? traj_sel + (size_t)t * MPC_NDISC : nullptr, (size_t)T * MPC_NDISC, nullptr, 0, 0);
+        launch_rows(h, s, B, G, K, Lt, wrap, ti, obs, h->tr.opp, table, fire, sel_plan);
+        return MPC_OK;
+    }
+    // step 11: the realised clearance on the new states
+    int stepped(int t, int32_t *) const
+    {
+        if (traj_clear)
+            launch_obstacles(h, s, B, G, K, Lt, wrap, t0 + t + 1, 1, x, obs, INFINITY, nullptr, nullptr, 0, traj_clear + t, (size_t)T, 1);
+        return MPC_OK;
+    }
+};
+extern "C" int mpc_closed_loop_obstacles_event(mpc_handle *h, int B, int T, int shift, const double *w, double thr, int max_hold, int G,
+                                               int K, int Lt, int wrap, int t0, const double *obs, double reach, double clear_thr,
+                                               int watch, double *x, const double *cl, int32_t *cl_index, double *U, double *lambda,
+                                               int32_t *held, int32_t *sel_plan, double *table, const double *disturbance,
+                                               double *traj_x, double *traj_u, int32_t *traj_sel, double *traj_clear,
+                                               uint8_t *traj_why, uint8_t *solved, int32_t *solve_count, int32_t *fail_count,
+                                               double *stats, void *stream, const mpc_track *trk)
+{
+    const char *who_ = "mpc_closed_loop_obstacles_event";
+    const std::string who(who_);
+    int rc = check_trigger_args(who_, w, thr, max_hold, held); if (rc) return rc;
+    if (T < 0) return fail(MPC_E_ARG, who + ": negative T");
+    rc = check_obstacle_args(who, B, G, K, Lt, t0, "t0", obs); if (rc) return rc;
+    rc = check_obstacle_rule(who, reach, clear_thr, watch); if (rc) return rc;
+    if (!sel_plan) return fail(MPC_E_ARG, who + ": null sel_plan");
+    if (!h) return fail(MPC_E_ARG, who + ": null handle");
+    rc = check_max_hold(h, who_, max_hold); if (rc) return rc;
+    rc = check_common(h, B, who_); if (rc) return rc;
+    rc = check_obstacle_window(who, t0, (long long)T + h->cfg.N, "t0"); if (rc) return rc;   // up to the last step's window
+    if (trk) { rc = check_track(h, trk, who_); if (rc) return rc; }
+    rc = check_tables(h, B, who_, READS_ALL, true); if (rc) return rc;
+    rc = check_rewritten_table(h, obstacle_discs(h) ? TAB_DISCS : TAB_FIELDS, table, B, who); if (rc) return rc;
+    rc = check_rate_rows(h, B, who); if (rc) return rc;
+    if (B == 0 || T == 0) return MPC_OK;
+    // every refusal stands before the first allocation (closed_loop_event_impl repeats the ones it shares)
+    if (!x || !cl || !U || (h->dc.m && !lambda) || (trk && !cl_index)) return fail(MPC_E_ARG, who + ": null buffer");
+    rc = reserve_traffic(h, B); if (rc) return rc;
+    rc = reserve_obstacle_rule(h, B); if (rc) return rc;
+    const ObstacleEventHook hook{h, (hipStream_t)stream, stream, B, T, shift, G, K, Lt, wrap, t0, obs, reach, clear_thr, watch,
+                                 x, U, held, sel_plan, table, traj_sel, traj_clear, traj_why};
+    return closed_loop_event_impl(who_, h, B, T, shift, w, thr, max_hold, x, cl, cl_index, U, lambda, held, disturbance, traj_x, traj_u,
+                                  solved, solve_count, fail_count, stats, stream, trk, cl_index, nullptr, hook);
 }
 
 extern "C" int mpc_last_speculation(mpc_handle *h, int64_t *issued, int64_t *used)

@@ -48,6 +48,33 @@ __global__ void __launch_bounds__(64) simulate_kernel(const DevCfg c_, int B, in
     }
 }
 
+// mpc_rollout_held: simulate_kernel with a start stage per agent -- X[B][N][nx], the states agent a reaches by going on
+// applying its plan U[a] of N stages from stage k = min(max(held[a], 0), N - 1): stage j applies u_{min(k + j, N - 1)},
+// the last input repeated into the tail.  The index rule is the in-place shift of trigger_kernel (plan_shift), the stage
+// is simulate_kernel's, operation for operation: the result is mpc_rollout on the shifted plan bit for bit.
+template <int MODEL, bool PA = false, class... PT>
+__global__ void __launch_bounds__(64) simulate_held_kernel(const DevCfg c_, int B, const double *__restrict__ x0,
+                                                           const double *__restrict__ U, const int *__restrict__ held,
+                                                           double *__restrict__ X, PT... pt)
+{
+    constexpr int NX = ModelDim<MODEL>::NX;
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= B) return;
+    DevCfg cm_;
+    if constexpr (PA) { cm_ = c_; agent_cfg(cm_, pt..., a); }
+    const DevCfg &c = PA ? cm_ : c_;
+    const int N = c_.N, k = max(0, min(held[a], N - 1));
+    double xv[NX];
+    for (int i = 0; i < NX; i++) xv[i] = x0[(size_t)a * NX + i];
+    for (int n = 0; n < N; n++) {
+        const int src = min(n + k, N - 1);
+        StageInput<MODEL> s;
+        prep_input(c, U[((size_t)a * N + src) * 2], U[((size_t)a * N + src) * 2 + 1], s);
+        stage_forward<MODEL>(c, s, xv);
+        for (int i = 0; i < NX; i++) X[((size_t)a * N + n) * NX + i] = xv[i];
+    }
+}
+
 // placement of the nearest-point grid of every centerline row (one wave per row): the box of the
 // candidate points grown by 25 mean spacings, cells of half a spacing (larger if that takes more than
 // GRID_CELLS cells).  A row the grid cannot describe (non-finite or coincident points, S - 1 > 65535)

@@ -124,6 +124,16 @@ MPC_DEV double add_rounded(double a, double b)
 }
 MPC_DEV bool trigger_fire(int held, int max_hold, double dev2, double thr2) { return held < 0 || held >= max_hold || !(dev2 < thr2); }
 
+// the in-place shift of a plan Ua [N][2] by the hd > 0 stages that have been applied, the last stage repeated into the tail
+MPC_DEV void plan_shift(double *Ua, int N, int hd)
+{
+    const int k = min(hd, N - 1);
+    for (int j = 0; j < N; j++) {           // ascending: a stage is read before it is overwritten
+        const int src = min(j + k, N - 1);
+        Ua[2 * j] = Ua[2 * src]; Ua[2 * j + 1] = Ua[2 * src + 1];
+    }
+}
+
 // mpc_trigger_eval, and step 1 - 2 of mpc_closed_loop_event (U != null: a firing agent's plan is shifted in place by
 // the `held` stages it has applied, the last stage repeated into the tail -- `held` applications of plant_step_kernel's
 // one-stage shift; force != 0: every agent fires, the nominal states are not known)
@@ -140,14 +150,18 @@ __global__ void __launch_bounds__(64) trigger_kernel(int B, int N, const double 
     const bool f = force != 0 || trigger_fire(hd, max_hold, d2, thr2);
     if (dev2) dev2[a] = d2;
     fire[a] = f ? 1 : 0;
-    if (U && f && hd > 0) {
-        double *Ua = U + (size_t)a * 2 * N;
-        const int k = min(hd, N - 1);
-        for (int j = 0; j < N; j++) {           // ascending: a stage is read before it is overwritten
-            const int src = min(j + k, N - 1);
-            Ua[2 * j] = Ua[2 * src]; Ua[2 * j + 1] = Ua[2 * src + 1];
-        }
-    }
+    if (U && f && hd > 0) plan_shift(U + (size_t)a * 2 * N, N, hd);
+}
+
+// step 4 of mpc_closed_loop_obstacles_event: the trigger's shift as a launch of its own, behind the obstacle rule -- the
+// plans of the agents that fire for any reason are shifted by the stages they have applied (one thread per agent)
+__global__ void __launch_bounds__(64) plan_shift_kernel(int B, int N, const int *__restrict__ held, const int *__restrict__ fire,
+                                                        double *__restrict__ U)
+{
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= B) return;
+    const int hd = held[a];
+    if (fire[a] != 0 && hd > 0) plan_shift(U + (size_t)a * 2 * N, N, hd);
 }
 
 // plant's and controller's parameters of agent a: rows plant_index[a] and index[a] of the bound table

@@ -214,6 +214,14 @@ struct mpc_handle {
         double *X = nullptr;
         int32_t *opp = nullptr;
     } tr;
+    // mpc_closed_loop_obstacles_event: the selection over the stages every plan still holds, sel_chk [cap][MPC_NDISC] and
+    // clear_chk [cap][MPC_NDISC] (what mpc_obstacle_trigger's caller passes)
+    struct ObstacleRuleBufs {
+        char *base = nullptr;
+        int cap = 0;
+        double *clear_chk = nullptr;
+        int32_t *sel_chk = nullptr;
+    } orule;
 };
 
 static int stage_m(const mpc_config *c)
@@ -482,6 +490,22 @@ static int reserve_traffic(mpc_handle *h, int B)
     if (hipMalloc((void **)&base, bytes) != hipSuccess) return fail(MPC_E_ALLOC, "traffic-loop hipMalloc failed");
     t.base = base; t.cap = (int)Bp;
     t.X = (double *)base; t.opp = (int32_t *)(t.X + nd * Bp);
+    HIPCHK(hipMemset(base, 0, bytes));
+    return MPC_OK;
+}
+// buffers of the obstacle rule for up to B agents (see mpc_handle::ObstacleRuleBufs)
+static int reserve_obstacle_rule(mpc_handle *h, int B)
+{
+    mpc_handle::ObstacleRuleBufs &o = h->orule;
+    if (B <= o.cap) return MPC_OK;
+    HIPCHK(hipSetDevice(h->device));
+    if (o.base) { HIPCHK(hipFree(o.base)); o.base = nullptr; o.cap = 0; }
+    const size_t Bp = ((size_t)B + 63) & ~(size_t)63;
+    const size_t bytes = (8 + 4) * MPC_NDISC * Bp;
+    char *base = nullptr;
+    if (hipMalloc((void **)&base, bytes) != hipSuccess) return fail(MPC_E_ALLOC, "obstacle-rule hipMalloc failed");
+    o.base = base; o.cap = (int)Bp;
+    o.clear_chk = (double *)base; o.sel_chk = (int32_t *)(o.clear_chk + MPC_NDISC * Bp);
     HIPCHK(hipMemset(base, 0, bytes));
     return MPC_OK;
 }

@@ -29,13 +29,19 @@ template <int W> MPC_DEV constexpr int obstacle_key() { return W == 3 ? 2 : 4; }
 // the agent's Kp lanes.  No atomics; a min of doubles does not depend on the order, so chunking changes no bit.
 // Outputs as in opponents_kernel, sel holding the track's index WITHIN the scene: sel [B][NDISC] (-1: none); sel_rec, the
 // same words at sel_rec[b * rec_stride + j]; clear at clear[b * clear_stride + j] for j < clear_slots (+inf: none).
-template <int W>
+// HELD (mpc_obstacle_trigger; hd = held [B]): agent b folds its first held_stages(held[b], Nst) stages alone -- the stages
+// a plan of Nst of which held[b] have been applied still holds, as mpc_rollout_held lays them out; the tail that repeats
+// the last input is staged like every stage (X has Nst stages) and never compared.  Everything else is the same code.
+// (The count is re-read from held per chunk and pass; 16 counts kept in registers cost 64 vector registers.)
+MPC_DEV int held_stages(int held, int N) { return N - max(0, min(held, N - 1)); }
+template <int W, bool HELD = false, class... HD>
 __global__ void __launch_bounds__(TR_BLK) obstacles_kernel(int B, int G, int K, int Kp, int spw, int Lt, int wrap, int ti, int Nst,
                                                            int nx, const double *__restrict__ X, const double *__restrict__ obs,
                                                            double reach2, int *__restrict__ sel, int *__restrict__ sel_rec,
                                                            size_t rec_stride, double *__restrict__ clear, size_t clear_stride,
-                                                           int clear_slots)
+                                                           int clear_slots, HD... hd)
 {
+    static_assert(sizeof...(HD) == (HELD ? 1 : 0), "the held form takes held [B], the plain form nothing");
     __shared__ double s_ox[OB_KC * OB_LD], s_oy[OB_KC * OB_LD], s_r2[OB_KC * OB_LD], s_x[OB_KC * OB_LD], s_y[OB_KC * OB_LD];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const size_t b0 = (size_t)blockIdx.x * spw * G;                 // first agent of the workgroup (a scene's first)
@@ -77,7 +83,12 @@ __global__ void __launch_bounds__(TR_BLK) obstacles_kernel(int B, int G, int K, 
                 const int ar = pair_on ? a : 0, orr = pair_on ? (a / G) * K + ol : 0;   // what the lane reads (in range whatever it is)
                 double cm = c[pass];
                 bool bd = false;
-                for (int k = 0; k < kc; k++) {
+                int kend = kc;
+                if constexpr (HELD) {                                // the stages the lane's agent still compares (a cached
+                    const int *__restrict__ held = (hd, ...);        // load per chunk: no count is kept in registers)
+                    kend = min(kc, (a < A ? held_stages(held[b0 + a], Nst) : 0) - k0);   // (<= 0 behind its last stage)
+                }
+                for (int k = 0; k < kend; k++) {
                     const double r2 = s_r2[k * OB_LD + orr];
                     if (r2 < 0.0) continue;                          // absent at this stage (a NaN radius is present, and takes the pair out)
                     const double g = traffic_g(s_x[k * OB_LD + ar], s_y[k * OB_LD + ar], s_ox[k * OB_LD + orr], s_oy[k * OB_LD + orr], r2);
@@ -125,18 +136,28 @@ __global__ void __launch_bounds__(TR_BLK) obstacles_kernel(int B, int G, int K, 
 // (ti + k) of track sel[b][j] of agent b's scene; W zeros where sel[b][j] is outside [0, K) and where the sample is
 // absent (its other words are not read).  One thread per (agent, stage, slot); every word written is a copy of an input
 // word or zero.
-template <int W>
+// MASKED (step 7 of mpc_closed_loop_obstacles_event; mk = (mask [B], sel_plan [B][NDISC])): the rows of the agents with
+// mask[b] != 0 alone are written -- a held agent's row stays the one its plan was solved on -- and for those agents
+// sel_plan[b] <- sel[b] (the thread of stage 0 writes it): the tracks the plan about to be solved is solved against.
+struct RowMask { const int *mask; int *sel_plan; };
+template <int W, bool MASKED = false, class... MK>
 __global__ void __launch_bounds__(256) rows_from_obstacles_kernel(int B, int N, int G, int K, int Lt, int wrap, int ti,
                                                                   const double *__restrict__ obs, const int *__restrict__ sel,
-                                                                  double *__restrict__ table)
+                                                                  double *__restrict__ table, MK... mk)
 {
     static_assert(NDISC == NFIELD, "one sel [B][2] serves the disc and the field table");
+    static_assert(sizeof...(MK) == (MASKED ? 1 : 0), "the masked form takes a RowMask, the plain form nothing");
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= (size_t)B * N * NDISC) return;
     const int j = (int)(t % NDISC);
     const size_t bk = t / NDISC;
     const int k = (int)(bk % N), b = (int)(bk / N);
     const int o = sel[(size_t)b * NDISC + j];
+    if constexpr (MASKED) {
+        const RowMask m = (mk, ...);
+        if (m.mask[b] == 0) return;
+        if (k == 0) m.sel_plan[(size_t)b * NDISC + j] = o;
+    }
     double *out = table + t * W;
     const double *__restrict__ p = nullptr;
     if (o >= 0 && o < K) {
@@ -145,6 +166,35 @@ __global__ void __launch_bounds__(256) rows_from_obstacles_kernel(int B, int N, 
     }
 #pragma unroll
     for (int i = 0; i < W; i++) out[i] = p ? p[i] : 0.0;
+}
+
+// The obstacle rule of mpc_obstacle_trigger on the held-window selection (sel_chk, clear_chk [B][NDISC]; one thread per
+// agent): why[b] bit 0 = fire_in[b] != 0 (null: 0); for held[b] > 0, bit 1 = watch & 1 and !(clear_chk[b][0] >= clear_thr)
+// -- +inf, nothing in reach, never fires --, bit 2 = watch & 2 and some sel_chk[b][j] >= 0 is not a member of the SET
+// sel_plan[b] (a change of order is no new obstacle).  fire_out[b] = why[b] != 0; why at why[b * why_stride] (null ok).
+__global__ void __launch_bounds__(64) obstacle_rule_kernel(int B, const int *__restrict__ held, const int *__restrict__ sel_chk,
+                                                           const double *__restrict__ clear_chk, const int *__restrict__ sel_plan,
+                                                           double clear_thr, int watch, const int *fire_in,
+                                                           int *fire_out, uint8_t *__restrict__ why, size_t why_stride)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int w = fire_in && fire_in[b] != 0 ? 1 : 0;
+    if (held[b] > 0) {
+        if ((watch & 1) && !(clear_chk[(size_t)b * NDISC] >= clear_thr)) w |= 2;
+        if (watch & 2) {
+#pragma unroll
+            for (int j = 0; j < NDISC; j++) {
+                const int o = sel_chk[(size_t)b * NDISC + j];
+                bool known = o < 0;
+#pragma unroll
+                for (int i = 0; i < NDISC; i++) known = known || sel_plan[(size_t)b * NDISC + i] == o;
+                if (!known) w |= 4;
+            }
+        }
+    }
+    fire_out[b] = w != 0;
+    if (why) why[(size_t)b * why_stride] = (uint8_t)w;
 }
 
 // mpc_roads_from_script: table[b][k] = the NROAD words of sample (ti + k) of script row sidx[b] -- clamped to the last

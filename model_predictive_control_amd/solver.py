@@ -42,6 +42,13 @@ TrafficLoopResult = collections.namedtuple(
 ObstacleLoopResult = collections.namedtuple(
     "ObstacleLoopResult", "x U lam traj_x traj_u failures stats traj_sel traj_clear table cl_index")
 
+# what BatchedMPC.closed_loop_obstacles_event returns: the fields of ObstacleLoopResult (U: the plans as last solved, not
+# shifted by the stages applied since), then solved [B, T] uint8, solve_count [B], held [B] int32 (stages of the plan
+# already applied), sel_plan [B, NDISC] int32 (the obstacles every agent's plan was solved against) and traj_why [B, T]
+# uint8 (bit 0: the car trigger -- deviation, hold limit, no plan --, bit 1: clearance, bit 2: a new obstacle)
+ObstacleEventLoopResult = collections.namedtuple(
+    "ObstacleEventLoopResult", ObstacleLoopResult._fields + ("solved", "solve_count", "held", "sel_plan", "traj_why"))
+
 
 class Track:
     """A table of track windows (BatchedMPC.track_windows): `win` [K * R, 2S], the window tensor -- an ordinary
@@ -972,6 +979,90 @@ class BatchedMPC:
             _ptr(table), _ptr(tx), _ptr(tu), _ptr(tsel), _ptr(tclear), _ptr(fails), _ptr(stats), self._stream(),
             C.byref(trk._c) if trk is not None else None))
         return ObstacleLoopResult(x, U, lam, tx, tu, fails, stats, tsel, tclear, table, ci)
+
+    # ------------------------------------------------------------------ event-triggered holding among scripted obstacles
+    def rollout_held(self, x, U, held):
+        """mpc_rollout_held: X [B, N, nx], the states an agent reaches by going on applying the plan U [B, 2N] of which it
+        has applied held[b] stages (int32 [B]) -- stage j applies u_{min(k + j, N - 1)} with k = min(max(held[b], 0), N - 1),
+        the last input repeated into the tail.  Bit for bit rollout(x, U shifted by k stages); held <= 0 is rollout(x, U)."""
+        self._free()
+        B = x.shape[0]
+        self._chk(x, (B, self.nx), "x"); self._chk(U, (B, self.n), "U")
+        self._chk(held, (B,), "held", torch.int32)
+        X = self._empty(B, self.N, self.nx)
+        _lib.check(self.lib.mpc_rollout_held(self._h, B, _ptr(x), _ptr(U), _ptr(held), _ptr(X), self._stream()))
+        return X
+
+    def obstacle_trigger(self, X, held, sel_plan, G, obs, ti=0, reach=float("inf"), clear_thr=0.0, watch=3, fire=None,
+                         wrap=False):
+        """mpc_obstacle_trigger: the obstacle rule of the event-triggered loop, pure.  X [B, N, nx] is rollout_held(x, U,
+        held): stage j of what agent b will go on applying meets sample ti + j of the scripts.  The selection of
+        obstacles_select runs over the N - k stages the held plan still has (k = min(max(held[b], 0), N - 1); the
+        repeated tail is not looked at) and gives sel_chk [B, NDISC] int32 and clear_chk [B, NDISC].  why [B] uint8: bit 0
+        = fire[b] != 0 (the caller's, e.g. trigger_eval's; None: zeros); for agents with held > 0, bit 1 (watch & 1) =
+        not clear_chk[b, 0] >= clear_thr, bit 2 (watch & 2) = some sel_chk[b, j] >= 0 is not in the set
+        sel_plan[b] ([B, NDISC] int32: the obstacles the held plan was solved against, -1: none).  clear_thr is in the
+        units of the clearance: d^2 - r^2 on an engine of CONSTR_DISCS -- a solved plan rides 0 to within alm_delta, so a
+        useful threshold is slightly negative --, a squared distance on every other.  Returns (fire_out = why != 0 as
+        int32 [B], why, sel_chk, clear_chk)."""
+        X, B, Nst = self._plans(X)
+        self._chk(X, (B, self.N, self.nx), "X")
+        G, K, Lt, wrap, ti, reach = self._obstacle_args(B, G, obs, wrap, ti, self.N, reach)
+        clear_thr, watch = float(clear_thr), int(watch)      # (the library refuses clear_thr > reach^2 or NaN, watch outside [0, 3])
+        self._chk(held, (B,), "held", torch.int32)
+        self._chk(sel_plan, (B, _lib.NDISC), "sel_plan", torch.int32)
+        if fire is not None:
+            self._chk(fire, (B,), "fire", torch.int32)
+        sel = torch.full((B, _lib.NDISC), -1, dtype=torch.int32, device=self.device)
+        clear = torch.full((B, _lib.NDISC), float("inf"), dtype=torch.float64, device=self.device)
+        why = torch.zeros(B, dtype=torch.uint8, device=self.device)
+        out = torch.zeros(B, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.mpc_obstacle_trigger(self._h, B, G, K, Lt, wrap, ti, _ptr(X), _ptr(obs), reach, _ptr(held),
+                                                 _ptr(sel_plan), clear_thr, watch, _ptr(fire), _ptr(sel), _ptr(clear), _ptr(why),
+                                                 _ptr(out), self._stream()))
+        return out, why, sel, clear
+
+    def closed_loop_obstacles_event(self, x, centerline, U, T, G, obs, w, thr, max_hold, reach=float("inf"), clear_thr=0.0,
+                                    watch=3, t0=0, wrap=False, held=None, sel_plan=None, lam=None, cl_index=None, shift=False,
+                                    table=None, track_obj=None, disturbance=None, stats=None):
+        """mpc_closed_loop_obstacles_event: closed_loop_obstacles in which an agent keeps applying the plan it holds, as in
+        closed_loop_event, and re-plans when the car trigger fires (w, thr, max_hold), when the plan it would go on applying
+        comes closer than clear_thr to a scripted obstacle (watch & 1) or when an obstacle that the plan was not solved
+        against enters its selection (watch & 2) -- obstacle_trigger on rollout_held, stage held + k of the held plan
+        meeting sample t0 + t + 1 + k.  Only the agents that re-plan get new rows of the bound disc / field table.  held
+        [B] int32 (None: -1) and sel_plan [B, NDISC] int32 (None: -1) continue a loop together with the U / lam / stats /
+        cl_index of an earlier result and t0 + T.  The other arguments are closed_loop_obstacles' and closed_loop_event's.
+        Returns an ObstacleEventLoopResult (copies; the table is the bound one)."""
+        B, T, t0 = self._loop_entry(x, U), int(T), int(t0)
+        thr, max_hold = self._trigger_args(thr, max_hold)
+        if T < 0:
+            raise ValueError("T must be >= 0")
+        G, K, Lt, wrap, t0, reach = self._obstacle_args(B, G, obs, wrap, t0, T + self.N, reach)
+        clear_thr, watch = float(clear_thr), int(watch)      # (the library refuses clear_thr > reach^2 or NaN, watch outside [0, 3])
+        kind = "discs" if int(self.cfg.constr_mode) == _lib.CONSTR_DISCS else "fields"
+        table = self._loop_table(kind, B, table, identity_index=True)
+        trk = None
+        if track_obj is not None:
+            trk = self._track(track_obj)
+            if centerline is not None and centerline is not trk.win:
+                raise ValueError("with track_obj the centerline table is track_obj.win (pass centerline=None)")
+            if cl_index is None:
+                raise ValueError("cl_index: the rows to start from are required with track_obj (track_locate)")
+            centerline = trk.win
+        cl = self._centerline(centerline, cl_index, B)
+        x, U, lam, held, tx, tu, solved, count, fails, stats = self._event_loop_state(B, T, x, U, lam, held, disturbance, stats)
+        sel_plan = torch.full((B, _lib.NDISC), -1, dtype=torch.int32, device=self.device) if sel_plan is None else sel_plan.clone()
+        self._chk(sel_plan, (B, _lib.NDISC), "sel_plan", torch.int32)
+        ci = None if cl_index is None else cl_index.clone()
+        tsel = torch.full((B, T, _lib.NDISC), -1, dtype=torch.int32, device=self.device)
+        tclear = torch.full((B, T), float("inf"), dtype=torch.float64, device=self.device)
+        twhy = torch.zeros(B, T, dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.mpc_closed_loop_obstacles_event(
+            self._h, B, T, int(bool(shift)), self._weights(w), thr, max_hold, G, K, Lt, wrap, t0, _ptr(obs), reach, clear_thr, watch,
+            _ptr(x), _ptr(cl), _ptr(ci), _ptr(U), _ptr(lam), _ptr(held), _ptr(sel_plan), _ptr(table), _ptr(disturbance), _ptr(tx),
+            _ptr(tu), _ptr(tsel), _ptr(tclear), _ptr(twhy), _ptr(solved), _ptr(count), _ptr(fails), _ptr(stats), self._stream(),
+            C.byref(trk._c) if trk is not None else None))
+        return ObstacleEventLoopResult(x, U, lam, tx, tu, fails, stats, tsel, tclear, table, ci, solved, count, held, sel_plan, twhy)
 
     def lane_payoff(self, ego, cars, ncars, params):
         """f-3: out[B, 2, 4] = target lane 1, 2 -> [total, safety, velocity, comfort] (game_theory.py:115-244)."""
