@@ -29,7 +29,7 @@ _default_hw_queues()
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPC_LIB_PATH", os.path.join(_HERE, "libmpc_hip.so"))  # override: dev experiments
-_SRC = [os.path.join(_HERE, "csrc", f) for f in ("mpc_api.hip", "mpc_handle.hpp", "mpc_launch.hpp", "mpc_rounds.hpp",
+_SRC = [os.path.join(_HERE, "csrc", f) for f in ("mpc_api.hip", "mpc_arena.hpp", "mpc_handle.hpp", "mpc_launch.hpp", "mpc_rounds.hpp",
                                                   "mpc_aux.hpp", "mpc_eval.hpp", "mpc_solver.hpp", "mpc_device.hpp",
                                                   "mpc_game.hpp", "mpc_solo.hpp", "mpc_event.hpp", "mpc_track.hpp",
  "mpc_obstacles.hpp", "mpc_traffic.hpp")]

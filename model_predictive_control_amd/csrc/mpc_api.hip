@@ -147,7 +147,7 @@ extern "C" int mpc_create(const mpc_config *cfg, int device, mpc_handle **out)
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) h->num_cus = cus;
     }
-    if (e == hipSuccess) e = hipHostMalloc((void **)&h->host_counts, 512, hipHostMallocDefault);
+    if (e == hipSuccess) e = h->pinned_mem.alloc(sizeof(PinnedCounts));
     if (e != hipSuccess) { delete h; return fail(MPC_E_HIP, std::string("mpc_create: ") + hipGetErrorString(e)); }
     read_switches(h);
     *out = h;
@@ -163,24 +163,13 @@ extern "C" int mpc_destroy(mpc_handle *h)
         h->worker.join();
     }
     (void)hipSetDevice(h->device);
-    if (h->arena) (void)hipFree(h->arena);
-    if (h->stage) (void)hipFree(h->stage);
-    if (h->ev.base) (void)hipFree(h->ev.base);
-    if (h->ev.xhat) (void)hipFree(h->ev.xhat);
-    if (h->tr.base) (void)hipFree(h->tr.base);
-    if (h->orule.base) (void)hipFree(h->orule.base);
-    if (h->own_ptab) (void)hipFree(h->own_ptab);
-    if (h->cl_gmeta) (void)hipFree(h->cl_gmeta);
-    if (h->cl_gxy) (void)hipFree(h->cl_gxy);
-    if (h->cl_gcells) (void)hipFree(h->cl_gcells);
-    if (h->host_counts) (void)hipHostFree(h->host_counts);
     if (h->syncev) (void)hipEventDestroy(h->syncev);
     for (auto ev : h->ev_pool) (void)hipEventDestroy(ev);
     for (int g = 0; g < MPC_MAX_GROUPS; g++) if (h->gstream[g]) (void)hipStreamDestroy(h->gstream[g]);
     for (int g = 0; g <= MPC_MAX_GROUPS; g++) if (h->gevent[g]) (void)hipEventDestroy(h->gevent[g]);
     for (int b = 0; b < 2; b++) for (int g = 0; g < MPC_MAX_GROUPS; g++) if (h->pollev[b][g]) (void)hipEventDestroy(h->pollev[b][g]);
     for (int b = 0; b < 2; b++) for (int g = 0; g < MPC_MAX_GROUPS; g++) if (h->soloev[g][b]) (void)hipEventDestroy(h->soloev[g][b]);
-    delete h;
+    delete h;   // (and with it every DevBuf: the handle's memory)
     return MPC_OK;
 }
 
@@ -191,47 +180,18 @@ extern "C" int mpc_centerline_blocks(mpc_handle *h, const double *cl, int C, voi
     // the grid costs 256 KB per centerline row: a table with one row per agent keeps the full scan
     if (C == 0 || !cl || C > MPC_GRID_MAX_ROWS) return MPC_OK;
     const DevCfg &c = h->dc;
-    if (C > h->cl_grid_cap) {
-        if (h->cl_gmeta) { HIPCHK(hipFree(h->cl_gmeta)); h->cl_gmeta = nullptr; }
-        if (h->cl_gxy) { HIPCHK(hipFree(h->cl_gxy)); h->cl_gxy = nullptr; }
-        if (h->cl_gcells) { HIPCHK(hipFree(h->cl_gcells)); h->cl_gcells = nullptr; }
-        h->cl_grid_cap = 0;
-        if (hipMalloc((void **)&h->cl_gmeta, sizeof(double) * GRID_META * (size_t)C) != hipSuccess ||
-            hipMalloc((void **)&h->cl_gxy, sizeof(double) * 2 * (size_t)c.S * (size_t)C) != hipSuccess ||
-            hipMalloc((void **)&h->cl_gcells, sizeof(unsigned) * (size_t)GRID_CELLS * (size_t)C) != hipSuccess)
-            return fail(MPC_E_ALLOC, "centerline grid hipMalloc failed");
-        h->cl_grid_cap = C;
+    GridBufs &g = h->grid;
+    if (C > g.cap) {   // (not zero-filled: the two kernels write all of it)
+        g.cap = 0;
+        rc = carve(g.arena, h->device, false, "centerline grid hipMalloc failed", [&](Carver &a) { grid_layout(a, g, (size_t)c.S, (size_t)C); });
+        if (rc) return rc;
+        g.cap = C;
     }
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(cl_grid_meta_kernel, dim3((unsigned)C), dim3(64), 0, s, c, cl, C, h->cl_gmeta, h->cl_gxy);
-    hipLaunchKernelGGL(cl_grid_cells_kernel, dim3(GRID_CELLS / 256, C), dim3(256), 0, s, c, cl, C, h->cl_gmeta, h->cl_gcells);
+    hipLaunchKernelGGL(cl_grid_meta_kernel, dim3((unsigned)C), dim3(64), 0, s, c, cl, C, g.gmeta, g.gxy);
+    hipLaunchKernelGGL(cl_grid_cells_kernel, dim3(GRID_CELLS / 256, C), dim3(256), 0, s, c, cl, C, g.gmeta, g.gcells);
     HIPCHK(hipGetLastError());
     h->cl_grid_for = cl;
-    return MPC_OK;
-}
-
-// the handle's own one-row parameter, box, rate and field tables and an index of B zeros (see mpc_handle::own_ptab)
-static int reserve_own_tables(mpc_handle *h, int B, const char *who)
-{
-    if (B <= h->own_cap) return MPC_OK;
-    if (h->own_ptab) { HIPCHK(hipFree(h->own_ptab)); h->own_ptab = h->own_btab = h->own_rtab = h->own_ftab = nullptr; h->own_pidx = nullptr; h->own_cap = 0; }
-    const size_t cap = ((size_t)B + 63) & ~(size_t)63;
-    constexpr int NS = MPC_NPARAM + 1 + MPC_NBOUND + MPC_NRATE;   // the three of fixed width, then the field row of the handle's horizon
-    const size_t ND = (size_t)NS + MPC_FIELD_ROW(h->cfg.N);
-    char *base = nullptr;
-    if (hipMalloc((void **)&base, sizeof(double) * ND + sizeof(int32_t) * cap) != hipSuccess)
-        return fail(MPC_E_ALLOC, std::string(who) + ": hipMalloc failed");
-    std::vector<double> ownv(ND, 0.0);
-    double *own = ownv.data();
-    (void)mpc_default_params(&h->cfg, own);
-    (void)mpc_default_bounds(&h->cfg, own + MPC_NPARAM + 1);
-    (void)mpc_default_rates(&h->cfg, own + MPC_NPARAM + 1 + MPC_NBOUND);
-    (void)mpc_default_fields(&h->cfg, own + NS);
-    h->own_ptab = (double *)base; h->own_btab = h->own_ptab + MPC_NPARAM + 1; h->own_rtab = h->own_btab + MPC_NBOUND;
-    h->own_ftab = h->own_ptab + NS;
-    h->own_pidx = (int32_t *)(base + sizeof(double) * ND); h->own_cap = (int)cap;
-    HIPCHK(hipMemcpy(base, own, sizeof(double) * ND, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(h->own_pidx, 0, sizeof(int32_t) * cap));
     return MPC_OK;
 }
 
@@ -432,7 +392,7 @@ static int plant_loop(mpc_handle *h, int B, int T, int shift, double *x, const d
 {
     // the solves' statistics: into the caller's buffer, or the handle's stage buffer
     int rc = stats ? MPC_OK : reserve_stage(h, sizeof(double) * 8 * (size_t)B); if (rc) return rc;
-    double *st = stats ? stats : h->stage;
+    double *st = stats ? stats : (double *)h->stage.p;
     hipStream_t s = (hipStream_t)stream;
     for (int t = 0; t < T; t++) {
         rc = before(t); if (rc) return rc;
@@ -781,7 +741,7 @@ static int solve_active_impl(mpc_handle *h, int B, const int32_t *active, const 
 {
     int rc = reserve_event(h, B); if (rc) return rc;
     const DevCfg &c = h->dc;
-    mpc_handle::EventBufs &e = h->ev;
+    EventBufs &e = h->ev;
     const dim3 gblk = grid_for(B, EV_BLK), grows = grid_for(B, EV_BLK / 64);
     hipLaunchKernelGGL(active_count_kernel, gblk, dim3(EV_BLK), 0, s, B, active, e.blk);
     hipLaunchKernelGGL(active_list_kernel, gblk, dim3(EV_BLK), 0, s, B, active, e.blk, e.list, e.count);
@@ -796,7 +756,7 @@ static int solve_active_impl(mpc_handle *h, int B, const int32_t *active, const 
     for (int k = TAB_BOX; k < TAB_KINDS; k++)   // (the parameter rows ride in the gather above)
         if (h->tab[k].table)
             hipLaunchKernelGGL(active_index_kernel, gblk, dim3(EV_BLK), 0, s, e.list, e.count, h->tab[k].idx, e.rows[k]);
-    int *cnt = (int *)((char *)h->host_counts + 384);   // pinned (see host_counts)
+    int *cnt = &h->pinned().n_active;
     HIPCHK(hipMemcpyAsync(cnt, e.count, sizeof(int), hipMemcpyDeviceToHost, s));
     rc = bounded_sync(h, s, "mpc_solve_active"); if (rc) return rc;
     const int nA = *cnt;
@@ -981,7 +941,7 @@ static int closed_loop_event_impl(const char *who_, mpc_handle *h, int B, int T,
     rc = reserve_event(h, B); if (rc) return rc;
     bool fresh = false;
     rc = reserve_xhat(h, B, &fresh); if (rc) return rc;
-    mpc_handle::EventBufs &e = h->ev;
+    EventBufs &e = h->ev;
     hipStream_t s = (hipStream_t)stream;
     double *st = stats ? stats : e.stats_own;
     const TrigW tw = trigger_weights(h, w);
@@ -1089,7 +1049,7 @@ static int closed_loop_traffic_impl(const std::string &who, TableKind kind, mpc_
     if (!x || !cl || !U || (h->dc.m && !lambda)) return fail(MPC_E_ARG, who + ": null buffer");
     rc = reserve_traffic(h, B); if (rc) return rc;
     const int N = h->dc.N;
-    mpc_handle::TrafficBufs &tr = h->tr;
+    TrafficBufs &tr = h->tr;
     hipStream_t s = (hipStream_t)stream;
     const auto before = [&](int t) -> int {
         const int rr = mpc_rollout(h, B, N, x, U, tr.X, stream); if (rr) return rr;
@@ -1295,7 +1255,7 @@ extern "C" int mpc_closed_loop_obstacles(mpc_handle *h, int B, int T, int shift,
     if (!x || !cl || !U || (h->dc.m && !lambda) || (trk && !cl_index)) return fail(MPC_E_ARG, who + ": null buffer");
     rc = reserve_traffic(h, B); if (rc) return rc;
     const int N = h->dc.N;
-    mpc_handle::TrafficBufs &tr = h->tr;
+    TrafficBufs &tr = h->tr;
     hipStream_t s = (hipStream_t)stream;
     const auto before = [&](int t) -> int {
         const int ti = t0 + t + 1;   // the script's time of step t (and in `after`)
@@ -1580,7 +1540,7 @@ extern "C" int mpc_debug_records(mpc_handle *h, int B, double *host_out)
     int rc = check_common(h, B, "mpc_debug_records"); if (rc) return rc;
     if (!host_out) return fail(MPC_E_ARG, "mpc_debug_records: null buffer");
     if (B == 0) return MPC_OK;
-    if (!h->arena || B > h->ws.B) return fail(MPC_E_ARG, "mpc_debug_records: more agents than the last solve held");
+    if (!h->arena.p || B > h->ws.B) return fail(MPC_E_ARG, "mpc_debug_records: more agents than the last solve held");
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(host_out, h->ws.rec, sizeof(double) * (size_t)B * REC, hipMemcpyDeviceToHost));
     for (int a = 0; a < B; a++)

@@ -1,13 +1,12 @@
-// mpc_handle.hpp -- host side of libmpc_hip.so, part 1: the handle behind the C-ABI, its error reporting, configuration
-// check, environment switches, stream-concurrency probe, workspace, bounded waits, and the per-agent tables bound to it
-// (one BoundTable per TableKind, one batch-size check for all of them: check_tables).  Host code (plus the probe's
-// idling kernel); included by mpc_api.hip alone.
+// mpc_handle.hpp -- host side of libmpc_hip.so, part 1: the handle behind the C-ABI, its configuration check, environment
+// switches, stream-concurrency probe, the reserve_* calls that grow its memory (owner and layouts: mpc_arena.hpp), bounded
+// waits, and the per-agent tables bound to it (one BoundTable per TableKind, one batch-size check for all of them:
+// check_tables).  Host code (plus the probe's idling kernel); included by mpc_api.hip alone.
 #pragma once
-#include "../../include/mpc_hip.h"
+#include "mpc_arena.hpp"
 #include "mpc_aux.hpp"
 #include "mpc_solo.hpp"
 #include "mpc_game.hpp"
-#include "mpc_event.hpp"
 #include "mpc_traffic.hpp"
 
 #include <algorithm>
@@ -17,31 +16,13 @@
 #include <cstring>
 #include <condition_variable>
 #include <mutex>
-#include <string>
 #include <thread>
 #include <array>
 #include <vector>
 
-using namespace mpc;
-
-#define MPC_MAX_GROUPS 8
 #define MPC_GRID_MAX_ROWS 1024   // centerline rows the nearest-point grid is built for (256 KB each)
 
-static thread_local std::string g_err;
-static int fail(int code, const std::string &msg) { g_err = msg; return code; }
-
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(MPC_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
-    } while (0)
-
-// The per-agent tables a caller can bind beside the handle's shared values: parameters (mpc_set_agent_params), input
-// boxes (mpc_set_agent_bounds), constraint data (mpc_set_agent_constraints), keep-out discs (mpc_set_agent_discs) and move
-// penalties (mpc_set_agent_rates), risk fields (mpc_set_agent_fields) and road data (mpc_set_agent_roads).  The kinds are walked in this order wherever they are checked; an entry point names the kinds it reads as a mask of READS_*
-// (check_tables).
-enum TableKind { TAB_PARAMS, TAB_BOX, TAB_CONSTR, TAB_DISCS, TAB_RATES, TAB_FIELDS, TAB_ROADS, TAB_KINDS };
+// the kinds of per-agent table (TableKind: mpc_arena.hpp) an entry point reads, as a mask
 enum : unsigned { READS_PARAMS = 1u << TAB_PARAMS, READS_BOX = 1u << TAB_BOX, READS_CONSTR = 1u << TAB_CONSTR, READS_DISCS = 1u << TAB_DISCS,
                   READS_RATES = 1u << TAB_RATES, READS_FIELDS = 1u << TAB_FIELDS, READS_ROADS = 1u << TAB_ROADS, READS_ALL = (1u << TAB_KINDS) - 1 };
 // messages, doubles per row (width_per_N: per stage of the handle's horizon -- table_width)
@@ -107,24 +88,21 @@ struct mpc_handle {
     int num_cus = 256;
     int nearest_mode = 2;                 // mpc_set_nearest_blocks: 0 full scan (MPC_NEAREST_SCAN), 2 grid of index ranges (default);
                                           // a table that mpc_centerline_blocks has not prepared takes the full scan
-    // the grid of index ranges of the centerline table last handed to mpc_centerline_blocks
-    const double *cl_grid_for = nullptr;             // the table the grid was prepared for (device pointer identity), or null
-    double *cl_gmeta = nullptr, *cl_gxy = nullptr;   // grid placement [C][GRID_META], interleaved points [C][S][2]
-    unsigned *cl_gcells = nullptr;                   // [C][GRID_CELLS]
-    int cl_grid_cap = 0;                             // rows the grid buffers hold
+    const double *cl_grid_for = nullptr;             // the table `grid` was prepared for (device pointer identity), or null
+    GridBufs grid;
     int solo_all = 4096;        // a batch of at most this many agents runs in the persistent kernel from the start
                                 // (MPC_SOLO_ALL; measured: kinematic 4 096 agents 62.8 -> 53.3 ms, 8 192 worse; Pacejka 1 024)
     int solo_max = 1024;        // a group with at most this many requests per round finishes in the persistent
                                 // wave-per-agent kernel (MPC_SOLO_MAX / mpc_set_solo_max; 0 = rounds only).
                                 // Default 1024 (kinematic model, measured in round 2, also for N = 40: profiles/r02c_*),
                                 // 128 on the Pacejka model (round 4: mpc_create)
+    // Memory: every allocation is a DevBuf member of the handle (or of one of its *Bufs), freed with it; what is carved
+    // out of one follows that arena's layout function (mpc_arena.hpp)
     int Bp_alloc = 0;      // workspace capacity (agents)
-    char *arena = nullptr; // one device allocation carved into the WorkspacePA arrays
-    size_t arena_bytes = 0;
+    DevBuf arena;          // carved into the Workspace arrays (workspace_layout)
     WorkspaceHost ws{};
-    int *host_counts = nullptr; // pinned, 512 B: [2 poll windows][MPC_MAX_GROUPS][2] ints, then (byte 128) the sixteen totals of a
-                                // solve (16 x 8 B), (byte 256) the persistent kernel's counters and (byte 384) a masked solve's count -- copies into pageable memory would
-                                // block the host until the stream has drained, whatever the wall-clock bound says
+    DevBuf pinned_mem{true};
+    PinnedCounts &pinned() const { return *reinterpret_cast<PinnedCounts *>(pinned_mem.p); }
     hipEvent_t pollev[2][MPC_MAX_GROUPS] = {{nullptr}};
     hipEvent_t soloev[MPC_MAX_GROUPS][2] = {{nullptr}}; // profile mode: around a group's persistent-kernel launch
     // profiling of the last solve
@@ -185,43 +163,11 @@ struct mpc_handle {
     // K1 kernels have theirs -- together with both.  With a table bound but not the ones its kernels come with, they run
     // on these one-row tables of the handle's own values (bit for bit the shared path: tests/test_gpu_agent_params.py,
     // tests/test_gpu_agent_bounds.py) and an index of zeros; made at the first such bind, one allocation.
-    double *own_ptab = nullptr;            // [MPC_NPARAM], a pad, then own_btab, own_rtab, own_ftab and the zeros
-    double *own_btab = nullptr;            // [MPC_NBOUND]
-    double *own_rtab = nullptr;            // [MPC_NRATE] zeros: no move penalty (the field forms stand behind the rate forms alone)
-    double *own_ftab = nullptr;            // [MPC_FIELD_ROW(N)] zeros: no source (the road forms of a handle without discs stand behind the field forms alone)
-    int32_t *own_pidx = nullptr;           // [own_cap] zeros
-    int own_cap = 0;
-    // staging buffers for the standalone entry points
-    double *stage = nullptr;
-    size_t stage_bytes = 0;
-    // mpc_solve_active / mpc_closed_loop_event: the compaction's list and counters, the staging rows the active agents
-    // are solved on (one allocation, grown like the workspace), and the nominal states of the event-triggered loop
-    // (their own allocation: they are STATE between calls and must outlive a regrown staging arena)
-    struct EventBufs {
-        char *base = nullptr;
-        int cap = 0;                                   // agents the arena holds
-        int *list = nullptr, *blk = nullptr, *count = nullptr, *fire = nullptr, *cis = nullptr;
-        int *rows[TAB_KINDS] = {};                     // the active agents' rows of the bound tables, by kind
-        double *xs = nullptr, *Us = nullptr, *lams = nullptr, *stats_s = nullptr, *stats_own = nullptr;
-        double *xhat = nullptr;                        // [xhat_B][nx]
-        int xhat_B = 0;
-    } ev;
-    // mpc_closed_loop_traffic: everybody's plans X [cap][N][nx] of the step and the opponents chosen from them
-    // [cap][MPC_NDISC] (one allocation, grown like the workspace)
-    struct TrafficBufs {
-        char *base = nullptr;
-        int cap = 0;
-        double *X = nullptr;
-        int32_t *opp = nullptr;
-    } tr;
-    // mpc_closed_loop_obstacles_event: the selection over the stages every plan still holds, sel_chk [cap][MPC_NDISC] and
-    // clear_chk [cap][MPC_NDISC] (what mpc_obstacle_trigger's caller passes)
-    struct ObstacleRuleBufs {
-        char *base = nullptr;
-        int cap = 0;
-        double *clear_chk = nullptr;
-        int32_t *sel_chk = nullptr;
-    } orule;
+    OwnTables own;
+    DevBuf stage;                          // the loops' statistics when the caller passes no buffer for them
+    EventBufs ev;                          // mpc_solve_active / mpc_closed_loop_event
+    TrafficBufs tr;                        // mpc_closed_loop_traffic and the obstacle loops
+    ObstacleRuleBufs orule;                // mpc_closed_loop_obstacles_event
 };
 
 static int stage_m(const mpc_config *c)
@@ -398,129 +344,74 @@ static void read_switches(mpc_handle *h)
     h->hw_queues = hwq ? atoi(hwq) : probe_stream_concurrency(h);
 }
 
-// carve the workspace for up to B agents (agent-major rows; caller buffers are used in place)
+// the workspace for up to B agents (agent-major rows; caller buffers are used in place)
 static int reserve(mpc_handle *h, int B)
 {
-    const DevCfg &c = h->dc;
-    const int Bp = (B + 63) & ~63;
+    const int Bp = (int)pad64((size_t)B);
     if (Bp <= h->Bp_alloc) { h->ws.Bp = h->Bp_alloc; h->ws.B = B; return MPC_OK; }
-    HIPCHK(hipSetDevice(h->device));
-    if (h->arena) { HIPCHK(hipFree(h->arena)); h->arena = nullptr; h->Bp_alloc = 0; }
-    const size_t n = c.n, m = c.m ? c.m : 1, M = c.M, nx = c.nx, N = c.N;
-    // a round holds at most two requests per agent (cost + speculative gradient): 2 Bp slots
-    const size_t JS = nx * (nx + 1) + 2, St = 2 * (size_t)Bp + 64 * (MPC_MAX_GROUPS + 1);
-    const size_t nd = 8 * n + 2 * M * n + 7 * m + REC;          // agent-major doubles per agent
-    const size_t nscr = (N + 1) * nx + 2 * N + N + N * JS;       // K1 scratch doubles per slot
-    const size_t ni = 4;                                         // list ints per agent
-    const size_t bytes = (nd * 8 + ni * 4) * (size_t)Bp + nscr * 8 * St + 4 * St + 8 * 4 * MPC_MAX_GROUPS + 256 + 64 + 256;
-    char *base = nullptr;
-    hipError_t e = hipMalloc((void **)&base, bytes);
-    if (e != hipSuccess) return fail(MPC_E_ALLOC, "workspace hipMalloc failed: " + std::string(hipGetErrorString(e)));
-    h->arena = base; h->arena_bytes = bytes; h->Bp_alloc = Bp;
     WorkspaceHost &w = h->ws;
-    double *dp = (double *)base;
-    auto takeD = [&](size_t cnt) { double *r = dp; dp += cnt * (size_t)Bp; return r; };
-    w.xk = takeD(n); w.gk = takeD(n); w.q = takeD(n); w.xn = takeD(n); w.xe = takeD(n); w.ge = takeD(n);
-    w.xe2 = takeD(n); w.ge2 = takeD(n);
-    w.S = takeD(M * n); w.Y = takeD(M * n);
-    w.Sig = takeD(m); w.Sig_old = takeD(m); w.e1 = takeD(m); w.e2 = takeD(m);
-    w.yhx = takeD(m); w.yhxn = takeD(m); w.yhe = takeD(m);
-    w.rec = takeD(REC);
-    auto takeS = [&](size_t cnt) { double *r = dp; dp += cnt * St; return r; };
-    w.trajx = takeS((N + 1) * nx); w.useq = takeS(2 * N); w.stage_L = takeS(N); w.jac = takeS(N * JS);
-    int *ip = (int *)dp;
-    auto takeI = [&](size_t cnt) { int *r = ip; ip += cnt * (size_t)Bp; return r; };
-    w.lists = takeI(4);
-    w.agent_of = ip; ip += St;
-    w.counts = ip; // 8 ints per group
-    w.totals = (unsigned long long *)(ip + 8 * MPC_MAX_GROUPS);
-    w.solo_ctr = (int *)(w.totals + 16); // [group][claim counter, list length]
-    w.Bp = Bp; w.B = B; w.St = (int)St; w.Ls = Bp;
+    h->Bp_alloc = 0;
+    const int rc = carve(h->arena, h->device, true, "workspace hipMalloc failed: ",
+                         [&](Carver &a) { workspace_layout(a, w, h->dc, (size_t)Bp); });
+    if (rc) return rc;
+    h->Bp_alloc = Bp;
+    w.Bp = Bp; w.B = B; w.St = (int)ws_slots((size_t)Bp); w.Ls = Bp;
     w.ws_xe = w.xe; w.ws_ge = w.ge; w.ws_yhe = w.yhe; w.ws_Sig = w.Sig;
-    HIPCHK(hipMemset(base, 0, bytes));
     return MPC_OK;
 }
 
-static int reserve_stage(mpc_handle *h, size_t bytes)
-{
-    if (bytes <= h->stage_bytes) return MPC_OK;
-    if (h->stage) { HIPCHK(hipFree(h->stage)); h->stage = nullptr; h->stage_bytes = 0; }
-    hipError_t e = hipMalloc((void **)&h->stage, bytes);
-    if (e != hipSuccess) return fail(MPC_E_ALLOC, "staging hipMalloc failed");
-    h->stage_bytes = bytes;
-    return MPC_OK;
-}
+static int reserve_stage(mpc_handle *h, size_t bytes) { return h->stage.grow(h->device, bytes, false, "staging hipMalloc failed"); }
 
-// staging of the masked solve for up to B agents (see mpc_handle::EventBufs)
-static int reserve_event(mpc_handle *h, int B)
+// One of the handle's *Bufs for up to B agents: its arena grown to layout(Carver &, bufs, dims..., capacity), zero-filled,
+// and its pointers placed
+template <class Bufs, class Layout, class... Dims>
+static int reserve_bufs(mpc_handle *h, Bufs &b, int B, const char *msg, Layout layout, const Dims &...dims)
 {
-    mpc_handle::EventBufs &e = h->ev;
-    if (B <= e.cap) return MPC_OK;
-    HIPCHK(hipSetDevice(h->device));
-    if (e.base) { HIPCHK(hipFree(e.base)); e.base = nullptr; e.cap = 0; }
-    const DevCfg &c = h->dc;
-    const size_t Bp = ((size_t)B + 63) & ~(size_t)63, m = c.m ? c.m : 1, nblk = (Bp + EV_BLK - 1) / EV_BLK;
-    const size_t nd = (size_t)c.nx + c.n + m + 8 + 8;            // doubles per agent: xs, Us, lams, stats_s, stats_own
-    const size_t bytes = nd * 8 * Bp + 4 * ((3 + TAB_KINDS) * Bp + nblk + 64);  // ints: list, fire, cis, rows of every kind [Bp], blk [nblk], count
-    char *base = nullptr;
-    if (hipMalloc((void **)&base, bytes) != hipSuccess) return fail(MPC_E_ALLOC, "masked-solve staging hipMalloc failed");
-    e.base = base; e.cap = (int)Bp;
-    double *dp = (double *)base;
-    auto takeD = [&](size_t cnt) { double *r = dp; dp += cnt * Bp; return r; };
-    e.xs = takeD(c.nx); e.Us = takeD(c.n); e.lams = takeD(m); e.stats_s = takeD(8); e.stats_own = takeD(8);
-    int *ip = (int *)dp;
-    auto takeI = [&](size_t cnt) { int *r = ip; ip += cnt; return r; };
-    e.list = takeI(Bp); e.fire = takeI(Bp); e.cis = takeI(Bp);
-    for (int *&rows : e.rows) rows = takeI(Bp);
-    e.blk = takeI(nblk); e.count = takeI(64);
-    HIPCHK(hipMemset(base, 0, bytes));
-    return MPC_OK;
+    if (B <= b.cap) return MPC_OK;
+    const size_t Bp = pad64((size_t)B);
+    b.cap = 0;
+    const int rc = carve(b.arena, h->device, true, msg, [&](Carver &a) { layout(a, b, dims..., Bp); });
+    if (rc == MPC_OK) b.cap = (int)Bp;
+    return rc;
 }
-// buffers of the traffic loop for up to B agents (see mpc_handle::TrafficBufs)
-static int reserve_traffic(mpc_handle *h, int B)
-{
-    mpc_handle::TrafficBufs &t = h->tr;
-    if (B <= t.cap) return MPC_OK;
-    HIPCHK(hipSetDevice(h->device));
-    if (t.base) { HIPCHK(hipFree(t.base)); t.base = nullptr; t.cap = 0; }
-    const size_t Bp = ((size_t)B + 63) & ~(size_t)63;
-    const size_t nd = (size_t)h->dc.N * h->dc.nx;                // doubles per agent: X
-    const size_t bytes = nd * 8 * Bp + 4 * MPC_NDISC * Bp;
-    char *base = nullptr;
-    if (hipMalloc((void **)&base, bytes) != hipSuccess) return fail(MPC_E_ALLOC, "traffic-loop hipMalloc failed");
-    t.base = base; t.cap = (int)Bp;
-    t.X = (double *)base; t.opp = (int32_t *)(t.X + nd * Bp);
-    HIPCHK(hipMemset(base, 0, bytes));
-    return MPC_OK;
-}
-// buffers of the obstacle rule for up to B agents (see mpc_handle::ObstacleRuleBufs)
-static int reserve_obstacle_rule(mpc_handle *h, int B)
-{
-    mpc_handle::ObstacleRuleBufs &o = h->orule;
-    if (B <= o.cap) return MPC_OK;
-    HIPCHK(hipSetDevice(h->device));
-    if (o.base) { HIPCHK(hipFree(o.base)); o.base = nullptr; o.cap = 0; }
-    const size_t Bp = ((size_t)B + 63) & ~(size_t)63;
-    const size_t bytes = (8 + 4) * MPC_NDISC * Bp;
-    char *base = nullptr;
-    if (hipMalloc((void **)&base, bytes) != hipSuccess) return fail(MPC_E_ALLOC, "obstacle-rule hipMalloc failed");
-    o.base = base; o.cap = (int)Bp;
-    o.clear_chk = (double *)base; o.sel_chk = (int32_t *)(o.clear_chk + MPC_NDISC * Bp);
-    HIPCHK(hipMemset(base, 0, bytes));
-    return MPC_OK;
-}
+// staging of the masked solve (EventBufs), buffers of the traffic loop (TrafficBufs) and of the obstacle rule (ObstacleRuleBufs)
+static int reserve_event(mpc_handle *h, int B) { return reserve_bufs(h, h->ev, B, "masked-solve staging hipMalloc failed", event_layout, h->dc); }
+static int reserve_traffic(mpc_handle *h, int B) { return reserve_bufs(h, h->tr, B, "traffic-loop hipMalloc failed", traffic_layout, h->dc); }
+static int reserve_obstacle_rule(mpc_handle *h, int B) { return reserve_bufs(h, h->orule, B, "obstacle-rule hipMalloc failed", obstacle_rule_layout); }
 // the nominal states for a batch of B agents; *fresh = they were (re)allocated: no agent's nominal state is known
 static int reserve_xhat(mpc_handle *h, int B, bool *fresh)
 {
-    mpc_handle::EventBufs &e = h->ev;
+    EventBufs &e = h->ev;
     *fresh = false;
     if (e.xhat && e.xhat_B == B) return MPC_OK;
-    HIPCHK(hipSetDevice(h->device));
-    if (e.xhat) { HIPCHK(hipFree(e.xhat)); e.xhat = nullptr; e.xhat_B = 0; }
-    const size_t bytes = sizeof(double) * (size_t)B * h->dc.nx;
-    if (hipMalloc((void **)&e.xhat, bytes) != hipSuccess) return fail(MPC_E_ALLOC, "nominal-state hipMalloc failed");
-    HIPCHK(hipMemset(e.xhat, 0, bytes));
-    e.xhat_B = B; *fresh = true;
+    HIPCHK(e.xhat_mem.release());           // (a batch of another size, a smaller one too: none of the states is this batch's)
+    e.xhat = nullptr; e.xhat_B = 0;
+    const int rc = e.xhat_mem.grow(h->device, sizeof(double) * (size_t)B * h->dc.nx, true, "nominal-state hipMalloc failed", fresh);
+    if (rc) return rc;
+    e.xhat = (double *)e.xhat_mem.p; e.xhat_B = B;
+    return MPC_OK;
+}
+// the handle's own one-row parameter, box, rate and field tables and an index of B zeros (see mpc_handle::own): the rows
+// are laid out and filled on the host and copied with the zeros behind them
+static int reserve_own_tables(mpc_handle *h, int B, const char *who)
+{
+    OwnTables &o = h->own;
+    if (B <= o.cap) return MPC_OK;
+    const size_t cap = pad64((size_t)B);
+    o.cap = 0;
+    const int rc = carve(o.arena, h->device, false, std::string(who) + ": hipMalloc failed",
+                         [&](Carver &a) { own_tables_layout(a, o, h->cfg.N, cap); });
+    if (rc) return rc;
+    std::vector<double> host((o.arena.bytes + 7) / 8, 0.0);
+    OwnTables rows;
+    Carver on_host((char *)host.data());
+    own_tables_layout(on_host, rows, h->cfg.N, cap);
+    (void)mpc_default_params(&h->cfg, rows.ptab);
+    (void)mpc_default_bounds(&h->cfg, rows.btab);
+    (void)mpc_default_rates(&h->cfg, rows.rtab);
+    (void)mpc_default_fields(&h->cfg, rows.ftab);
+    HIPCHK(hipMemcpy(o.arena.p, host.data(), o.arena.bytes, hipMemcpyHostToDevice));
+    o.cap = (int)cap;
     return MPC_OK;
 }
 
@@ -579,7 +470,7 @@ static int check_common(mpc_handle *h, int B, const char *who, bool from_worker 
 static NearTab near_for(const mpc_handle *h, const double *cl)
 {
     NearTab nt = {nullptr, nullptr, nullptr};
-    if (h->nearest_mode == 2 && h->cl_grid_for && h->cl_grid_for == cl) { nt.gmeta = h->cl_gmeta; nt.gcells = h->cl_gcells; nt.gxy = h->cl_gxy; }
+    if (h->nearest_mode == 2 && h->cl_grid_for && h->cl_grid_for == cl) { nt.gmeta = h->grid.gmeta; nt.gcells = h->grid.gcells; nt.gxy = h->grid.gxy; }
     return nt;
 }
 

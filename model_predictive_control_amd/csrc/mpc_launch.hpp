@@ -30,16 +30,16 @@ template <class F> static void with_model_table(const mpc_handle *h, const int32
 
 // The workspace as every kernel form with a table argument takes it: those forms exist together with the parameter form
 // alone (PA = true), so without a parameter table of the caller's they run on the handle's own one-row table
-// (mpc_handle::own_ptab; its index of zeros needs no slicing per group)
+// (mpc_handle::own; its index of zeros needs no slicing per group)
 static WorkspacePA with_own_params(const mpc_handle *h, const WorkspaceHost &w)
 {
     WorkspacePA wp = w;
-    if (!wp.ptab) { wp.ptab = h->own_ptab; wp.pidx = h->own_pidx; }
+    if (!wp.ptab) { wp.ptab = h->own.ptab; wp.pidx = h->own.pidx; }
     return wp;
 }
 // ... and the box as the table forms of the persistent kernel take it: they exist behind the box form alone, so
-// without a bounds table of the caller's they run on the handle's own one-row box table (mpc_handle::own_btab)
-static BoxTab with_own_box(const mpc_handle *h, const WorkspaceHost &w) { return w.bound(TAB_BOX) ? w.box() : BoxTab{h->own_btab, h->own_pidx}; }
+// without a bounds table of the caller's they run on the handle's own one-row box table (OwnTables::btab)
+static BoxTab with_own_box(const mpc_handle *h, const WorkspaceHost &w) { return w.bound(TAB_BOX) ? w.box() : BoxTab{h->own.btab, h->own.pidx}; }
 
 // The table forms of stage_kernel, stage_adjoint_kernel, solo_eval_kernel and (behind BoxTab) solo_kernel: which tables
 // view `w` hands its kernels as their trailing pack t..., decided by what is bound, the first that applies:
@@ -50,14 +50,14 @@ static BoxTab with_own_box(const mpc_handle *h, const WorkspaceHost &w) { return
 //   5. a disc table         <DiscTab>                                  (a handle of MPC_CONSTR_DISCS)
 //   6. none of them         the empty pack: the kernels without a table argument
 // (bind_agent_table refuses the pairs no form takes).  A form that stands behind a table the caller has not bound runs on
-// the handle's own one-row table of zeros in its place (`rates`: mpc_handle::own_rtab, zero weights; `fields`:
-// mpc_handle::own_ftab, A == 0 is skipped by a branch -- neither changes a bit).  f(PA, wp, t...): a table form is a form
+// the handle's own one-row table of zeros in its place (`rates`: OwnTables::rtab, zero weights; `fields`:
+// OwnTables::ftab, A == 0 is skipped by a branch -- neither changes a bit).  f(PA, wp, t...): a table form is a form
 // of the per-agent kernel (PA = std::true_type, wp = with_own_params), the empty pack keeps the run-time choice (PA says
 // whether a parameter table is bound, wp = w) -- so naming kernel<..., PA(), decltype(t)...> instantiates these forms alone.
 template <class F> static void with_table_form(const mpc_handle *h, const WorkspaceHost &w, F &&f)
 {
-    const auto rates = [&] { return w.bound(TAB_RATES) ? w.rate() : RateTab{h->own_rtab, h->own_pidx}; };
-    const auto fields = [&] { return w.bound(TAB_FIELDS) ? w.field() : FieldTab{h->own_ftab, h->own_pidx}; };
+    const auto rates = [&] { return w.bound(TAB_RATES) ? w.rate() : RateTab{h->own.rtab, h->own.pidx}; };
+    const auto fields = [&] { return w.bound(TAB_FIELDS) ? w.field() : FieldTab{h->own.ftab, h->own.pidx}; };
     const auto form = [&](auto... t) { f(std::true_type{}, with_own_params(h, w), t...); };
     const bool discs = w.bound(TAB_DISCS);
     if (w.bound(TAB_ROADS)) { if (discs) form(w.disc(), rates(), w.road()); else form(rates(), fields(), w.road()); }

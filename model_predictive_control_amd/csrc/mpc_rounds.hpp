@@ -64,8 +64,7 @@ struct SolveRun {
     // the solver records of a fresh solve, the handle's figures back to zero, the round guard
     int begin()
     {
-        HIPCHK(hipMemsetAsync(w.counts, 0, 8 * MPC_MAX_GROUPS * sizeof(int) + 16 * sizeof(unsigned long long) +
-                                               2 * MPC_MAX_GROUPS * sizeof(int), s));
+        HIPCHK(hipMemsetAsync(w.counts, 0, sizeof(DevCounters), s));   // counts, totals and solo_ctr
         hipLaunchKernelGGL(init_kernel, dim3((unsigned)(((size_t)B * REC + 255) / 256)), dim3(256), 0, s, c, w);
         h->rounds = 0; h->evals_grad = 0; h->evals_cost = 0; h->eval_ms = 0.0; h->step_ms = 0.0;
         h->lbfgs_ms = 0.0; h->lbfgs_rows = 0; h->solo_agents = 0;
@@ -172,7 +171,7 @@ struct SolveRun {
         if (le != hipSuccess && le != hipErrorNotReady) { rc_loop = MPC_E_HIP; return; }
         const int wb = (int)(r.window & 1);
         if (!h->pollev[wb][g] && hipEventCreateWithFlags(&h->pollev[wb][g], hipEventDisableTiming) != hipSuccess) { rc_loop = MPC_E_HIP; return; }
-        if (hipMemcpyAsync(h->host_counts + 16 * wb + 2 * g, v.counts + cur * 4, 2 * sizeof(int), hipMemcpyDeviceToHost, gs[g]) != hipSuccess ||
+        if (hipMemcpyAsync(h->pinned().poll[wb][g], v.counts + cur * 4, 2 * sizeof(int), hipMemcpyDeviceToHost, gs[g]) != hipSuccess ||
             hipEventRecord(h->pollev[wb][g], gs[g]) != hipSuccess) { rc_loop = MPC_E_HIP; return; }
         r.window++;
     }
@@ -187,7 +186,8 @@ struct SolveRun {
     // what the counters of window `pb` say about group g; returns false when the group is done with rounds
     bool decide(int g, int pb)
     {
-        const int reqs = h->host_counts[16 * pb + 2 * g] + h->host_counts[16 * pb + 2 * g + 1];
+        const int *polled = h->pinned().poll[pb][g];
+        const int reqs = polled[0] + polled[1];
         if (reqs == 0) return false;
         gr[g].slot_bound = std::min(gr[g].slot_bound, 2 * reqs);
         if (solo_ok && h->solo_max > 0 && reqs <= h->solo_max) {
@@ -239,7 +239,7 @@ struct SolveRun {
                 if (host_trace)
                     trace.push_back({(long long)g, r.round - (r.window - oldest) * check_every + check_every - 1,
                                      (long long)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_loop0).count(),
-                                     (long long)(h->host_counts[16 * pb + 2 * g] + h->host_counts[16 * pb + 2 * g + 1])});
+                                     (long long)(h->pinned().poll[pb][g][0] + h->pinned().poll[pb][g][1])});
                 bool go = decide(g, pb);
                 if (go && r.round >= max_rounds) {
                     // the round limit: nothing more can be queued; the verdict is the LAST window's
@@ -294,12 +294,11 @@ struct SolveRun {
             }
         }
         for (int g = 0; g < ng; g++) h->rounds = std::max<int64_t>(h->rounds, rounds_done[g]);
-        unsigned long long *tot = (unsigned long long *)((char *)h->host_counts + 128);   // pinned (see host_counts)
-        int *sctr = (int *)((char *)h->host_counts + 256);
-        static_assert(16 * sizeof(unsigned long long) == 128 && 2 * MPC_MAX_GROUPS * sizeof(int) == 64, "pinned staging layout");
+        unsigned long long *tot = h->pinned().totals;
+        int *sctr = h->pinned().solo_ctr;
         hipLaunchKernelGGL(totals_kernel, grid_for(B, 256), dim3(256), 0, s, w);
-        HIPCHK(hipMemcpyAsync(tot, w.totals, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(sctr, w.solo_ctr, 2 * MPC_MAX_GROUPS * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(tot, w.totals, sizeof(PinnedCounts::totals), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(sctr, w.solo_ctr, sizeof(PinnedCounts::solo_ctr), hipMemcpyDeviceToHost, s));
         { const int rs = bounded_sync(h, s, "mpc_solve_batch"); if (rs) return rs; }
         h->evals_grad = (int64_t)tot[0]; h->evals_cost = (int64_t)tot[1]; h->lbfgs_rows = (int64_t)tot[2];
         h->spec_issued = (int64_t)tot[4]; h->spec_used = (int64_t)tot[5];
