@@ -682,6 +682,61 @@ int mpc_closed_loop_obstacles_event(mpc_handle *h, int B, int T, int shift, cons
                                     uint8_t *traj_why, uint8_t *solved, int32_t *solve_count, int32_t *fail_count,
                                     double *stats, void *stream, const mpc_track *trk);
 
+/* Event-triggered holding in traffic: the car trigger watches the plant alone, and an opponent that changes its plan does
+ * not move my plant off my plan; these two calls add the trigger that watches the other agents' plans.  It is time-aligned
+ * by construction: mpc_rollout_held's X[b][j] is the state agent b reaches at time now + j + 1 whether b has just
+ * re-planned or is held[b] stages into its plan, so one X serves the selection and the gather of the whole batch.
+ * mpc_opponent_trigger: the rule of mpc_obstacle_trigger on the other agents, pure -- it shifts no plan and rewrites no
+ * table.  The scene arguments (G, radius, reach) are mpc_opponents_from_plans'; X [B][N][nx] is mpc_rollout_held's; opp_plan
+ * [B][MPC_NDISC] (int32) holds the GLOBAL indices of the agents the held plan was solved against (-1: none).  With k_b =
+ * min(max(held[b], 0), N - 1) and n_b = N - k_b, the selection of mpc_opponents_from_plans runs for agent b over the stages
+ * j < n_b and no others: c(b, o) = min_{j < n_b} g_j.  The count is b's own, not the opponent's -- o's positions are read as
+ * X has them, its own repeated tail included: that is what o goes on applying as far as anyone knows, and what a gather at
+ * this step copies.  A non-finite g_j at j < n_b takes the pair out, one at j >= n_b is never looked at.  opp_chk
+ * [B][MPC_NDISC] (int32) and clear_chk [B][MPC_NDISC] (out; -1 and +inf for an unused slot).  Then why [B] (uint8, out,
+ * NULL ok) and fire_out [B] (int32, out; may be fire_in) are mpc_obstacle_trigger's, word for word, with opp_chk for sel_chk
+ * and opp_plan for sel_plan:
+ *     bit 0 (1)  fire_in[b] != 0 (NULL: none)
+ *     bit 1 (2)  held[b] > 0, watch & 1 and !(clear_chk[b][0] >= clear_thr)
+ *     bit 2 (4)  held[b] > 0, watch & 2 and some opp_chk[b][j] >= 0 is not a member of {opp_plan[b][0], opp_plan[b][1]}
+ * Asynchronous on `stream`.  MPC_E_ARG before any launch: everything mpc_opponents_from_plans refuses (Nst = N), clear_thr >
+ * reach^2 or NaN, watch outside [0, 3], a NULL X, held, opp_plan, opp_chk, clear_chk or fire_out.
+ * mpc_closed_loop_traffic_event: mpc_closed_loop_traffic(_field) in which an agent keeps applying the plan it holds.  The
+ * arguments are those of mpc_closed_loop_event (w, thr, max_hold, held, disturbance, solved, solve_count) and of the traffic
+ * loops (G, radius, reach, table, traj_opp, traj_clear), clear_thr and watch as above, opp_plan [B][MPC_NDISC] (in/out) and
+ * traj_why [B][T] (uint8, NULL ok).  On a handle of MPC_CONSTR_DISCS `table` is the bound disc table and `shape` must be
+ * NULL; on every other handle `table` is the bound field table and shape [B][4] is required (mpc_fields_from_plans').  The
+ * table has P == B rows and so has a bound rate table, as in the traffic loops.  Blocking.  Step t, every launch being the one
+ * the public call of that name makes:
+ *   1. fire = mpc_trigger_eval(x, xhat, held) -- no plan is shifted yet; a handle that has no nominal states for this B
+ *      fires everybody at its first step, as in mpc_closed_loop_event
+ *   2. X = mpc_rollout_held(x, U, held), into a buffer of the handle
+ *   3. fire, traj_why[.][t] = mpc_opponent_trigger(X, held, opp_plan, fire_in = fire)
+ *   4. shift != 0: the plans of the firing agents with held > 0 are shifted in place by k_b stages
+ *   5. opp = mpc_opponents_from_plans(X, Nst = N) of everybody; traj_opp [B][T][MPC_NDISC] records it
+ *   6. the gather of the handle's kind (mpc_discs_from_plans / mpc_fields_from_plans) from X and opp into the rows of the
+ *      FIRING agents alone, and opp_plan[b] = opp[b] for them: a held agent's row stays the one its plan was solved on
+ *   7. mpc_solve_active(fire); lambda is NOT re-slotted
+ *   8. the rate table's u_prev write
+ *   9. the step of mpc_closed_loop_event (plant, nominal state, held, solved, solve_count, fail_count, disturbance)
+ *  10. traj_clear[.][t] as in mpc_closed_loop_traffic: slot 0 of the selection on the new states (Nst = 1, reach = +inf)
+ * A held agent sees an opponent's re-plan at the step after it (the X of step 2 is rolled from the plans before the solve
+ * of step 7), as in a Jacobi sweep.  held, opp_plan, U and lambda are in/out: a second call with what the first returned
+ * continues it.  U returns as last solved (not shifted by the stages applied since).  thr = 0 with shift != 0 is
+ * mpc_closed_loop_traffic(_field) bit for bit; G = 1 is mpc_closed_loop_event on a table of zeros; watch = 0 fires by
+ * deviation and hold limit alone.  MPC_E_ARG, before the first allocation: what mpc_closed_loop_event, the traffic loops and
+ * mpc_opponent_trigger refuse, a NULL opp_plan, a shape on a disc handle and none on another. */
+int mpc_opponent_trigger(mpc_handle *h, int B, int G, const double *X, const double *radius, double reach,
+                         const int32_t *held, const int32_t *opp_plan, double clear_thr, int watch,
+                         const int32_t *fire_in, int32_t *opp_chk, double *clear_chk, uint8_t *why,
+                         int32_t *fire_out, void *stream);
+int mpc_closed_loop_traffic_event(mpc_handle *h, int B, int T, int shift, const double *w, double thr, int max_hold,
+                                  int G, const double *radius, const double *shape, double reach, double clear_thr, int watch,
+                                  double *x, const double *cl, const int32_t *cl_index, double *U, double *lambda,
+                                  int32_t *held, int32_t *opp_plan, double *table, const double *disturbance,
+                                  double *traj_x, double *traj_u, int32_t *traj_opp, double *traj_clear, uint8_t *traj_why,
+                                  uint8_t *solved, int32_t *solve_count, int32_t *fail_count, double *stats, void *stream);
+
 /* profiling aid: rounds (eval launches) and kernel time of the last mpc_solve_batch */
 int mpc_last_solve_info(mpc_handle *h, int64_t *rounds, int64_t *evals_grad, int64_t *evals_cost,
                         double *eval_ms, double *step_ms);

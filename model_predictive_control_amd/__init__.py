@@ -8,7 +8,7 @@ from ._lib import (MODEL_KINEMATIC, MODEL_PACEJKA, WRAP_FLOOR, WRAP_FMOD, WRAP_I
                    NSTATS, NPARAM, MpcConfig, default_config, default_params, param_rows, NBOUND,
                    default_bounds, bound_rows, NCONSTR, default_constraints, constraint_rows, MpcError,
                    obstacle_tracks, obstacle_width, NROAD, default_roads, road_rows)
-from .solver import BatchedMPC, Track, TrafficLoopResult, ObstacleLoopResult, ObstacleEventLoopResult
+from .solver import BatchedMPC, Track, TrafficLoopResult, ObstacleLoopResult, ObstacleEventLoopResult, TrafficEventLoopResult
 from .tracks import stadium_track, circle_track
 
 __all__ = ["BatchedMPC", "MpcConfig", "default_config", "MpcError", "MODEL_KINEMATIC", "MODEL_PACEJKA",
@@ -18,4 +18,4 @@ __all__ = ["BatchedMPC", "MpcConfig", "default_config", "MpcError", "MODEL_KINEM
            "default_params", "param_rows", "NBOUND", "default_bounds", "bound_rows", "NCONSTR",
            "default_constraints", "constraint_rows", "Track", "TrafficLoopResult", "stadium_track",
            "circle_track", "ObstacleLoopResult", "ObstacleEventLoopResult", "obstacle_tracks", "obstacle_width", "NROAD",
-           "default_roads", "road_rows"]
+           "default_roads", "road_rows", "TrafficEventLoopResult"]

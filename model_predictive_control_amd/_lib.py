@@ -61,6 +61,7 @@ EXPORTS = [
     "mpc_opponents_from_plans", "mpc_closed_loop_traffic",
     "mpc_obstacles_select", "mpc_discs_from_obstacles", "mpc_fields_from_obstacles", "mpc_closed_loop_obstacles",
     "mpc_rollout_held", "mpc_obstacle_trigger", "mpc_closed_loop_obstacles_event",
+    "mpc_opponent_trigger", "mpc_closed_loop_traffic_event",
     "mpc_track_init", "mpc_track_windows", "mpc_track_locate", "mpc_track_select", "mpc_closed_loop_track",
 ]
 NREC = 64
@@ -212,6 +213,9 @@ def load():
     L.mpc_obstacle_trigger.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp, C.c_double, vp, vp, C.c_double, ci, vp, vp, vp, vp, vp, vp]
     L.mpc_closed_loop_obstacles_event.argtypes = [vp, ci, ci, ci, C.POINTER(C.c_double), C.c_double, ci, ci, ci, ci, ci, ci, vp,
                                                   C.c_double, C.c_double, ci] + [vp] * 19 + [tp]
+    L.mpc_opponent_trigger.argtypes = [vp, ci, ci, vp, vp, C.c_double, vp, vp, C.c_double, ci, vp, vp, vp, vp, vp, vp]
+    L.mpc_closed_loop_traffic_event.argtypes = [vp, ci, ci, ci, C.POINTER(C.c_double), C.c_double, ci, ci, vp, vp, C.c_double,
+                                                C.c_double, ci] + [vp] * 19
     L.mpc_step_lds_plan.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     L.mpc_math_probe.argtypes = [vp, ci, ci, vp, vp, vp, vp]
     L.mpc_lane_payoff.argtypes = [vp, ci, ci, C.POINTER(C.c_double), vp, vp, vp, vp, vp]

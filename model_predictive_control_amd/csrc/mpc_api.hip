@@ -427,12 +427,12 @@ static int rows_from_plans(const std::string &who, Kernel kernel, mpc_handle *h,
 extern "C" int mpc_discs_from_plans(mpc_handle *h, int B, const double *X, const int32_t *opp, const double *radius,
                                     double *table, void *stream)
 {
-    return rows_from_plans("mpc_discs_from_plans", discs_from_plans_kernel, h, B, X, opp, radius, table, stream);
+    return rows_from_plans("mpc_discs_from_plans", discs_from_plans_kernel<>, h, B, X, opp, radius, table, stream);
 }
 extern "C" int mpc_fields_from_plans(mpc_handle *h, int B, const double *X, const int32_t *opp, const double *shape,
                                      double *table, void *stream)
 {
-    return rows_from_plans("mpc_fields_from_plans", fields_from_plans_kernel, h, B, X, opp, shape, table, stream);
+    return rows_from_plans("mpc_fields_from_plans", fields_from_plans_kernel<>, h, B, X, opp, shape, table, stream);
 }
 
 extern "C" int mpc_rhs(mpc_handle *h, int B, const double *x, const double *u, double *dx, void *stream)
@@ -1006,14 +1006,21 @@ static int check_scene_args(const std::string &who, int B, int G, double reach, 
     return MPC_OK;
 }
 // the selection on plans X [B][Nst][nx] (see opponents_kernel for the three outputs)
+// (held != null: the held form -- agent b compares the stages a plan of Nst of which held[b] are applied still holds)
 static void launch_opponents(mpc_handle *h, hipStream_t s, int B, int G, int Nst, const double *X, const double *radius, double reach,
-                             int32_t *opp, int32_t *opp_rec, size_t rec_stride, double *clear, size_t clear_stride, int clear_slots)
+                             int32_t *opp, int32_t *opp_rec, size_t rec_stride, double *clear, size_t clear_stride, int clear_slots,
+                             const int32_t *held = nullptr)
 {
     int Gp = 1;
     while (Gp < G) Gp <<= 1;
     const int spw = 64 / Gp, scenes = B / G;
-    hipLaunchKernelGGL(opponents_kernel, dim3((unsigned)((scenes + spw - 1) / spw)), dim3(TR_BLK), 0, s, B, G, Gp, spw, Nst, h->dc.nx, X,
-                       radius, reach * reach, opp, opp_rec, rec_stride, clear, clear_stride, clear_slots);
+    const dim3 grid((unsigned)((scenes + spw - 1) / spw));
+    if (held)
+        hipLaunchKernelGGL((opponents_kernel<true, const int32_t *>), grid, dim3(TR_BLK), 0, s, B, G, Gp, spw, Nst, h->dc.nx, X, radius,
+                           reach * reach, opp, opp_rec, rec_stride, clear, clear_stride, clear_slots, held);
+    else
+        hipLaunchKernelGGL(opponents_kernel<>, grid, dim3(TR_BLK), 0, s, B, G, Gp, spw, Nst, h->dc.nx, X, radius, reach * reach, opp,
+                           opp_rec, rec_stride, clear, clear_stride, clear_slots);
 }
 
 extern "C" int mpc_opponents_from_plans(mpc_handle *h, int B, int G, int Nst, const double *X, const double *radius, double reach,
@@ -1384,6 +1391,121 @@ extern "C" int mpc_closed_loop_obstacles_event(mpc_handle *h, int B, int T, int 
                                  x, U, held, sel_plan, table, traj_sel, traj_clear, traj_why};
     return closed_loop_event_impl(who_, h, B, T, shift, w, thr, max_hold, x, cl, cl_index, U, lambda, held, disturbance, traj_x, traj_u,
                                   solved, solve_count, fail_count, stats, stream, trk, cl_index, nullptr, hook);
+}
+
+// ------------------------------------------------------------------------------ event-triggered holding in traffic
+// the selection of opponents over the stages every plan still holds, then the rule of the obstacles on global agent
+// indices (opp_chk [B][MPC_NDISC], clear_chk [B][MPC_NDISC])
+static void launch_opponent_trigger(mpc_handle *h, hipStream_t s, int B, int G, const double *X, const double *radius, double reach,
+                                    const int32_t *held, const int32_t *opp_plan, double clear_thr, int watch, const int32_t *fire_in,
+                                    int32_t *opp_chk, double *clear_chk, uint8_t *why, size_t why_stride, int32_t *fire_out)
+{
+    launch_opponents(h, s, B, G, h->cfg.N, X, radius, reach, opp_chk, nullptr, 0, clear_chk, MPC_NDISC, MPC_NDISC, held);
+    hipLaunchKernelGGL(obstacle_rule_kernel, grid_for(B, 64), dim3(64), 0, s, B, held, opp_chk, clear_chk, opp_plan, clear_thr, watch,
+                       fire_in, fire_out, why, why_stride);
+}
+
+extern "C" int mpc_opponent_trigger(mpc_handle *h, int B, int G, const double *X, const double *radius, double reach,
+                                    const int32_t *held, const int32_t *opp_plan, double clear_thr, int watch,
+                                    const int32_t *fire_in, int32_t *opp_chk, double *clear_chk, uint8_t *why, int32_t *fire_out,
+                                    void *stream)
+{
+    const std::string who = "mpc_opponent_trigger";
+    int rc = check_scene_args(who, B, G, reach, radius); if (rc) return rc;
+    rc = check_obstacle_rule(who, reach, clear_thr, watch); if (rc) return rc;
+    if (!X || !held || !opp_plan || !opp_chk || !clear_chk || !fire_out)
+        return fail(MPC_E_ARG, who + ": null X, held, opp_plan, opp_chk, clear_chk or fire_out");
+    rc = check_common(h, B, who.c_str()); if (rc) return rc;
+    rc = check_tables(h, B, who.c_str(), READS_ALL); if (rc) return rc;
+    if (B == 0) return MPC_OK;
+    launch_opponent_trigger(h, (hipStream_t)stream, B, G, X, radius, reach, held, opp_plan, clear_thr, watch, fire_in, opp_chk,
+                            clear_chk, why, 1, fire_out);
+    HIPCHK(hipGetLastError());
+    return MPC_OK;
+}
+
+// the gather of the selected opponents' plans into the rows of the agents with mask[b] != 0 alone, and opp_plan[b] <- opp[b]
+// for them (the masked forms of discs_from_plans_kernel / fields_from_plans_kernel; `per`: radius [B] or shape [B][4])
+static void launch_plan_rows_masked(mpc_handle *h, hipStream_t s, bool discs, int B, const double *X, const int32_t *opp, const double *per,
+                                    double *table, const int32_t *mask, int32_t *opp_plan)
+{
+    const size_t words = (size_t)B * h->cfg.N * MPC_NDISC;   // (== MPC_NFIELD)
+    const dim3 grid((unsigned)((words + 255) / 256));
+    if (discs)
+        hipLaunchKernelGGL((discs_from_plans_kernel<true, RowMask>), grid, dim3(256), 0, s, B, h->cfg.N, h->dc.nx, X, opp, per, table,
+                           RowMask{mask, opp_plan});
+    else
+        hipLaunchKernelGGL((fields_from_plans_kernel<true, RowMask>), grid, dim3(256), 0, s, B, h->cfg.N, h->dc.nx, X, opp, per, table,
+                           RowMask{mask, opp_plan});
+}
+
+// The event-triggered traffic loop: closed_loop_event_impl with the hook of the traffic -- every launch the one the public
+// call of that name makes (see include/mpc_hip.h for the ten steps)
+struct TrafficEventHook {
+    static constexpr bool on = true;
+    mpc_handle *h; hipStream_t s; void *stream;
+    int B, T, shift, G;
+    const double *radius, *per; bool discs; double reach, clear_thr; int watch;
+    double *x, *U; int32_t *held, *opp_plan; double *table;
+    int32_t *traj_opp; double *traj_clear; uint8_t *traj_why;
+    // steps 2 - 4: what every agent will go on applying, the rule on top of `fire`, the shift of the agents that fire
+    int fired(int t, int32_t *fire) const
+    {
+        const int rr = mpc_rollout_held(h, B, x, U, held, h->tr.X, stream); if (rr) return rr;
+        launch_opponent_trigger(h, s, B, G, h->tr.X, radius, reach, held, opp_plan, clear_thr, watch, fire, h->orule.sel_chk,
+                                h->orule.clear_chk, traj_why ? traj_why + t : nullptr, (size_t)T, fire);
+        if (shift) hipLaunchKernelGGL(plan_shift_kernel, grid_for(B, 64), dim3(64), 0, s, B, h->dc.N, held, fire, U);
+        return MPC_OK;
+    }
+    // steps 5 - 6: everybody's selection on the full horizon, the rows and opp_plan of the agents that fire
+    int selected(int t, int32_t *fire) const
+    {
+        launch_opponents(h, s, B, G, h->dc.N, h->tr.X, radius, reach, h->tr.opp, traj_opp ? traj_opp + (size_t)t * MPC_NDISC : nullptr,
+                         (size_t)T * MPC_NDISC, nullptr, 0, 0);
+        launch_plan_rows_masked(h, s, discs, B, h->tr.X, h->tr.opp, per, table, fire, opp_plan);
+        return MPC_OK;
+    }
+    // step 10: the realised clearance on the new states
+    int stepped(int t, int32_t *) const
+    {
+        if (traj_clear) launch_opponents(h, s, B, G, 1, x, radius, INFINITY, nullptr, nullptr, 0, traj_clear + t, (size_t)T, 1);
+        return MPC_OK;
+    }
+};
+extern "C" int mpc_closed_loop_traffic_event(mpc_handle *h, int B, int T, int shift, const double *w, double thr, int max_hold, int G,
+                                             const double *radius, const double *shape, double reach, double clear_thr, int watch,
+                                             double *x, const double *cl, const int32_t *cl_index, double *U, double *lambda,
+                                             int32_t *held, int32_t *opp_plan, double *table, const double *disturbance,
+                                             double *traj_x, double *traj_u, int32_t *traj_opp, double *traj_clear,
+                                             uint8_t *traj_why, uint8_t *solved, int32_t *solve_count, int32_t *fail_count,
+                                             double *stats, void *stream)
+{
+    const char *who_ = "mpc_closed_loop_traffic_event";
+    const std::string who(who_);
+    int rc = check_trigger_args(who_, w, thr, max_hold, held); if (rc) return rc;
+    if (T < 0) return fail(MPC_E_ARG, who + ": negative T");
+    rc = check_scene_args(who, B, G, reach, radius); if (rc) return rc;
+    rc = check_obstacle_rule(who, reach, clear_thr, watch); if (rc) return rc;
+    if (!opp_plan) return fail(MPC_E_ARG, who + ": null opp_plan");
+    if (!h) return fail(MPC_E_ARG, who + ": null handle");
+    rc = check_max_hold(h, who_, max_hold); if (rc) return rc;
+    rc = check_common(h, B, who_); if (rc) return rc;
+    const bool discs = obstacle_discs(h);
+    if (discs && shape)
+        return fail(MPC_E_ARG, who + ": the handle's constr_mode is MPC_CONSTR_DISCS: there an opponent is a disc and shape must be NULL");
+    if (!discs && !shape) return fail(MPC_E_ARG, who + ": null shape (the handle's opponents are risk fields: shape [B][4])");
+    rc = check_tables(h, B, who_, READS_ALL, true); if (rc) return rc;
+    rc = check_rewritten_table(h, discs ? TAB_DISCS : TAB_FIELDS, table, B, who); if (rc) return rc;
+    rc = check_rate_rows(h, B, who); if (rc) return rc;
+    if (B == 0 || T == 0) return MPC_OK;
+    // every refusal stands before the first allocation (closed_loop_event_impl repeats the ones it shares)
+    if (!x || !cl || !U || (h->dc.m && !lambda)) return fail(MPC_E_ARG, who + ": null buffer");
+    rc = reserve_traffic(h, B); if (rc) return rc;
+    rc = reserve_obstacle_rule(h, B); if (rc) return rc;
+    const TrafficEventHook hook{h, (hipStream_t)stream, stream, B, T, shift, G, radius, discs ? radius : shape, discs, reach, clear_thr,
+                                watch, x, U, held, opp_plan, table, traj_opp, traj_clear, traj_why};
+    return closed_loop_event_impl(who_, h, B, T, shift, w, thr, max_hold, x, cl, cl_index, U, lambda, held, disturbance, traj_x, traj_u,
+                                  solved, solve_count, fail_count, stats, stream, nullptr, nullptr, nullptr, hook);
 }
 
 extern "C" int mpc_last_speculation(mpc_handle *h, int64_t *issued, int64_t *used)

@@ -242,16 +242,28 @@ __global__ void __launch_bounds__(64) rate_prev_kernel(int B, int N, const doubl
 
 // mpc_discs_from_plans: table[b][k][j] = (X[o][k][0], X[o][k][1], radius[o]) for o = opp[b][j], zeros where there is no such
 // agent (o < 0 or o >= B).  One thread per (agent, stage, disc); every word written is a copy of an input word or zero.
+// MASKED (step 6 of mpc_closed_loop_traffic_event and, in rows_from_obstacles_kernel, step 7 of
+// mpc_closed_loop_obstacles_event; mk = RowMask{mask [B], sel_plan [B][NDISC]}): the rows of the agents with mask[b] != 0
+// alone are written -- a held agent's row stays the one its plan was solved on -- and for those agents
+// sel_plan[b] <- opp[b] (the thread of stage 0 writes it): what the plan about to be solved is solved against.
+struct RowMask { const int *mask; int *sel_plan; };
+template <bool MASKED = false, class... MK>
 __global__ void __launch_bounds__(256) discs_from_plans_kernel(int B, int N, int nx, const double *__restrict__ X,
                                                                const int *__restrict__ opp, const double *__restrict__ radius,
-                                                               double *__restrict__ table)
+                                                               double *__restrict__ table, MK... mk)
 {
+    static_assert(sizeof...(MK) == (MASKED ? 1 : 0), "the masked form takes a RowMask, the plain form nothing");
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= (size_t)B * N * NDISC) return;
     const int j = (int)(t % NDISC);
     const size_t bk = t / NDISC;
     const int k = (int)(bk % N), b = (int)(bk / N);
     const int o = opp[(size_t)b * NDISC + j];
+    if constexpr (MASKED) {
+        const RowMask m = (mk, ...);
+        if (m.mask[b] == 0) return;
+        if (k == 0) m.sel_plan[(size_t)b * NDISC + j] = o;
+    }
     double cx = 0.0, cy = 0.0, r = 0.0;
     if (o >= 0 && o < B) {
         const double *__restrict__ xo = X + ((size_t)o * N + k) * nx;
@@ -264,18 +276,26 @@ __global__ void __launch_bounds__(256) discs_from_plans_kernel(int B, int N, int
 // mpc_fields_from_plans: table[b][k][j] = [cx, cy, c, s, A, kx, ky, alpha] for o = opp[b][j] -- the opponent's planned
 // position X[o][k][0..1], the device sincos of its planned heading X[o][k][2], its shape[o][0..2] as an obstacle, and the
 // skew shape[o][3] * (X[b][k][3] - X[o][k][3]) (the subtraction and the product each rounded on its own) -- eight zeros
-// where there is no such agent (o < 0 or o >= B).  One thread per (agent, stage, source).
+// where there is no such agent (o < 0 or o >= B).  One thread per (agent, stage, source).  MASKED: as in
+// discs_from_plans_kernel.
+template <bool MASKED = false, class... MK>
 __global__ void __launch_bounds__(256) fields_from_plans_kernel(int B, int N, int nx, const double *__restrict__ X,
                                                                 const int *__restrict__ opp, const double *__restrict__ shape,
-                                                                double *__restrict__ table)
+                                                                double *__restrict__ table, MK... mk)
 {
 #pragma clang fp contract(off)
+    static_assert(sizeof...(MK) == (MASKED ? 1 : 0), "the masked form takes a RowMask, the plain form nothing");
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= (size_t)B * N * NFIELD) return;
     const int j = (int)(t % NFIELD);
     const size_t bk = t / NFIELD;
     const int k = (int)(bk % N), b = (int)(bk / N);
     const int o = opp[(size_t)b * NFIELD + j];
+    if constexpr (MASKED) {
+        const RowMask m = (mk, ...);
+        if (m.mask[b] == 0) return;
+        if (k == 0) m.sel_plan[(size_t)b * NFIELD + j] = o;
+    }
     double v[NFSRC] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (o >= 0 && o < B) {
         const double *__restrict__ xo = X + ((size_t)o * N + k) * nx;

@@ -29,11 +29,10 @@ template <int W> MPC_DEV constexpr int obstacle_key() { return W == 3 ? 2 : 4; }
 // the agent's Kp lanes.  No atomics; a min of doubles does not depend on the order, so chunking changes no bit.
 // Outputs as in opponents_kernel, sel holding the track's index WITHIN the scene: sel [B][NDISC] (-1: none); sel_rec, the
 // same words at sel_rec[b * rec_stride + j]; clear at clear[b * clear_stride + j] for j < clear_slots (+inf: none).
-// HELD (mpc_obstacle_trigger; hd = held [B]): agent b folds its first held_stages(held[b], Nst) stages alone -- the stages
+// HELD (mpc_obstacle_trigger; hd = held [B]): agent b folds its first held_stages(held[b], Nst) (mpc_traffic.hpp) stages alone -- the stages
 // a plan of Nst of which held[b] have been applied still holds, as mpc_rollout_held lays them out; the tail that repeats
 // the last input is staged like every stage (X has Nst stages) and never compared.  Everything else is the same code.
 // (The count is re-read from held per chunk and pass; 16 counts kept in registers cost 64 vector registers.)
-MPC_DEV int held_stages(int held, int N) { return N - max(0, min(held, N - 1)); }
 template <int W, bool HELD = false, class... HD>
 __global__ void __launch_bounds__(TR_BLK) obstacles_kernel(int B, int G, int K, int Kp, int spw, int Lt, int wrap, int ti, int Nst,
                                                            int nx, const double *__restrict__ X, const double *__restrict__ obs,
@@ -139,7 +138,7 @@ __global__ void __launch_bounds__(TR_BLK) obstacles_kernel(int B, int G, int K, 
 // MASKED (step 7 of mpc_closed_loop_obstacles_event; mk = (mask [B], sel_plan [B][NDISC])): the rows of the agents with
 // mask[b] != 0 alone are written -- a held agent's row stays the one its plan was solved on -- and for those agents
 // sel_plan[b] <- sel[b] (the thread of stage 0 writes it): the tracks the plan about to be solved is solved against.
-struct RowMask { const int *mask; int *sel_plan; };
+// (RowMask: mpc_event.hpp, beside the masked gathers from plans)
 template <int W, bool MASKED = false, class... MK>
 __global__ void __launch_bounds__(256) rows_from_obstacles_kernel(int B, int N, int G, int K, int Lt, int wrap, int ti,
                                                                   const double *__restrict__ obs, const int *__restrict__ sel,

@@ -35,12 +35,21 @@ MPC_DEV double traffic_sq(double r)
 // min of doubles does not depend on the order, so chunking the stages changes no bit.
 // Outputs, each optional: opp [B][NDISC] global indices (-1: none); opp_rec, the same words at opp_rec[b * rec_stride + j];
 // clear at clear[b * clear_stride + j] for j < clear_slots (+inf: none).
+// HELD (mpc_opponent_trigger; hd = held [B]): the lane's own agent b folds its first n_b = held_stages(held[b], Nst) stages
+// alone -- the stages a plan of Nst of which held[b] have been applied still holds, as mpc_rollout_held lays them out.  The
+// count is the agent's, not the opponent's: opponent o is read at the stages j < n_b as X has them, its own repeated tail
+// included (what o goes on applying as far as anyone knows, and what a gather at this step copies).  Every stage is staged
+// like before (X has Nst stages); the tail behind n_b is never compared, so a non-finite g_j there does not take the pair
+// out.  Everything else is the same code.
+MPC_DEV int held_stages(int held, int N) { return N - max(0, min(held, N - 1)); }
+template <bool HELD = false, class... HD>
 __global__ void __launch_bounds__(TR_BLK) opponents_kernel(int B, int G, int Gp, int spw, int Nst, int nx,
                                                            const double *__restrict__ X, const double *__restrict__ radius,
                                                            double reach2, int *__restrict__ opp, int *__restrict__ opp_rec,
                                                            size_t rec_stride, double *__restrict__ clear, size_t clear_stride,
-                                                           int clear_slots)
+                                                           int clear_slots, HD... hd)
 {
+    static_assert(sizeof...(HD) == (HELD ? 1 : 0), "the held form takes held [B], the plain form nothing");
     __shared__ double s_x[TR_KC * SCENE_MAX], s_y[TR_KC * SCENE_MAX];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const size_t b0 = (size_t)blockIdx.x * spw * G;                 // first agent of the workgroup (a scene's first)
@@ -60,6 +69,11 @@ __global__ void __launch_bounds__(TR_BLK) opponents_kernel(int B, int G, int Gp,
         const double r2 = pair_on ? traffic_sq(radius[b0 + orr]) : 0.0;
         double c = inf;
         bool bad = false;
+        int nb = Nst;                                                // the stages the lane's agent compares
+        if constexpr (HELD) {
+            const int *__restrict__ held = (hd, ...);
+            nb = agent_on ? held_stages(held[b0 + a], Nst) : 0;
+        }
         for (int ch = 0; ch < nch; ch++) {
             const int k0 = ch * TR_KC, kc = min(TR_KC, Nst - k0);
             if (nch > 1 || pass == 0) {                              // (uniform over the workgroup)
@@ -72,7 +86,9 @@ __global__ void __launch_bounds__(TR_BLK) opponents_kernel(int B, int G, int Gp,
                 }
                 __syncthreads();
             }
-            for (int k = 0; k < kc; k++) {
+            int kend = kc;
+            if constexpr (HELD) kend = min(kc, nb - k0);             // (<= 0 behind the agent's last stage)
+            for (int k = 0; k < kend; k++) {
                 const double g = traffic_g(s_x[k * SCENE_MAX + ar], s_y[k * SCENE_MAX + ar], s_x[k * SCENE_MAX + orr],
                                            s_y[k * SCENE_MAX + orr], r2);
                 if (!isfinite(g)) bad = true;

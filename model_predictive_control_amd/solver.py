@@ -49,6 +49,13 @@ ObstacleLoopResult = collections.namedtuple(
 ObstacleEventLoopResult = collections.namedtuple(
     "ObstacleEventLoopResult", ObstacleLoopResult._fields + ("solved", "solve_count", "held", "sel_plan", "traj_why"))
 
+# what BatchedMPC.closed_loop_traffic_event returns: the fields of TrafficLoopResult (U: the plans as last solved, not
+# shifted by the stages applied since), then solved [B, T] uint8, solve_count [B], held [B] int32 (stages of the plan
+# already applied), opp_plan [B, NDISC] int32 (the agents every agent's plan was solved against, global indices) and
+# traj_why [B, T] uint8 (bit 0: the car trigger, bit 1: clearance to the others' plans, bit 2: a new opponent)
+TrafficEventLoopResult = collections.namedtuple(
+    "TrafficEventLoopResult", TrafficLoopResult._fields + ("solved", "solve_count", "held", "opp_plan", "traj_why"))
+
 
 class Track:
     """A table of track windows (BatchedMPC.track_windows): `win` [K * R, 2S], the window tensor -- an ordinary
@@ -1063,6 +1070,79 @@ class BatchedMPC:
             _ptr(tu), _ptr(tsel), _ptr(tclear), _ptr(twhy), _ptr(solved), _ptr(count), _ptr(fails), _ptr(stats), self._stream(),
             C.byref(trk._c) if trk is not None else None))
         return ObstacleEventLoopResult(x, U, lam, tx, tu, fails, stats, tsel, tclear, table, ci, solved, count, held, sel_plan, twhy)
+
+    # ------------------------------------------------------------------ event-triggered holding in traffic
+    def _opp_plan(self, B, opp_plan):
+        """opp_plan [B, NDISC] int32 of the traffic rule: global agent indices in [-1, B) (-1: none)"""
+        self._chk(opp_plan, (B, _lib.NDISC), "opp_plan", torch.int32)
+        if B and (int(opp_plan.min()) < -1 or int(opp_plan.max()) >= B):
+            raise ValueError(f"opp_plan: agent indices must be in [-1, {B}) (-1: none)")
+        return opp_plan
+
+    def opponent_trigger(self, X, held, opp_plan, G, radius, reach=float("inf"), clear_thr=0.0, watch=3, fire=None):
+        """mpc_opponent_trigger: the rule of obstacle_trigger on the other agents' plans, pure.  X [B, N, nx] is
+        rollout_held(x, U, held): stage j of what every agent will go on applying, at time now + j + 1 for the whole batch.
+        The selection of opponents_from_plans runs for agent b over the N - k stages its held plan still has (k =
+        min(max(held[b], 0), N - 1); the count is b's own, the opponents' positions are read as X has them) and gives
+        opp_chk [B, NDISC] int32 (global agent indices) and clear_chk [B, NDISC].  why [B] uint8: bit 0 = fire[b] != 0 (the
+        caller's, e.g. trigger_eval's; None: zeros); for agents with held > 0, bit 1 (watch & 1) = not clear_chk[b, 0] >=
+        clear_thr, bit 2 (watch & 2) = some opp_chk[b, j] >= 0 is not in the set opp_plan[b] ([B, NDISC] int32: the agents
+        the held plan was solved against, -1: none).  Returns (fire_out = why != 0 as int32 [B], why, opp_chk, clear_chk)."""
+        X, B, Nst = self._plans(X)
+        self._chk(X, (B, self.N, self.nx), "X")
+        G, reach = self._scene_args(B, G, radius, reach)
+        clear_thr, watch = float(clear_thr), int(watch)      # (the library refuses clear_thr > reach^2 or NaN, watch outside [0, 3])
+        self._chk(held, (B,), "held", torch.int32)
+        self._opp_plan(B, opp_plan)
+        if fire is not None:
+            self._chk(fire, (B,), "fire", torch.int32)
+        opp = torch.full((B, _lib.NDISC), -1, dtype=torch.int32, device=self.device)
+        clear = torch.full((B, _lib.NDISC), float("inf"), dtype=torch.float64, device=self.device)
+        why = torch.zeros(B, dtype=torch.uint8, device=self.device)
+        out = torch.zeros(B, dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.mpc_opponent_trigger(self._h, B, G, _ptr(X), _ptr(radius), reach, _ptr(held), _ptr(opp_plan), clear_thr,
+                                                 watch, _ptr(fire), _ptr(opp), _ptr(clear), _ptr(why), _ptr(out), self._stream()))
+        return out, why, opp, clear
+
+    def closed_loop_traffic_event(self, x, centerline, U, T, G, radius, w, thr, max_hold, shape=None, reach=float("inf"),
+                                  clear_thr=0.0, watch=3, held=None, opp_plan=None, lam=None, cl_index=None, shift=False,
+                                  table=None, disturbance=None, stats=None):
+        """mpc_closed_loop_traffic_event: closed_loop_traffic (an engine of CONSTR_DISCS; shape=None) or
+        closed_loop_traffic_field (every other engine; shape [B, 4]) in which an agent keeps applying the plan it holds, as in
+        closed_loop_event, and re-plans when the car trigger fires (w, thr, max_hold), when the plan it would go on applying
+        comes closer than clear_thr to what the others would go on applying (watch & 1), or when an agent that the plan was
+        not solved against enters its selection (watch & 2) -- opponent_trigger on rollout_held.  Only the agents that
+        re-plan get new rows of the bound disc / field table.  held [B] int32 (None: -1) and opp_plan [B, NDISC] int32
+        (None: -1) continue a loop together with the U / lam / stats of an earlier result.  The other arguments are the
+        traffic loops' and closed_loop_event's.  Returns a TrafficEventLoopResult (copies; the table is the bound one)."""
+        B, T = self._loop_entry(x, U), int(T)
+        thr, max_hold = self._trigger_args(thr, max_hold)
+        if T < 0:
+            raise ValueError("T must be >= 0")
+        G, reach = self._scene_args(B, G, radius, reach)
+        clear_thr, watch = float(clear_thr), int(watch)      # (the library refuses clear_thr > reach^2 or NaN, watch outside [0, 3])
+        discs = int(self.cfg.constr_mode) == _lib.CONSTR_DISCS
+        if discs and shape is not None:                        # before a table is made and bound for the caller
+            raise ValueError("closed_loop_traffic_event: the engine's constr_mode is CONSTR_DISCS, where an opponent is a disc "
+                             "(shape must be None)")
+        if not discs:
+            if shape is None:
+                raise ValueError("closed_loop_traffic_event: shape [B, 4] is required on an engine whose opponents are risk fields")
+            self._chk(shape, (B, 4), "shape")
+        table = self._loop_table("discs" if discs else "fields", B, table, identity_index=True)
+        cl = self._centerline(centerline, cl_index, B)
+        x, U, lam, held, tx, tu, solved, count, fails, stats = self._event_loop_state(B, T, x, U, lam, held, disturbance, stats)
+        opp_plan = torch.full((B, _lib.NDISC), -1, dtype=torch.int32, device=self.device) if opp_plan is None else opp_plan.clone()
+        self._opp_plan(B, opp_plan)
+        topp = torch.full((B, T, _lib.NDISC), -1, dtype=torch.int32, device=self.device)
+        tclear = torch.full((B, T), float("inf"), dtype=torch.float64, device=self.device)
+        twhy = torch.zeros(B, T, dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.mpc_closed_loop_traffic_event(
+            self._h, B, T, int(bool(shift)), self._weights(w), thr, max_hold, G, _ptr(radius), _ptr(shape), reach, clear_thr, watch,
+            _ptr(x), _ptr(cl), _ptr(cl_index), _ptr(U), _ptr(lam), _ptr(held), _ptr(opp_plan), _ptr(table), _ptr(disturbance),
+            _ptr(tx), _ptr(tu), _ptr(topp), _ptr(tclear), _ptr(twhy), _ptr(solved), _ptr(count), _ptr(fails), _ptr(stats),
+            self._stream()))
+        return TrafficEventLoopResult(x, U, lam, tx, tu, fails, stats, topp, tclear, table, solved, count, held, opp_plan, twhy)
 
     def lane_payoff(self, ego, cars, ncars, params):
         """f-3: out[B, 2, 4] = target lane 1, 2 -> [total, safety, velocity, comfort] (game_theory.py:115-244)."""
