@@ -1002,8 +1002,11 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
             // each, and a batch waits for the one agent that does (the Pacejka benchmark's slowest: 2 400 of
             // its 3 081 evaluations).  The memo replays the outcome and the counts, not the evaluations: the
             // result and every statistic are those of the run that was not repeated.
-            if (!c.no_memo && memo_status != 0 && m == 0 && !overwrite && c.max_total_evals == 0 &&
-                memo_iters < max_it && eps < memo_mineps) {
+            // (A run that ended ON the iteration limit is replayed while the limit is the same; under an evaluation
+            // budget, while the replayed run ends below it: none of its stop tests saw the budget reached.)
+            if (!c.no_memo && memo_status != 0 && m == 0 && !overwrite &&
+                (c.max_total_evals == 0 || nevals + memo_evals < c.max_total_evals) &&
+                (memo_status == ST_MAXITER ? memo_iters == max_it : memo_iters < max_it) && eps < memo_mineps) {
                 ps_status = memo_status; ps_iters = memo_iters; ps_eps = memo_eps;
                 nevals += memo_evals;
                 phase = PH_INNER_EXIT;
@@ -1284,8 +1287,11 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
                 }
                 wave_sum2_n(ys, ss, n);
                 const bool all_same = __ballot(!same) == 0ull;
-                // the pair goes into the free ring slot; it joins the history only if the
-                // curvature test accepts it
+                // the pair goes into ring slot lidx only if the curvature test accepts it: once the ring is
+                // full that slot holds the oldest pair, which the two-loop still reads after a rejected update
+                // (alpaqa LBFGS::update returns before it stores)
+                const bool valid = isfinite(ys) && !(ss < min_div) && !(ys < min_div);
+                const int nv = valid ? n : 0;                 // (a rejected pair is stored by no lane)
                 if (MC < 0 && hist_ready) {
                     // the prefetched LDS copy of the history gets the new pair too; the wait comes before
                     // this step's first global stores so that it does not have to drain them
@@ -1294,15 +1300,14 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
 #pragma unroll
                         for (int e = 0; e < NE; e++) {
                             const int j = lane + 64 * e;
-                            if (j < n) { hist[(int)lidx * n + j] = s.v[e]; hist[(P + (int)lidx) * n + j] = yv.v[e]; }
+                            if (j < nv) { hist[(int)lidx * n + j] = s.v[e]; hist[(P + (int)lidx) * n + j] = yv.v[e]; }
                         }
                     }
                 }
-                strow<NE>(w.S + ((size_t)a * c.M + lidx) * n, n, lane, s);
-                strow<NE>(w.Y + ((size_t)a * c.M + lidx) * n, n, lane, yv);
+                strow<NE>(w.S + ((size_t)a * c.M + lidx) * n, nv, lane, s);
+                strow<NE>(w.Y + ((size_t)a * c.M + lidx) * n, nv, lane, yv);
                 X = xp; G = gq;
                 strow<NE>(w.xk + an, n, lane, xp); strow<NE>(w.gk + an, n, lane, gq);
-                const bool valid = isfinite(ys) && !(ss < min_div) && !(ys < min_div);
                 if (valid) { lidx = lidx + 1 < c.M ? lidx + 1 : 0; lfull |= lidx == 0; }
                 if (noprog > 0 || k % c.max_no_progress == 0) noprog = all_same ? noprog + 1 : 0;
             }
@@ -1333,8 +1338,8 @@ __device__ int advance_agent(const DevCfg &cfg, const Workspace &ws, int a, int 
             const int out_of_time = inner_tot >= c.max_total_inner ||
                                     (c.max_total_evals > 0 && nevals >= c.max_total_evals);
             const int backtrack = !conv && !overwrite && !out_of_time;
-            // (memo for PH_OUTER_BEGIN: only a run that ended without progress / non-finite inside its limits)
-            if (backtrack && m == 0 && (ps_status == ST_NOPROGRESS || ps_status == ST_NOTFINITE)) {
+            // (memo for PH_OUTER_BEGIN: a run that ended without progress / non-finite / on its iteration limit)
+            if (backtrack && m == 0 && (ps_status == ST_NOPROGRESS || ps_status == ST_NOTFINITE || ps_status == ST_MAXITER)) {
                 if (memo_status == 0) {       // a real run: remember it (a replayed one keeps the memo as it is)
                     memo_status = ps_status; memo_iters = ps_iters; memo_evals = nevals - run_ev0;
                     memo_mineps = run_mineps; memo_eps = ps_eps;
